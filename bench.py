@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the Puzzle-15 PPO rollout on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one full `PPOCollector.collect()` over the workload: reset+scramble, the fused
 step/observe/reward/mask + policy forward + Gumbel sampling rollout, the GAE pass, compaction into
 the reference merge order, and (N > 1) the RCCL gather of the finished trajectories to rank 0.
 1 env-step = 1 trajectory record.  Weak scaling: every GPU gets --envs episodes.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, runs W warm-up and K timed steps and prints ONE JSON line (rank 0) with the
+driver's contract fields plus
   "roofline":     dominant kernel (rollout) against the f32 MFMA peak, measured with HIP events
                   around the kernel on its own stream (tw_collect_stats.ms_rollout)
+--dump-outputs DIR writes what the last timed step returned (a seeded sample of its records) as
+DIR/<field>.npy.  --full adds the measurements that take runs of their own (N = 1):
+  the f16 modes and BASELINE configs 1, 2, 5 as side entries, and
   "cpu_baseline": the CPU oracle (reference algorithm restated in C, rayon pool -> pthreads)
                   timed on this box's host cores over a bounded sample of the same workload.
 """
@@ -238,6 +242,38 @@ def headline(args, world, use_dist, total_records, wall, records, ms_rollout, E_
     }
 
 
+DUMP_BYTES = 64_000_000           # --dump-outputs: at most this much in all (64 MB)
+DUMP_SEED = 0
+
+
+def dump_outputs(fields, out_dir, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """Writes a collect's result (name -> device tensor, as `CollectedData.to_torch()` or the gather give it) as out_dir/<name>.npy:
+    floats and 8/16-bit integers as float32, wider integers as float64 (both exact).  Fields of equal length (per record, per
+    episode) share one row sample; the smallest group is taken first, whole if it fits in its share, and every group gets a seeded,
+    sorted sample of as many rows as its share of the budget holds -- the same rows for the same arguments.  Returns {name: shape}."""
+    import torch
+    signed = {getattr(torch, f"uint{b}", None): getattr(torch, f"int{b}") for b in (16, 32, 64)}
+    groups = {}
+    for name, t in fields.items():
+        t = t.view(signed[t.dtype]) if t.dtype in signed else t       # (index_select has no unsigned wide kernels; the values fit)
+        dt = np.float32 if (t.is_floating_point() or t.element_size() <= 2) else np.float64
+        width = t[0].numel() if t.shape[0] else 1
+        groups.setdefault(int(t.shape[0]), []).append((name, t, dt, width * np.dtype(dt).itemsize))
+    os.makedirs(out_dir, exist_ok=True)
+    left, shapes = budget - 4096 * len(fields), {}         # (room for the .npy headers)
+    for i, (rows, fs) in enumerate(sorted(groups.items(), key=lambda g: g[0] * sum(f[3] for f in g[1]))):
+        row_bytes = sum(f[3] for f in fs)
+        k = min(rows, left // (len(groups) - i) // row_bytes if i < len(groups) - 1 else left // row_bytes)
+        idx = np.arange(rows) if k == rows else np.sort(np.random.default_rng(seed + rows).choice(rows, k, replace=False))
+        idx_t = torch.from_numpy(idx).to(fs[0][1].device)
+        for name, t, dt, _ in fs:
+            a = t.index_select(0, idx_t).cpu().numpy().astype(dt)
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            shapes[name] = list(a.shape)
+        left -= k * row_bytes
+    return shapes
+
+
 STRONG_TOTAL_ENVS = 2_097_152      # BASELINE.json config 4: "2M envs sharded over 8 x MI355X"
 
 
@@ -256,7 +292,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-twists", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time the side entries (f16 modes, BASELINE configs 1, 2, 5, evaluations) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"write the last timed step's result (a seeded sample of at most {DUMP_BYTES // 10**6} MB) as DIR/<field>.npy")
     ap.add_argument("--dry-launch", action="store_true", help="print the launch plan (ranks, command) as JSON and exit; needs no GPU")
     return ap.parse_args(argv)
 
@@ -380,15 +420,21 @@ def main():
         if os.environ.get("TW_GATHER", "torch") == "cabi" or rehearsal:
             comm = Comm()
 
-    def step(i):
+    kept = []                             # --dump-outputs: what the last timed step returned (rank 0's gathered result at N > 1)
+
+    def step(i, keep=False):
         seed = 1000 + i
         if use_dist:
             merged, datas = collect_sharded(coll, env, policy, seed=seed, dst=0, max_episode_records=t_max, gatherer=gatherer,
                                             reserve_cus=reserve, step_episodes=step_eps, comm=comm)       # the gather is inside the timed region
             n = sum(len(d) for d in datas)
+            if keep and merged is not None:
+                kept.append(merged)
             del merged
             return n, {"ms_rollout": sum(d.stats["ms_rollout"] for d in datas)}
         data = coll.collect(env, policy, seed=seed)
+        if keep:
+            kept.append(data)
         return len(data), data.stats
 
     def fence():
@@ -405,7 +451,7 @@ def main():
     trace = [] if os.environ.get("TW_BENCH_TRACE") else None     # per-step wall times on stderr (diagnostic)
     for i in range(args.steps):
         ts = time.perf_counter()
-        n, st = step(args.warmup + i)
+        n, st = step(args.warmup + i, keep=args.dump_outputs is not None and i == args.steps - 1)
         records += n
         ms_rollout.append(st["ms_rollout"])
         if trace is not None:
@@ -428,7 +474,12 @@ def main():
         out = headline(args, world, use_dist, total_records, wall, records, ms_rollout, E_total, gather_info)
         if rehearsal:
             out["rehearsal"] = f"{world} ranks on ONE GPU over a stand-in transport (TW_BENCH_REHEARSAL): a run of the N > 1 code path, not a measurement"
-        if world == 1 and args.precision == "fp32" and not use_dist:
+        if kept:
+            res = kept.pop()
+            shapes = dump_outputs(res if isinstance(res, dict) else res.to_torch(), args.dump_outputs)
+            del res
+            print(f"[bench] outputs of the last timed step (seed {1000 + args.warmup + args.steps - 1}) in {args.dump_outputs}: {shapes}", file=sys.stderr)
+        if args.full and world == 1 and args.precision == "fp32" and not use_dist:
             # side measurements, not the headline: the same workload in the two f16-matrix-core modes.
             #   fp16x2: every f32 operand as two f16 terms -- logits within 5e-8 of the reference f32 arithmetic on sampled
             #           records (tests/tools/acc_modes.py; the exact f32 mode is within 2e-8), tests allow BASELINE.json's 1e-5
@@ -455,7 +506,7 @@ def main():
             out["f16_input_mode"] = side_mode("fp16")
             # BASELINE.json's other single-GPU configurations on the same clock (side entries, outside the headline's timed region)
             out.update(side_configs(twisterl, torch))
-        if not args.no_cpu_baseline and world == 1 and not use_dist:     # timed on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not use_dist:     # timed on rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(arrs, obs_perms, act_perms, side, args.difficulty, args.cpu_seconds, args.cpu_threads)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

@@ -3,7 +3,7 @@
 set -e
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/f16prof; mkdir -p $out
-python3 bench.py --precision fp16 --steps 5 --warmup 2 > $out/bench_f16_p15.json 2> $out/bench_f16_p15.err
+python3 bench.py --full --precision fp16 --steps 5 --warmup 2 > $out/bench_f16_p15.json 2> $out/bench_f16_p15.err
 python3 bench.py --precision fp16 --puzzle 8 --envs 65536 --difficulty 32 --no-twists --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_f16_p8_65k.json 2>> $out/bench_f16_p15.err
 python3 bench.py --precision fp32 --puzzle 8 --envs 65536 --difficulty 32 --no-twists --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_f32_p8_65k.json 2>> $out/bench_f16_p15.err
 (cd /tmp && rocprofv3 --kernel-trace --stats -d $out/stats -o s -f csv -- python3 $OLDPWD/bench.py --precision fp16 --steps 5 --warmup 2 --no-cpu-baseline > $out/stats.log 2>&1)

@@ -5,8 +5,8 @@
 set -e
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/r04; mkdir -p $out
-python3 bench.py --steps 10 --warmup 3 > $out/bench.json 2> $out/bench.err
-(cd /tmp && rocprofv3 --kernel-trace --stats -d $out/stats -o s -f csv -- python3 $OLDPWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $out/stats.log 2>&1)
+python3 bench.py --full --steps 10 --warmup 3 > $out/bench.json 2> $out/bench.err
+(cd /tmp && rocprofv3 --kernel-trace --stats -d $out/stats -o s -f csv -- python3 $OLDPWD/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $out/stats.log 2>&1)
 echo "[profile_r04] bench + kernel stats done"
 mkdir -p $out/traffic
 for p in fp32 fp16x2 fp16; do

@@ -149,3 +149,47 @@ def test_traffic_profile_is_not_older_than_the_newest_bench_round():
     d = json.load(open(os.path.join(ROOT, newest)))
     fin = d["tw::finalize_ppo_kernel"]["bytes_per_record"]
     assert 98.0 <= fin <= 120.0, fin                                            # each padded record is read once (round 4; 188 before)
+
+
+def test_side_measurements_are_opt_in():
+    """A plain run times the headline alone; the side entries and the CPU baseline run only with --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 5 and plain.warmup == 2
+    full = bench.parse_args(["--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert full.full is True and full.no_cpu_baseline is True and full.dump_outputs == "out"
+    r = _run(["--gpus", "2", "--full", "--dump-outputs", "out", "--dry-launch"])
+    assert r.returncode == 0, r.stderr
+    cmd = json.loads(r.stdout.strip().splitlines()[-1])["command"]
+    assert cmd[cmd.index(BENCH) + 1:] == ["--gpus", "2", "--full", "--dump-outputs", "out"]      # the ranks get both options
+
+
+def test_dump_outputs_is_seeded_exact_and_bounded(tmp_path):
+    """--dump-outputs on a stand-in result of the collector's layout: float32 / float64 files only, integer fields exact, per-episode
+    fields whole, a sorted sample of the records that is the same on every call, the same rows in every per-record field, and the
+    whole dump within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, E = 400_000, 2_000
+    g = torch.Generator().manual_seed(3)
+    rid = torch.arange(n, dtype=torch.float32)
+    fields = {"obs": torch.randint(0, 256, (n, 16), generator=g, dtype=torch.uint8), "logits": torch.stack([rid] * 4, 1),
+              "perms": torch.randint(-1, 2, (n,), generator=g, dtype=torch.int8), "values": rid.clone(), "rewards": torch.randn(n, generator=g),
+              "actions": torch.randint(0, 4, (n,), generator=g, dtype=torch.uint8), "advs": torch.randn(n, generator=g), "rets": torch.randn(n, generator=g),
+              "ep_len": torch.full((E,), 200, dtype=torch.int32).to(torch.uint32), "ep_start": (torch.arange(E, dtype=torch.int64) * 200 + 2**40).to(torch.uint64)}
+    budget = 8 << 20
+    a, b = tmp_path / "a", tmp_path / "b"
+    shapes = bench.dump_outputs(fields, str(a), budget=budget)
+    assert shapes == bench.dump_outputs(fields, str(b), budget=budget)
+    assert set(shapes) == set(fields) and shapes["ep_len"] == [E] and shapes["obs"][1] == 16 and 0 < shapes["values"][0] < n
+    assert sum(f.stat().st_size for f in a.iterdir()) <= budget
+    load = lambda d, k: np.load(d / (k + ".npy"))
+    for k in fields:
+        assert load(a, k).dtype in (np.float32, np.float64) and np.array_equal(load(a, k), load(b, k)), k
+    rows = load(a, "values").astype(np.int64)                      # the record ids of the sample
+    assert np.all(np.diff(rows) > 0) and np.array_equal(load(a, "logits")[:, 2].astype(np.int64), rows)
+    assert np.array_equal(load(a, "obs"), fields["obs"].numpy()[rows]) and np.array_equal(load(a, "perms"), fields["perms"].numpy()[rows])
+    assert np.array_equal(load(a, "ep_start").astype(np.int64), fields["ep_start"].view(torch.int64).numpy())     # > 2**24: float64
