@@ -57,6 +57,25 @@ __device__ __forceinline__ float relu_lim_v(float x, float lim)
     return y;
 }
 
+// gumbel_argmax4 for a wave whose lanes l and l^32 carry the same episode (the same logits and draw): the lower half transforms
+// uniforms 0 and 1, the upper half 2 and 3 -- the same operations on other lanes, so the same bits -- and two v_permlane32_swap
+// give every lane all four perturbed logits; the argmax is gumbel_argmax4's (strict '>', first max wins, NaN never wins).
+__device__ __forceinline__ int gumbel_argmax4_halves(const float l[4], const u32x4 w, bool upper)
+{
+    const uint32_t w0 = upper ? w.z : w.x, w1 = upper ? w.w : w.y;
+    const float l0 = upper ? l[2] : l[0], l1 = upper ? l[3] : l[1];
+    const float g0 = l0 - tw_logf(__builtin_fabsf(tw_logf(u32_to_unit(w0))));
+    const float g1 = l1 - tw_logf(__builtin_fabsf(tw_logf(u32_to_unit(w1))));
+    // swap(x, x): the first result holds the lower half's x in every lane, the second the upper half's
+    const auto s0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(g0), __float_as_uint(g0), false, false);
+    const auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(g1), __float_as_uint(g1), false, false);
+    const float g[4] = {__uint_as_float(s0[0]), __uint_as_float(s1[0]), __uint_as_float(s0[1]), __uint_as_float(s1[1])};
+    int best = 0; float bv = g[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i) if (g[i] > bv) { bv = g[i]; best = i; }
+    return best;
+}
+
 #ifdef TW_ABLATE   // timing-only switches of the diagnostic build, per translation unit (TW_ENG_DBG: 4 = no weight / table streams)
 static __device__ int g_eng_dbg;
 #endif
@@ -119,7 +138,7 @@ struct Engine3 {
     PolicyDev pol;
     int tid, lane, wave, j, h;
     uint32_t voff;                                          // lane*16: per-lane byte offset inside a DMA piece
-    int bias_row, zero_row, n_chunks, rp;                   // rp: ring slot of chunk 0 of the next forward
+    int bias_row, zero_row, n_chunks;
     float emb_lim, common_lim;                              // 0 (ReLU) or -inf (none): relu_lim()
     float *lds_w, *lds_t, *lds_b1, *lds_wh, *lds_bh, *lds_wn;   // lds_wn: head weights in natural order [output 0..4][hidden]
     const uint8_t *perm_obs, *perm_act;
@@ -202,7 +221,6 @@ struct Engine3 {
         // chunks 0 and 1 of the first forward into slots 0 and 1
 #pragma unroll
         for (int op = 0; op < NOPS; ++op) { stream_op(0, 0, op); stream_op(n_chunks > 1 ? 1 : 0, 1, op); }
-        rp = 0;
     }
     __device__ __forceinline__ void begin2() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
     __device__ __forceinline__ void end() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -231,19 +249,24 @@ struct Engine3 {
         }
     }
 
+    // The four maxes in one string, b[0] first: b[0] is the only element the next MFMA reads (b[u] feeds k-step u, NT MFMAs apart),
+    // and the three maxes behind it are the two VALU-write -> MFMA-read wait states it needs -- no s_nop per element.
     __device__ __forceinline__ void finish_b(f32x4 &b) const
     {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) b[u] = relu_lim(b[u], emb_lim);
+        float x0 = b[0], x1 = b[1], x2 = b[2], x3 = b[3];
+        asm("v_max_f32 %0, %4, %0\n\tv_max_f32 %1, %4, %1\n\tv_max_f32 %2, %4, %2\n\tv_max_f32 %3, %4, %3"
+            : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "s"(emb_lim));
+        b[0] = x0; b[1] = x1; b[2] = x2; b[3] = x3;
     }
 
     // One group of 4*NT MFMAs with B operands `bq`, while (a) the gather of the NEXT group is read
-    // through the ONE set of per-row LDS pointers `ga` (+ 4*ng floats) and summed into bnext, (b) the A
+    // through the ONE set of per-row LDS pointers `ga` (+ goff floats: ring slot and k-step half, an
+    // immediate of the reads) and summed into bnext, (b) the A
     // operands of the following k-steps are fetched (after the group's last k-step: k-step kp0+4 of the
     // same slot, or k-step 0 of the next slot `wn_base` when LAST), (c) DMA ops [op0, op1) are issued.
     template <bool HAVE_NEXT_GATHER, bool LAST, bool CROSS>
     __device__ __forceinline__ void group(f32x16 (&acc)[NT], f32x4 (&aw)[NQ], const f32x4 bq, const float *w_base, int kp0,
-                                          const float *wn_base, lds_cfloat *const (&ga)[NC + 1], int ng, f32x4 &bnext,
+                                          const float *wn_base, lds_cfloat *const (&ga)[NC + 1], int goff, f32x4 &bnext,
                                           int s_chunk, int s_slot, int op0, int op1)
     {
         constexpr int LAT = M >= 16 ? 4 : 1;
@@ -274,7 +297,7 @@ struct Engine3 {
             if constexpr (HAVE_NEXT_GATHER) {
 #pragma unroll
                 for (int q = 0; q <= ((DBG & 1) ? 0 : NC); ++q)
-                    if (rd_slot(q) == m) rd[q] = *reinterpret_cast<const __attribute__((address_space(3))) f32x4 *>(ga[q] + 4 * ng);
+                    if (rd_slot(q) == m) rd[q] = *reinterpret_cast<const __attribute__((address_space(3))) f32x4 *>(ga[q] + goff);
 #pragma unroll
                 for (int q = 0; q <= ((DBG & 1) ? 0 : NC); ++q)
                     if (add_slot(q) == m) {
@@ -291,6 +314,33 @@ struct Engine3 {
         }
     }
 
+    // One chunk c in ring slot S0 (S1: chunk c+1, complete; S2: streamed now), all three compile-time facts, so every ring read
+    // has its slot in the immediate offset.  V: virtual steps per forward (n_chunks rounded up to a multiple of three).
+    template <int S0>
+    __device__ __forceinline__ void chunk(f32x16 (&acc)[NT], f32x4 (&aw)[NQ], f32x4 &bq, const float *wl, lds_cfloat *const (&ga)[NC + 1],
+                                          int c, int V)
+    {
+        constexpr int S1 = (S0 + 1) % 3, S2 = (S0 + 2) % 3;
+        const float *wb = wl + S0 * WSLOT, *wn = wl + S1 * WSLOT;
+        // virtual step c+2 is streamed now: a chunk of this forward, a chunk of the next one (>= V), or a bubble (>= n_chunks, < V:
+        // gets chunk 0's data, never read)
+        int sc = c + 2;
+        if (sc >= n_chunks) sc = sc >= V ? sc - V : 0;
+        constexpr int H0 = (NOPS + 1) / 2;
+        f32x4 b1v, b2v;
+        group<true, false, false>(acc, aw, bq, wb, 0, wn, ga, S0 * R3_TSLOT + 4, b1v, sc, S2, 0, H0);
+        // always prefetch across the boundary: after the last chunk the speculative gather (rows of the
+        // NEXT timestep are not known yet) and the A operands of the slot after it are discarded
+        group<true, true, true>(acc, aw, b1v, wb, 4, wn, ga, S1 * R3_TSLOT, b2v, sc, S2, H0, NOPS);
+        bq = b2v;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of virtual step c+2 have landed
+        __syncthreads();
+    }
+
+    // Ring positions are compile-time facts: chunk c of every forward sits in slot c % 3.  With n_chunks not a multiple of three
+    // the sequence is padded with bubble steps that exist only in the ring (no MFMAs, no barrier): chunk 0 of the next forward is
+    // streamed by the last chunks as usual, and what the bubble's place would have streamed (chunk 1 of the next forward, into the
+    // slot the last chunk frees) is issued behind the last barrier and waited for at the start of the next forward.
     __device__ __forceinline__ void forward(const int (&rowoff)[NC], float (&lg)[4], float &value)
     {
         f32x16 acc[NT];
@@ -299,15 +349,22 @@ struct Engine3 {
 #pragma unroll
             for (int g = 0; g < 16; ++g) acc[r][g] = 0.0f;
 
-        const int lane_w = (h * NQ * 32 + j) * 4;
-        // ONE set of gather pointers (bias row + NC cells) into the ring slot being gathered from; it is
-        // advanced by the slot distance once per chunk (NC+1 VALU adds per 8*NT MFMAs)
-        lds_cfloat *ga[NC + 1];     // 32-bit LDS pointers (generic pointers would cost two VGPRs each)
-        ga[0] = (lds_cfloat *)(lds_t + rp * R3_TSLOT + bias_row * LSTR + h * (KC / 2));
-#pragma unroll
-        for (int q = 0; q < NC; ++q) ga[q + 1] = (lds_cfloat *)(lds_t + rp * R3_TSLOT) + rowoff[q];
+        const int V = (n_chunks + 2) / 3 * 3;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the previous forward's tail streams (chunk 1 of this one) have landed
+        __syncthreads();
 
-        // exposed once per forward: the first group's B operands and the first A operands
+        const float *wl = lds_w + (h * NQ * 32 + j) * 4;
+        // ONE set of gather pointers (bias row + NC cells) for the whole forward; the slot is an immediate offset of each read
+        lds_cfloat *ga[NC + 1];     // 32-bit LDS pointers (generic pointers would cost two VGPRs each)
+        ga[0] = (lds_cfloat *)(lds_t + bias_row * LSTR + h * (KC / 2));
+#pragma unroll
+        for (int q = 0; q < NC; ++q) ga[q + 1] = (lds_cfloat *)lds_t + rowoff[q];
+        // the addresses in full: left to itself hipcc folds the table's base (48 KiB) into the immediates, which then overflow the
+        // 16-bit offset for slots 1 and 2 -- and it keeps a second set of row addresses for those
+#pragma unroll
+        for (int q = 0; q <= NC; ++q) asm volatile("" : "+v"(ga[q]));
+
+        // exposed once per forward: the first group's B operands and the first A operands (slot 0)
         f32x4 bq;
         {
             const f32x4 r0 = *reinterpret_cast<const __attribute__((address_space(3))) f32x4 *>(ga[0]);
@@ -324,31 +381,21 @@ struct Engine3 {
         }
         f32x4 aw[NQ];
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) aw[q] = *reinterpret_cast<const f32x4 *>(lds_w + rp * WSLOT + lane_w + q * 128);
+        for (int q = 0; q < NQ; ++q) aw[q] = *reinterpret_cast<const f32x4 *>(wl + q * 128);
 
-        int s0 = rp;                                         // ring slot of the current chunk
-        for (int c = 0; c < n_chunks; ++c) {
-            const int s1 = s0 == 2 ? 0 : s0 + 1, s2 = s1 == 2 ? 0 : s1 + 1;
-            const float *wb = lds_w + s0 * WSLOT + lane_w, *wn = lds_w + s1 * WSLOT + lane_w;
-            int sc = c + 2; if (sc >= n_chunks) sc -= n_chunks;      // chunk streamed now (wraps into the next forward)
-            if (n_chunks == 1) sc = 0;
-            constexpr int H0 = (NOPS + 1) / 2;
-            f32x4 b1v, b2v;
-            group<true, false, false>(acc, aw, bq, wb, 0, wn, ga, 1, b1v, sc, s2, 0, H0);
-            {   // point the gather at the next slot (group 1's MFMAs only use registers)
-                const int delta = (s1 - s0) * R3_TSLOT;
-#pragma unroll
-                for (int q = 0; q <= NC; ++q) ga[q] += delta;
-            }
-            // always prefetch across the boundary: after the last chunk the speculative gather (rows of the
-            // NEXT timestep are not known yet) is discarded, the A operands of its first k-step are kept
-            group<true, true, true>(acc, aw, b1v, wb, 4, wn, ga, 0, b2v, sc, s2, H0, NOPS);
-            bq = b2v;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of chunk c+2 have landed
-            __syncthreads();
-            s0 = s1;
+        for (int c = 0; c < n_chunks; c += 3) {
+            chunk<0>(acc, aw, bq, wl, ga, c, V);
+            if (c + 1 < n_chunks) chunk<1>(acc, aw, bq, wl, ga, c + 1, V);
+            if (c + 2 < n_chunks) chunk<2>(acc, aw, bq, wl, ga, c + 2, V);
         }
-        rp = s0;
+        if (V != n_chunks) {        // the bubble's streams: chunk 0 (only if no chunk streamed it) and chunk 1 of the next forward
+            const int c1 = n_chunks > 1 ? 1 : 0;
+#pragma unroll
+            for (int op = 0; op < NOPS; ++op) {
+                if (V - 2 >= n_chunks) stream_op(0, 0, op);
+                stream_op(c1, 1, op);
+            }
+        }
 
         if constexpr (DBG & 8) {
             value = 0.0f;

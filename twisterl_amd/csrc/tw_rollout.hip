@@ -249,7 +249,8 @@ __global__ void __launch_bounds__((Geom<NT, NC, DBG, NW>::WAVES * 64), ((NW == 8
             for (int i = 0; i < 4; ++i) lg[i] = ((mb >> i) & 1u) ? lg[i] : -1e10f;   // policy.rs:62
             rew = puzzle_reward(st, env);
             const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
-            action = gumbel_argmax4(lg, gw);
+            if constexpr (NW == 8) action = gumbel_argmax4_halves(lg, gw, h != 0);   // (lanes j and j+32: one episode)
+            else action = gumbel_argmax4(lg, gw);
         }
         // ---- push the record (ppo.rs:71-76), then is_final / step (ppo.rs:78-79) --------------
         if (alive) {
