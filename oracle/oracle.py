@@ -316,6 +316,32 @@ class Policy:
                                  C.c_int(arith), lg, C.byref(v))
         return [float(x) for x in lg][: self.n_actions], float(v.value)
 
+    def forward_batch(self, obs, masks, perms, arith=ARITH_REF, num_threads=1):
+        """`forward` over n records at once: obs [n, cells] ids, masks [n, n_actions] bools, perms [n] (-1 = None) ->
+        (masked logits [n, n_actions] f32, values [n] f32), the same bits as n `forward` calls, on `num_threads` threads."""
+        o = np.ascontiguousarray(obs, dtype=np.int64)
+        n = o.shape[0]
+        if n == 0:
+            return np.empty((0, self.n_actions), np.float32), np.empty(0, np.float32)
+        o = o.reshape(n, -1)
+        m = np.ascontiguousarray(np.asarray(masks).reshape(n, self.n_actions), dtype=np.uint8)
+        p = np.ascontiguousarray(np.asarray(perms).reshape(n), dtype=np.int32)
+        obs_size = int(self.pol.obs_size)
+        if (o.min() < 0 or o.max() >= obs_size):
+            raise ValueError(f"obs ids must lie in [0, {obs_size})")
+        if (p.min() < -1 or p.max() >= self.n_perms):
+            raise ValueError(f"perms must lie in [-1, {self.n_perms})")
+        if o.shape[1] > MAX_CELLS * 4:
+            raise ValueError("too many obs ids per record")
+        lg = np.empty((n, self.n_actions), np.float32)
+        v = np.empty(n, np.float32)
+        L = lib()
+        L.two_policy_forward_batch(C.byref(self.pol), o.ctypes.data_as(C.POINTER(C.c_int64)), C.c_uint64(n),
+                                   C.c_int(o.shape[1]), m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                   p.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int(arith), C.c_int(max(1, int(num_threads))),
+                                   _fp(lg), _fp(v))
+        return lg, v
+
     def predict(self, obs, masks, perm=-1, arith=ARITH_REF):
         o, n = self._obs(obs)
         pr = (C.c_float * max(self.n_actions, 1))()

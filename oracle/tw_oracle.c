@@ -382,6 +382,45 @@ void two_policy_forward(const two_policy *pol, const int64_t *obs, int n_obs,
         masked_logits_out[i] = masks[i] ? logits[i] : -1e10f;
 }
 
+typedef struct {
+    const two_policy *pol; const int64_t *obs; uint64_t n; int cells; const uint8_t *masks; const int32_t *perms;
+    int arith; float *logits; float *values; atomic_ullong next;
+} fwd_batch_job;
+
+#define TWO_FWD_BLOCK 256ULL
+static void *fwd_batch_worker(void *arg)
+{
+    fwd_batch_job *j = (fwd_batch_job *)arg;
+    const int A = j->pol->n_actions;
+    for (;;) {
+        const unsigned long long r0 = atomic_fetch_add(&j->next, TWO_FWD_BLOCK);
+        if (r0 >= j->n) break;
+        const unsigned long long r1 = r0 + TWO_FWD_BLOCK < j->n ? r0 + TWO_FWD_BLOCK : j->n;
+        for (unsigned long long r = r0; r < r1; ++r)
+            two_policy_forward(j->pol, j->obs + (size_t)r * j->cells, j->cells, j->masks + (size_t)r * A, j->perms[r],
+                               j->arith, j->logits + (size_t)r * A, j->values + r);
+    }
+    return NULL;
+}
+
+void two_policy_forward_batch(const two_policy *pol, const int64_t *obs, uint64_t n, int cells,
+                              const uint8_t *masks, const int32_t *perms, int arith, int num_threads,
+                              float *logits_out, float *values_out)
+{
+    fwd_batch_job job; job.pol = pol; job.obs = obs; job.n = n; job.cells = cells; job.masks = masks; job.perms = perms;
+    job.arith = arith; job.logits = logits_out; job.values = values_out;
+    atomic_init(&job.next, 0ULL);
+    int nt = num_threads < 1 ? 1 : num_threads;
+    if (nt == 1) {
+        fwd_batch_worker(&job);
+    } else {
+        pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nt);
+        for (int i = 0; i < nt; ++i) pthread_create(&th[i], NULL, fwd_batch_worker, &job);
+        for (int i = 0; i < nt; ++i) pthread_join(th[i], NULL);
+        free(th);
+    }
+}
+
 static void masked_softmax(const float *logits, const uint8_t *masks, int n, float *probs)
 {
     /* policy.rs:43-47 / 118-124: no max-subtraction, eps 1e-6 */

@@ -107,6 +107,11 @@ void two_policy_raw_predict(const two_policy *pol, const int64_t *obs, int n_obs
 void two_policy_forward(const two_policy *pol, const int64_t *obs, int n_obs,
                         const uint8_t *masks, int perm, int arith,
                         float *masked_logits_out, float *value_out);
+/* two_policy_forward over n records (obs[n*cells], masks[n*n_actions], perms[n]), split over num_threads threads
+ * the way the collectors split episodes (an atomic counter hands out blocks of records); same bits as n single calls */
+void two_policy_forward_batch(const two_policy *pol, const int64_t *obs, uint64_t n, int cells,
+                              const uint8_t *masks, const int32_t *perms, int arith, int num_threads,
+                              float *logits_out, float *values_out);
 /* Policy::predict_with_perm (policy.rs:39-49) given an explicit perm */
 void two_policy_predict(const two_policy *pol, const int64_t *obs, int n_obs,
                         const uint8_t *masks, int perm, int arith,

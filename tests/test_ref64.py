@@ -1,0 +1,173 @@
+"""CPU: the oracle's batched forward and the float64 reference (tests/ref64.py) the GPU tolerance tests stand on.
+
+* Policy.forward_batch gives the bits of one Policy.forward per record in every arithmetic mode, with and without twists,
+  with partial masks, on one thread and on several.
+* The float64 forward stays within 1e-5 of the oracle's reference order and of its fma chain, and the float64 GAE within
+  1e-5 of the oracle's f32 GAE at the benchmark's horizon and beyond.
+* Both float64 pieces reproduce the reference's own known answers (tests/golden/reference_known_answers.json).
+"""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from tests.ref64 import MASKED, embedding_bag_f64, forward_f64, gae_f64, gae_f64_episodes, linear_f64
+from tests.util import make_deep_policy_arrays, make_policy_arrays, puzzle_transpose_twist, trained_puzzle8_arrays
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_known_answers.json")
+
+
+def _records(n2, n, seed, all_legal=False):
+    """n records of random boards of an n2-cell puzzle: obs ids 16c + tile, random masks with at least one legal move,
+    twists drawn from {-1, 0, 1}."""
+    rng = np.random.default_rng(seed)
+    boards = np.argsort(rng.random((n, n2)), axis=1)
+    obs = np.arange(n2)[None, :] * n2 + boards
+    masks = np.ones((n, 4), bool) if all_legal else rng.random((n, 4)) < 0.6
+    masks[np.arange(n), rng.integers(0, 4, n)] = True
+    perms = rng.integers(-1, 2, n).astype(np.int32)
+    return obs, masks, perms
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("arith", [0, 1, 2])
+def test_forward_batch_equals_per_record_forward(oracle, arith):
+    arrs = make_policy_arrays(16, seed=4, emb=64, hidden=32)
+    op, ap = puzzle_transpose_twist(4)
+    pol = oracle.Policy(*arrs, op, ap)
+    obs, masks, perms = _records(16, 400, seed=arith)
+    assert set(perms.tolist()) == {-1, 0, 1} and not masks.all()
+    want_l = np.empty((400, 4), np.float32)
+    want_v = np.empty(400, np.float32)
+    for r in range(400):
+        lg, v = pol.forward(obs[r].tolist(), masks[r].tolist(), perm=int(perms[r]), arith=arith)
+        want_l[r], want_v[r] = lg, v
+    for threads in (1, 3):
+        lg, v = pol.forward_batch(obs, masks, perms, arith=arith, num_threads=threads)
+        assert np.array_equal(_bits(lg), _bits(want_l)), threads
+        assert np.array_equal(_bits(v), _bits(want_v)), threads
+    assert np.all((want_l == np.float32(MASKED)) == ~masks)
+
+
+def test_forward_batch_rejects_out_of_range_records(oracle):
+    arrs = make_policy_arrays(9, seed=0, emb=32, hidden=32)
+    pol = oracle.Policy(*arrs)
+    obs, masks, _ = _records(9, 4, seed=0)
+    with pytest.raises(ValueError):
+        pol.forward_batch(obs + 81, masks, np.full(4, -1))
+    with pytest.raises(ValueError):
+        pol.forward_batch(obs, masks, np.zeros(4))              # no twists in this policy
+
+
+def _policies():
+    op16, ap16 = puzzle_transpose_twist(4)
+    op9, ap9 = puzzle_transpose_twist(3)
+    return {
+        "synthetic_scale1": (16, make_policy_arrays(16, seed=0), op16, ap16),
+        "synthetic_scale3": (16, make_policy_arrays(16, seed=1, scale=3.0), op16, ap16),
+        "trained_puzzle8": (9, trained_puzzle8_arrays(), op9, ap9),
+        "deep": (16, make_deep_policy_arrays(16, seed=2, emb=96, common=(128, 64), policy_layers=(32,), value_layers=(48, 16)),
+                 op16, ap16),
+    }
+
+
+@pytest.mark.parametrize("name", ["synthetic_scale1", "synthetic_scale3", "trained_puzzle8", "deep"])
+def test_forward_f64_within_1e5_of_the_oracle(oracle, name):
+    n2, arrs, op, ap = _policies()[name]
+    pol = oracle.Policy(*arrs, op, ap)
+    obs, masks, perms = _records(n2, 3000, seed=7)
+    l64, v64 = forward_f64(arrs, op, ap, obs, masks, perms, chunk=1000)
+    assert np.all((l64 == MASKED) == ~masks)
+    assert np.all(np.float32(l64[~masks]) == np.float32(MASKED))
+    for arith in (oracle.ARITH_REF, oracle.ARITH_CHAIN):
+        lg, v = pol.forward_batch(obs, masks, perms, arith=arith, num_threads=4)
+        assert np.array_equal(lg == np.float32(MASKED), ~masks)
+        dl = float(np.max(np.abs(lg[masks] - l64[masks])))
+        dv = float(np.max(np.abs(v - v64)))
+        assert dl < 1e-5 and dv < 1e-5, (name, arith, dl, dv)
+    # the check is not vacuous: the reference's own scale keeps the logits and values away from zero
+    assert float(np.max(np.abs(l64[masks]))) > 1e-2 and float(np.max(np.abs(v64))) > 1e-2
+
+
+def test_forward_f64_twists_follow_the_reference(oracle):
+    """perm p: obs ids through obs_perms[p], logits gathered by act_perms[p] -- a transposed board under the transpose twist
+    sees the un-twisted forward of the original board, its logits permuted left<->up, right<->down."""
+    arrs = make_policy_arrays(9, seed=5, emb=64, hidden=32)
+    op, ap = puzzle_transpose_twist(3)
+    obs, masks, _ = _records(9, 200, seed=3, all_legal=True)
+    T = np.array([(i % 3) * 3 + (i // 3) for i in range(9)])
+    board = obs - np.arange(9) * 9
+    tboard = np.empty_like(board)
+    tboard[:, T] = T[board]
+    tobs = np.arange(9) * 9 + tboard
+    l0, v0 = forward_f64(arrs, [], [], obs, masks, np.full(200, -1))
+    l1, v1 = forward_f64(arrs, op, ap, tobs, masks, np.ones(200, np.int64))
+    np.testing.assert_allclose(v1, v0, rtol=0, atol=1e-12)
+    np.testing.assert_allclose(l1, l0[:, [1, 0, 3, 2]], rtol=0, atol=1e-12)
+
+
+def _episode(n, seed):
+    rng = np.random.default_rng(seed)
+    rews = np.full(n, np.float32(-0.5 / 256), np.float32)
+    rews[-1] = np.float32(1.0) if seed % 2 else np.float32(-0.5)
+    vals = rng.uniform(-1.0, 1.0, n).astype(np.float32)
+    return rews, vals
+
+
+@pytest.mark.parametrize("n", [1, 2, 257, 1022])
+def test_gae_f64_within_1e5_of_the_oracle(oracle, n):
+    for seed in range(4):
+        rews, vals = _episode(n, seed)
+        a32, r32 = oracle.gae(rews, vals, 0.995, 0.995)
+        a64, r64 = gae_f64(rews, vals, 0.995, 0.995)
+        assert float(np.max(np.abs(a32 - a64))) < 1e-5 and float(np.max(np.abs(r32 - r64))) < 1e-5, (n, seed)
+
+
+def test_gae_f64_episodes_equals_one_episode_at_a_time():
+    lens = [257, 1, 13, 257, 2, 100]
+    parts = [_episode(n, s) for s, n in enumerate(lens)]
+    rews = np.concatenate([p[0] for p in parts])
+    vals = np.concatenate([p[1] for p in parts])
+    a, r = gae_f64_episodes(rews, vals, lens, 0.995, 0.99)
+    s = 0
+    for n, (rw, vl) in zip(lens, parts):
+        a1, r1 = gae_f64(rw, vl, 0.995, 0.99)
+        assert np.array_equal(a[s:s + n], a1) and np.array_equal(r[s:s + n], r1)
+        s += n
+
+
+def test_known_answers_of_the_reference(oracle):
+    ka = json.load(open(GOLDEN))
+    for key in ("linear_forward", "linear_forward_relu"):
+        c = ka[key]
+        out = linear_f64(c["weights"], c["bias"], c["relu"], np.asarray([c["input"]]))
+        assert np.array_equal(out[0], np.asarray(c["out"], np.float64)), key
+        # the same Linear as a one-layer policy head of the oracle (an identity EmbeddingBag feeding it)
+        n_in = len(c["input"])
+        pol = oracle.Policy(np.eye(n_in, dtype=np.float32), np.zeros(n_in, np.float32), [],
+                            [(np.asarray(c["weights"], np.float32), np.asarray(c["bias"], np.float32), c["relu"])],
+                            [(np.zeros(n_in, np.float32), np.zeros(1, np.float32), False)], emb_relu=False)
+        for arith in (oracle.ARITH_REF, oracle.ARITH_CHAIN):
+            ids = [i for i, x in enumerate(c["input"]) for _ in range(int(x))]
+            lg, _ = pol.raw_predict(ids, arith=arith)
+            assert lg == c["out"], (key, arith)
+    c = ka["embedding_bag"]
+    out = embedding_bag_f64(c["vectors"], c["bias"], c["relu"], np.asarray([c["input"]]))
+    assert np.array_equal(out[0], np.asarray(c["out"], np.float64))
+    arrs = (np.asarray(c["vectors"], np.float32), np.asarray(c["bias"], np.float32), [],
+            [(np.eye(2, dtype=np.float32).reshape(-1), np.zeros(2, np.float32), False)],
+            [(np.zeros(2, np.float32), np.zeros(1, np.float32), False)])
+    l64, _ = forward_f64(arrs, [], [], np.asarray([c["input"]]), np.ones((1, 2), bool), [-1], emb_relu=c["relu"])
+    lg, _ = oracle.Policy(*arrs, emb_relu=c["relu"]).forward_batch(np.asarray([c["input"]]), np.ones((1, 2), bool), [-1])
+    assert l64[0].tolist() == c["out"] == lg[0].tolist()
+    c = ka["dummy_env_ppo"]
+    a64, r64 = gae_f64(c["rewards"], c["values"], c["gamma"], c["lambda"])
+    np.testing.assert_allclose(r64, c["derived_rets"], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(a64, c["derived_advs"], rtol=0, atol=1e-12)
+    a32, r32 = oracle.gae(c["rewards"], c["values"], c["gamma"], c["lambda"])
+    np.testing.assert_allclose(r32, r64, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(a32, a64, rtol=0, atol=1e-6)
