@@ -82,8 +82,7 @@ enum {
     TW_OPT_AZ_REUSE = 5,    /* lane-per-episode self-play kernel, how a node whose move takes its parent's move back finds   */
                             /* the stored output of its grandparent (same board): 0 product, 1 no reuse, 3 by the link only, */
                             /* 4 by the link while counting where the path level would have differed; 2 (the path level at   */
-                            /* any depth: returns different bytes, kept for the record) only in the TW_ABLATE build -- the   */
-                            /* product build refuses it with TW_ERR_INVALID                                                  */
+                            /* any depth, which returns different bytes) is refused with TW_ERR_INVALID                      */
     TW_OPT_AZ_VARIANT = 2   /* self-play with few deep searches: 0 automatic (walker-per-wave kernel where it applies),    */
                             /* 2 always the lane-per-episode kernel; walker kernel with a pinned shape: 3 / 4 / 5 / 6 =    */
                             /* two / one / four / eight walkers per workgroup, + 16 / + 32 = the 16- / 32-column engine,   */

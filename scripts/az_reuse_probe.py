@@ -1,7 +1,8 @@
 """Round 3, VERDICT item 1: how the lane-per-episode self-play kernel finds the grandparent whose stored network output a node
 that takes its parent's move back reuses.  For every case: the collect under TW_OPT_AZ_REUSE = 1 (no reuse: the baseline
-bytes), 3 (parent links), 0 (product: search path in LDS, parent links below PATH_DEPTH levels), 2 (round 2's first form: the path
-level whatever the depth), each repeated; and once under 4, which counts how the two ways disagree.
+bytes), 3 (parent links), 0 (product: search path in LDS, parent links below PATH_DEPTH levels), each repeated; and once under 4,
+which counts how the two ways disagree.  (Round 2's first form, 2 -- the path level whatever the depth --, is no longer built:
+its numbers are in profiles/r03_az_reuse_probe.txt.)
     python scripts/az_reuse_probe.py [repeats]"""
 import sys
 sys.path.insert(0, ".")
@@ -36,7 +37,7 @@ for E, S, MED, D, pol, fg in cases:
     coll = twisterl.collector.AZCollector(E, S, 1.41, MED, 1)
     res = {}
     with launch_option(TW_OPT_AZ_VARIANT, 2), launch_option(TW_OPT_FORCE_GEOM, fg):
-        for mode in (1, 3, 0, 2):
+        for mode in (1, 3, 0):
             with launch_option(TW_OPT_AZ_REUSE, mode):
                 ds = []
                 for r in range(reps if mode != 1 else 1):
@@ -49,7 +50,7 @@ for E, S, MED, D, pol, fg in cases:
             dg4 = digest(d4)
     base = res[1][0][0]
     print(f"E {E} searches {S} MED {MED} twists {pol is pol_t} launch {res[1][4]}x{res[1][5]}")
-    for mode, name in ((1, "no reuse"), (3, "parent links"), (0, "product"), (2, "path whatever the depth")):
+    for mode, name in ((1, "no reuse"), (3, "parent links"), (0, "product")):
         ds, ms, reused, fwd, _, _ = res[mode]
         print(f"   mode {mode} ({name}): {ms:8.2f} ms  reused {reused}/{fwd}  same bytes as no-reuse: {[x == base for x in ds]}  repeats identical: {len(set(ds)) == 1}")
     print(f"   mode 4 same bytes as no-reuse: {dg4 == base}; " + "; ".join(f"{n} {c}" for n, c in zip(NAMES, cnt)), flush=True)

@@ -17,11 +17,11 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
-# The diagnostic variant (TW_ABLATE=1 in the environment: -DTW_ABLATE, cycle stamps and knock-out switches) is a DIFFERENT
+# The diagnostic variant (TW_ABLATE=1 in the environment: -DTW_ABLATE, cycle stamps) is a DIFFERENT
 # library in its own directory: the product library is never overwritten by an instrumented build, and a process loads the
 # instrumented one only while TW_ABLATE is set.
 ABLATE = bool(os.environ.get("TW_ABLATE"))
-# A measurement variant (TW_VARIANT=<name> with TW_EXTRA_FLAGS=-D..., e.g. the builtin forms of the inline-asm MFMAs) likewise
+# A measurement variant (TW_VARIANT=<name> with TW_EXTRA_FLAGS=-D..., the two sides of an A/B experiment) likewise
 # builds into, and loads from, a directory of its own.
 VARIANT = os.environ.get("TW_VARIANT", "")
 LIB_DIR = os.path.join(PKG, "lib", "ablate") if ABLATE else os.path.join(PKG, "lib", "variants", VARIANT) if VARIANT else os.path.join(PKG, "lib")
@@ -97,7 +97,7 @@ def scan_hazards(verbose: bool = False) -> int:
 def build_library(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
     flags = list(FLAGS)
-    if ABLATE:                           # timing-only ablation variants of the kernels (profiling aid)
+    if ABLATE:                           # the same kernels with cycle stamps (tw_common.hpp; TW_STAMPS=1 prints them)
         flags.append("-DTW_ABLATE")
     if os.environ.get("TW_EXTRA_FLAGS"):
         flags += os.environ["TW_EXTRA_FLAGS"].split()

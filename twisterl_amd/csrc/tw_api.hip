@@ -255,12 +255,8 @@ extern "C" int tw_set_launch_option(int option, int value)
             if (value < 0 || (value != 0 && value < 1000)) { set_error("TW_OPT_AZ_TREE_BUDGET_MIN: %d cycles (0 = automatic, else >= 1000)", value); return TW_ERR_INVALID; }
             g_az_tree_budget_min.store(value); return TW_OK;
         case TW_OPT_AZ_REUSE:
-            if (value < 0 || value > 4) { set_error("TW_OPT_AZ_REUSE: value %d not in {0 .. 4}", value); return TW_ERR_INVALID; }
-#ifndef TW_ABLATE
-            // 2 reads the path level whatever the depth -- another board's output below PATH_DEPTH -- and skips the board check: it
-            // returns different bytes (profiles/r03_az_reuse_probe.txt).  Kept for the record in the diagnostic build only.
-            if (value == 2) { set_error("TW_OPT_AZ_REUSE: 2 is a diagnostic form (wrong below the path depth); the product build takes 0, 1, 3 or 4"); return TW_ERR_INVALID; }
-#endif
+            // (2, the path level whatever the depth, read another board's output below PATH_DEPTH: profiles/r03_az_reuse_probe.txt)
+            if (value < 0 || value > 4 || value == 2) { set_error("TW_OPT_AZ_REUSE: value %d not in {0, 1, 3, 4}", value); return TW_ERR_INVALID; }
             g_az_reuse.store(value); return TW_OK;
         default: set_error("tw_set_launch_option: unknown option %d", option); return TW_ERR_INVALID;
     }

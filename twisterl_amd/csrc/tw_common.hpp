@@ -12,6 +12,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdio>
+#include <cstdlib>
 
 #include "twisterl_hip.h"
 
@@ -38,10 +40,61 @@
 // Inline-asm MFMAs remain in the two f16 engines only (tw_engine16.hpp, tw_engine16x2.hpp: the accumulator as an in/out "v" operand;
 // with the builtin hipcc parks the embedding tiles in AGPRs and shuttles common-layer tiles around them: +17 % and 2.7 x,
 // profiles/r04_mfma_intrinsic_vs_asm.txt).  An asm MFMA gets no hazard padding from hipcc: twisterl_amd/build.py scans the assembly of
-// every build for that (scripts/scan_mfma_hazards.py).  -DTW_MFMA_INTRIN=<mask> compiles a site with the builtin instead (the
-// measurement: TW_VARIANT=intrin): bit 3 Engine16, bit 4 Engine16x2.  (Engine3S and Engine3T use the builtin since round 4.)
-#ifndef TW_MFMA_INTRIN
-#define TW_MFMA_INTRIN 0
+// every build for that (scripts/scan_mfma_hazards.py).  (Engine3S and Engine3T use the builtin since round 4.)
+
+// Cycle stamps of the diagnostic build (-DTW_ABLATE: `TW_ABLATE=1 python -m twisterl_amd.build`, a library of its own under lib/ablate/).
+// A kernel keeps per-wave sums of s_memtime differences and event counts in registers and flushes them with atomicAdd into a
+// __device__ array at its end; the host clears that array before the launch and prints it after, both only while TW_STAMPS is set.
+// In the product build every one of these expands to nothing: the stamps never change what runs.
+//   TW_STAMP_ARRAY(g, n)              the __device__ array of a kernel family (file scope)
+//   TW_STAMP_VARS(a = 0, b[4] = {})   per-wave sums (unsigned long long; a block or a class member)
+//   TW_STAMP(t)                       t = the cycle counter now (a new constant)
+//   TW_RESTAMP(t)                     t = the cycle counter now (t from TW_STAMP_VARS)
+//   TW_STAMP_ADD(acc, t0, t1)         acc += t1 - t0
+//   TW_STAMP_COUNT(acc, n)            acc += n
+//   TW_STAMP_USE(x)                   the next stamp is taken after x (a VGPR value) is complete
+//   TW_STAMP_FLUSH(cond, dst, v...)   if cond: atomicAdd(&dst[i], v_i) for each value
+//   TW_STAMPS_CLEAR(g)                host, before the launch: zero the array
+//   TW_STAMPS_REPORT(g, stream, h, { ... })   host, after the launch: wait for the stream, read the array into h[] and run the block
+#ifdef TW_ABLATE
+#define TW_STAMP_ARRAY(g, n)          __device__ unsigned long long g[n]
+#define TW_STAMP_VARS(...)            unsigned long long __VA_ARGS__
+#define TW_STAMP(t)                   const unsigned long long t = __builtin_readcyclecounter()
+#define TW_RESTAMP(t)                 ((t) = __builtin_readcyclecounter())
+#define TW_STAMP_ADD(acc, t0, t1)     ((acc) += (t1) - (t0))
+#define TW_STAMP_COUNT(acc, n)        ((acc) += (n))
+#define TW_STAMP_USE(x)               asm volatile("" :: "v"(x))
+#define TW_STAMP_FLUSH(cond, dst, ...)                                                                                        \
+    do {                                                                                                                      \
+        if (cond) {                                                                                                           \
+            const unsigned long long tw_v_[] = {__VA_ARGS__};                                                                 \
+            for (unsigned tw_i_ = 0; tw_i_ < sizeof(tw_v_) / sizeof(tw_v_[0]); ++tw_i_) atomicAdd(&(dst)[tw_i_], tw_v_[tw_i_]); \
+        }                                                                                                                     \
+    } while (0)
+#define TW_STAMPS_CLEAR(g)                                                                                                    \
+    do {                                                                                                                      \
+        if (getenv("TW_STAMPS")) { const decltype(g) tw_z_ = {}; TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g), tw_z_, sizeof(tw_z_))); } \
+    } while (0)
+#define TW_STAMPS_REPORT(g, stream, h, ...)                                                                                   \
+    do {                                                                                                                      \
+        if (getenv("TW_STAMPS")) {                                                                                            \
+            unsigned long long h[sizeof(g) / sizeof(g[0])];                                                                   \
+            TW_HIP(hipStreamSynchronize(stream));                                                                             \
+            TW_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g), sizeof(h)));                                                         \
+            __VA_ARGS__                                                                                                       \
+        }                                                                                                                     \
+    } while (0)
+#else
+#define TW_STAMP_ARRAY(g, n)          static_assert(true, "")
+#define TW_STAMP_VARS(...)            static_assert(true, "")
+#define TW_STAMP(t)                   do {} while (0)
+#define TW_RESTAMP(t)                 do {} while (0)
+#define TW_STAMP_ADD(acc, t0, t1)     do {} while (0)
+#define TW_STAMP_COUNT(acc, n)        do {} while (0)
+#define TW_STAMP_USE(x)               do {} while (0)
+#define TW_STAMP_FLUSH(cond, dst, ...) do {} while (0)
+#define TW_STAMPS_CLEAR(g)            do {} while (0)
+#define TW_STAMPS_REPORT(g, stream, h, ...) do {} while (0)
 #endif
 
 namespace tw {

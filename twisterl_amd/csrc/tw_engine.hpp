@@ -76,10 +76,6 @@ __device__ __forceinline__ int gumbel_argmax4_halves(const float l[4], const u32
     return best;
 }
 
-#ifdef TW_ABLATE   // timing-only switches of the diagnostic build, per translation unit (TW_ENG_DBG: 4 = no weight / table streams)
-static __device__ int g_eng_dbg;
-#endif
-
 template <int NT> struct Tiles { static constexpr int NQ = (NT + 3) / 4; };
 
 constexpr int MAX_LDS_PERMS = 4;   // twist tables kept in LDS (more twists fall back to global reads)
@@ -88,9 +84,6 @@ constexpr int MAX_LDS_PERMS = 4;   // twist tables kept in LDS (more twists fall
 // g = (i&3) + 4*(i>>3), h = (i>>2)&1: the C/D layout (row = (g&3) + 8*(g>>2) + 4h for
 // accumulator register g on lane half h) then holds hidden unit 32r + 2g + h in register g.
 // (tw_api.hip builds the W1 image [k][q][i][4] = W1[k][hid(4q+c, i)] with the same formula.)
-//
-// DBG != 0 builds are timing-only ablations (wrong results): 1 no gather, 2 no A-operand reads,
-// 4 no weight streams, 8 no heads.  Never used by the product path.
 
 // =====================================================================================================
 // Engine3: the policy-forward engine.  Ring of three LDS slots, 16-column chunks; BOTH weight streams are pure LDS-DMA (the table
@@ -114,7 +107,7 @@ __host__ __device__ inline size_t engine3_lds_floats(int obs_size)
 
 // NW = waves per workgroup (8: two per SIMD, the throughput geometry; 2 / 1: small batches, so that a few thousand
 // episodes still spread over many CUs -- each workgroup streams the whole weight set either way).
-template <int NT, int NC, int DBG = 0, int NW_ = 8>
+template <int NT, int NC, int NW_ = 8>
 struct Engine3 {
     static constexpr int NW = NW_, KC = R3_KC, THREADS = 64 * NW_, EPB = NW * EPW, LSTR = R3_LSTR;
     static constexpr int NQ     = Tiles<NT>::NQ;
@@ -149,17 +142,10 @@ struct Engine3 {
     // everything wave-dependent is folded into dsrc_* / ddst_* at begin1: an op costs two 64-bit scalar adds, one 32-bit add
     // and the M0 write (the generic form spent 9 scalar instructions per op, which a lone wave per SIMD cannot hide).
     static_assert(WPIECE % NW == 0, "W1 pieces per chunk must be a multiple of the wave count");
-#ifdef TW_ABLATE
-    int eng_dbg = 0;
-#endif
     const uint8_t *dsrc_w, *dsrc_t;        // image bases (+ this wave's first W1 piece)
     uint32_t ddst_w, ddst_t;               // LDS byte addresses of ring slot 0 (+ this wave's first W1 piece)
     __device__ __forceinline__ void stream_op(int chunk, int slot, int op)
     {
-        if constexpr (DBG & 4) return;
-#ifdef TW_ABLATE
-        if (eng_dbg & 4) return;
-#endif
         if (NW * op < WPIECE) {
             const uint8_t *src = dsrc_w + (size_t)chunk * (WSLOT * 4) + (size_t)op * (NW * 1024);
             const uint32_t dst = ddst_w + (uint32_t)slot * (WSLOT * 4) + (uint32_t)op * (NW * 1024);
@@ -177,9 +163,6 @@ struct Engine3 {
     __device__ __forceinline__ void begin1(const PolicyDev &p, float *lds)
     {
         pol = p;
-#ifdef TW_ABLATE
-        eng_dbg = __builtin_amdgcn_readfirstlane(g_eng_dbg);
-#endif
         tid  = threadIdx.x;
         lane = tid & 63;
         wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -279,11 +262,9 @@ struct Engine3 {
             const int u = m / NT, r = m % NT;
             acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[r / 4][r % 4], bq[u], acc[r], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(DBG & 2)) {
-                if (r % 4 == 3 || r == NT - 1) {
-                    if (u < 3 || !LAST) aw[r / 4] = *reinterpret_cast<const f32x4 *>(w_base + ((kp0 + u + 1) * 2 * NQ + r / 4) * 128);
-                    else if (CROSS) aw[r / 4] = *reinterpret_cast<const f32x4 *>(wn_base + (r / 4) * 128);
-                }
+            if (r % 4 == 3 || r == NT - 1) {
+                if (u < 3 || !LAST) aw[r / 4] = *reinterpret_cast<const f32x4 *>(w_base + ((kp0 + u + 1) * 2 * NQ + r / 4) * 128);
+                else if (CROSS) aw[r / 4] = *reinterpret_cast<const f32x4 *>(wn_base + (r / 4) * 128);
             }
             {   // DMA ops spread over the group
                 if constexpr (NW == 8) {
@@ -296,10 +277,10 @@ struct Engine3 {
             }
             if constexpr (HAVE_NEXT_GATHER) {
 #pragma unroll
-                for (int q = 0; q <= ((DBG & 1) ? 0 : NC); ++q)
+                for (int q = 0; q <= NC; ++q)
                     if (rd_slot(q) == m) rd[q] = *reinterpret_cast<const __attribute__((address_space(3))) f32x4 *>(ga[q] + goff);
 #pragma unroll
-                for (int q = 0; q <= ((DBG & 1) ? 0 : NC); ++q)
+                for (int q = 0; q <= NC; ++q)
                     if (add_slot(q) == m) {
                         const f32x2 qlo = __builtin_shufflevector(rd[q], rd[q], 0, 1);
                         const f32x2 qhi = __builtin_shufflevector(rd[q], rd[q], 2, 3);
@@ -369,13 +350,12 @@ struct Engine3 {
         {
             const f32x4 r0 = *reinterpret_cast<const __attribute__((address_space(3))) f32x4 *>(ga[0]);
             f32x2 lo = __builtin_shufflevector(r0, r0, 0, 1), hi = __builtin_shufflevector(r0, r0, 2, 3);
-            if constexpr (!(DBG & 1))
 #pragma unroll
-                for (int q = 1; q <= NC; ++q) {
-                    const f32x4 rq = *reinterpret_cast<const __attribute__((address_space(3))) f32x4 *>(ga[q]);
-                    lo = pk_add(lo, __builtin_shufflevector(rq, rq, 0, 1));
-                    hi = pk_add(hi, __builtin_shufflevector(rq, rq, 2, 3));
-                }
+            for (int q = 1; q <= NC; ++q) {
+                const f32x4 rq = *reinterpret_cast<const __attribute__((address_space(3))) f32x4 *>(ga[q]);
+                lo = pk_add(lo, __builtin_shufflevector(rq, rq, 0, 1));
+                hi = pk_add(hi, __builtin_shufflevector(rq, rq, 2, 3));
+            }
             bq[0] = lo[0]; bq[1] = lo[1]; bq[2] = hi[0]; bq[3] = hi[1];
             finish_b(bq);
         }
@@ -397,13 +377,6 @@ struct Engine3 {
             }
         }
 
-        if constexpr (DBG & 8) {
-            value = 0.0f;
-#pragma unroll
-            for (int r = 0; r < NT; ++r) value += acc[r][0];
-            lg[0] = lg[1] = lg[2] = lg[3] = 0.0f;
-            return;
-        }
         if constexpr (NT >= 2) {
             // Heads as v_fma_f32 chains.  As MFMAs the k-ordered chain over the hidden units is 16*NT DEPENDENT 32x32x2 products
             // of which 5 rows in 32 are used: 6 % of the matrix-pipe time for 1 % of the FLOPs.  Instead: v_permlane32_swap
@@ -496,8 +469,8 @@ struct Engine3 {
 constexpr int R3S_XCHG = 256 + 1024, R3S_USER = 256;   // floats: head hand-off + B-operand exchange [2][2][64][4] | kernel use (MCTS leaf broadcast)
 
 template <int NT, int NC, int NS>
-struct Engine3S : Engine3<NT, NC, 0, NS> {
-    using B = Engine3<NT, NC, 0, NS>;
+struct Engine3S : Engine3<NT, NC, NS> {
+    using B = Engine3<NT, NC, NS>;
     static constexpr int EPB = EPW, NTL = NT / NS, KC = B::KC, NQ = B::NQ, WSLOT = B::WSLOT;
     static constexpr int WOPS = B::WPIECE / NS, TOPS = (B::TPIECE + NS - 1) / NS, NOPS = WOPS + TOPS;   // DMA ops per wave and chunk: W1 pieces, table pieces
     static constexpr bool SPLIT = true;
@@ -513,14 +486,7 @@ struct Engine3S : Engine3<NT, NC, 0, NS> {
     const uint8_t *swp, *stp;
     int sv, n3;                            // virtual step whose data is streamed next (sv == step + 2); steps per forward (multiple of 3)
     uint32_t voffW[WOPS], voffT[TOPS], mT[TOPS];
-#ifdef TW_ABLATE
-    unsigned long long stq[6] = {0, 0, 0, 0, 0, 0};   // prologue | chunk loop | - | - | heads | -
-#define TW_S3(var) const unsigned long long var = __builtin_readcyclecounter()
-#define TW_A3(i, a, b) stq[i] += (b) - (a)
-#else
-#define TW_S3(var)
-#define TW_A3(i, a, b)
-#endif
+    TW_STAMP_VARS(stq[6] = {});   // cycle stamps (tw_common.hpp): prologue | chunk loop | - | - | heads | -
 
     __host__ __device__ static size_t lds_floats(int obs_size) { return engine3_lds_floats<NT>(obs_size) + R3S_XCHG + R3S_USER; }
     __host__ __device__ static size_t lds_floats(const PolicyDev &p) { return lds_floats(p.obs_size); }
@@ -571,9 +537,6 @@ struct Engine3S : Engine3<NT, NC, 0, NS> {
     template <int S, int OP>   // DMA op OP of this wave: a piece of the chunk streamed next into ring slot S
     __device__ __forceinline__ void stream() const
     {
-#ifdef TW_ABLATE
-        if (this->eng_dbg & 4) return;
-#endif
         if constexpr (OP < WOPS)
             TW_GLDS16_ADD(voffW[OP], this->ddst_w, S * WSLOT * 4 + OP * NS * 1024, swp);
         else
@@ -685,7 +648,7 @@ struct Engine3S : Engine3<NT, NC, 0, NS> {
             __syncthreads();
         };
 
-        TW_S3(q_in);
+        TW_STAMP(q_in);
         {
             read_a(abase, aw);                                                  // slot 0
 #pragma unroll
@@ -696,21 +659,21 @@ struct Engine3S : Engine3<NT, NC, 0, NS> {
             gather_finish(0);
             __syncthreads();
         }
-        TW_S3(q_pro);
-        TW_A3(0, q_in, q_pro);
+        TW_STAMP(q_pro);
+        TW_STAMP_ADD(stq[0], q_in, q_pro);
         for (int c = 0; c < n3; c += 3) {
             step(std::integral_constant<int, 0>{}, c);
             step(std::integral_constant<int, 1>{}, c + 1);
             step(std::integral_constant<int, 2>{}, c + 2);
         }
-        TW_S3(q_lp);
-        TW_A3(1, q_pro, q_lp);
+        TW_STAMP(q_lp);
+        TW_STAMP_ADD(stq[1], q_pro, q_lp);
 
         // heads.  The k-ordered chain over the hidden units is serial, and as a chain of dependent 32x32x2 MFMAs it costs
         // 64 cycles per two units.  Here instead: every wave writes its ReLU'd hidden units into the ring slot the last chunk
         // just freed ([unit/4][episode][4], units >= 128 in the W slot), then half-wave hw = 2*wave + h runs the chain of
         // output hw (4 logits, value) for its 32 episodes as 4-cycle v_fma_f32 steps -- the same fma chain, bit for bit.
-        TW_S3(q_h0);
+        TW_STAMP(q_h0);
         {
             constexpr int fs = 2;                                                // the last step's slot: free until step 0 of the next forward streams into it
             float *hid_lo = this->lds_t + fs * R3_TSLOT, *hid_hi = this->lds_w + fs * WSLOT;
@@ -755,14 +718,10 @@ struct Engine3S : Engine3<NT, NC, 0, NS> {
             for (int i = 0; i < 4; ++i) lg[i] = lds_x[i * 32 + j];
             value = lds_x[4 * 32 + j];
         }
-        TW_S3(q_h1);
-        TW_A3(4, q_h0, q_h1);
+        TW_STAMP(q_h1);
+        TW_STAMP_ADD(stq[4], q_h0, q_h1);
     }
 };
-
-#ifdef TW_ABLATE
-#include "tw_engine_diag.hpp"          // Engine3G: a geometry measured no faster (profiles/r03_mid_rollout_two_groups_per_cu.txt); diagnostic build only
-#endif
 
 // =====================================================================================================
 // Engine3T: the tiny-batch geometry.  v_mfma_f32_16x16x4_f32 is a k-ordered fma chain too (scripts/mfma_probe/
@@ -783,8 +742,8 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // FS ("force scalar"): the scalar operands of the DMA ops through v_readfirstlane -- for a kernel whose control flow made the compiler
 // carry the engine's running source pointer in vector registers (the walker kernel in solve mode: an "s" asm operand cannot take those)
 template <int NT, int NC, bool FS = false>
-struct Engine3T : Engine3<NT, NC, 0, 4> {
-    using B = Engine3<NT, NC, 0, 4>;
+struct Engine3T : Engine3<NT, NC, 4> {
+    using B = Engine3<NT, NC, 4>;
     static constexpr int NS = 4, EPB = 16, TPW = NT / 2, KC = B::KC, NQ = B::NQ, WSLOT = B::WSLOT, H = NT * 32;
     static constexpr int TOPS = (B::TPIECE + 3) / 4;                       // table DMA ops per wave and 16-column chunk
     static constexpr int NOPS = 2 * TOPS;                                  // ... per step (a step is a PAIR of chunks)
@@ -837,9 +796,7 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
     }
-#ifdef TW_ABLATE
-    unsigned long long stq[6] = {0, 0, 0, 0, 0, 0};   // prologue | step loop | - | - | heads | -
-#endif
+    TW_STAMP_VARS(stq[6] = {});   // cycle stamps (tw_common.hpp): prologue | step loop | - | - | heads | -
 
     __host__ __device__ static size_t lds_floats(int obs_size) { return engine3_lds_floats<NT>(obs_size) + R3S_XCHG + R3S_USER + (HID_IN_RING ? 0 : NT * 32 * 16); }
     __host__ __device__ static size_t lds_floats(const PolicyDev &p) { return lds_floats(p.obs_size); }
@@ -859,9 +816,6 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
     __device__ __forceinline__ void stream() const
     {
         constexpr int HALF = OP / TOPS, K = OP % TOPS;
-#ifdef TW_KNOCK
-        if (TW_KNOCK & 4) return;                 // timing-only knock-outs (a variant build with -DTW_KNOCK=bits): 1 no row reads, 2 no A-operand loads, 4 no table streams, 8 no MFMAs, 16 no closing wait
-#endif
         const uint8_t *src = stp; uint32_t mk = mT[K];
         if constexpr (FS) {
             const uint64_t u = (uint64_t)(uintptr_t)stp;
@@ -986,9 +940,6 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 float sm = gr[hf][0];                                             // bias row, then the cells in order
-#ifdef TW_KNOCK
-                if (!(TW_KNOCK & 64))                                             // 64: no add chains
-#endif
 #pragma unroll
                 for (int c = 1; c <= NC; ++c) sm = sm + gr[hf][c];
                 xb[(buf * 64 + this->lane) * 8 + hf * 4 + wave] = relu_lim_v(sm, this->emb_lim);
@@ -1001,9 +952,6 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
             constexpr int P = decltype(pc)::value, Q = P ^ 1;
             constexpr int M = 8 * TPW;
             // A operands of the NEXT pair, requested first: they land during this step (the closing wait covers them)
-#ifdef TW_KNOCK
-            if (!(TW_KNOCK & 2))
-#endif
             {
                 const float *ap = agl + aoff;
 #pragma unroll
@@ -1022,14 +970,8 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
                     const int g = m / TPW, t = m % TPW;
                     // (the builtin: the inline-asm form of rounds 1 to 3 measured no faster in round 4 -- config 1 1.052 ms against 1.072,
                     //  self-play equal, profiles/r04_mfma_intrinsic_vs_asm.txt -- and sat outside hipcc's hazard padding)
-#ifdef TW_KNOCK
-                    if (!(TW_KNOCK & 8))
-#endif
                     acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[P][g][t], g < 4 ? bq0[g & 3] : bq1[g & 3], acc[t], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-#ifdef TW_KNOCK
-                    if (!(TW_KNOCK & 1))
-#endif
 #pragma unroll
                     for (int r = m * 2 * (NC + 1) / M; r < (m + 1) * 2 * (NC + 1) / M; ++r)         // the next pair, complete in pair-slot Q
                         gr[r / (NC + 1)][r % (NC + 1)] = ga[r % (NC + 1)][(2 * Q + r / (NC + 1)) * R3_TSLOT];
@@ -1041,17 +983,11 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
                 stream_pair<P>();
             }
             advance();
-#ifdef TW_KNOCK
-            if (!(TW_KNOCK & 16))
-#endif
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef TW_KNOCK
-            if (!(TW_KNOCK & 32))                                                 // 32: no barrier at the end of a step
-#endif
             this->template fsync<EB>();
         };
 
-        TW_S3(q_in);
+        TW_STAMP(q_in);
         {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf)
@@ -1060,17 +996,17 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
             gather_finish(0);
             this->template fsync<EB>();
         }
-        TW_S3(q_pro);
-        TW_A3(0, q_in, q_pro);
+        TW_STAMP(q_pro);
+        TW_STAMP_ADD(stq[0], q_in, q_pro);
         for (int p = 0; p < n2; p += 2) {
             step(std::integral_constant<int, 0>{}, p);
             step(std::integral_constant<int, 1>{}, p + 1);
         }
-        TW_S3(q_lp);
-        TW_A3(1, q_pro, q_lp);
+        TW_STAMP(q_lp);
+        TW_STAMP_ADD(stq[1], q_pro, q_lp);
 
         // heads: hidden units -> the buffer behind the table ring as [unit/4][16 episodes][4], then one v_fma_f32 chain per (episode, output)
-        TW_S3(q_h0);
+        TW_STAMP(q_h0);
         {
             const int half = wave >> 1, q = NT == 8 ? (wave & 1) : 0, cc0 = NT == 8 ? 0 : 2 * (wave & 1);
             float *hid = HID_IN_RING ? tbase + 4 * R3_TSLOT : lds_user + R3S_USER;
@@ -1103,22 +1039,18 @@ struct Engine3T : Engine3<NT, NC, 0, 4> {
             for (int i = 0; i < 4; ++i) lg[i] = lds_x[i * 16 + jj];
             value = lds_x[4 * 16 + jj];
         }
-        TW_S3(q_h1);
-        TW_A3(4, q_h0, q_h1);
+        TW_STAMP(q_h1);
+        TW_STAMP_ADD(stq[4], q_h0, q_h1);
     }
 };
 
 // launch geometry code -> engine: NW > 0 = NW independent waves of 32 episodes (Engine3); NW < 0 = -NW waves sharing 32 (Engine3S)
-template <int NT, int NC, int DBG, int NW> struct Geom { using Eng = Engine3<NT, NC, DBG, NW>; static constexpr int WAVES = NW; };
-template <int NT, int NC, int DBG> struct Geom<NT, NC, DBG, -4> { using Eng = Engine3S<NT, NC, 4>; static constexpr int WAVES = 4; };
-template <int NT, int NC, int DBG> struct Geom<NT, NC, DBG, -2> { using Eng = Engine3S<NT, NC, 2>; static constexpr int WAVES = 2; };
-template <int NT, int NC, int DBG> struct Geom<NT, NC, DBG, -16> { using Eng = Engine3T<NT, NC>; static constexpr int WAVES = 4; };   // 16 episodes per workgroup
-template <int NT, int NC, int DBG> struct Geom<NT, NC, DBG, -17> { using Eng = Engine3T<NT, NC, true>; static constexpr int WAVES = 4; };   // ... its scalar DMA operands forced (walker kernel, solve mode)
-#ifdef TW_ABLATE
-template <int NT, int NC, int DBG> struct Geom<NT, NC, DBG, -5> { using Eng = Engine3G<NT, NC>; static constexpr int WAVES = 4; };    // four waves share 32, two workgroups per CU (tw_engine_diag.hpp)
-#endif
-template <int NT, int NC, int DBG> struct Geom<NT, NC, DBG, -64> { using Eng = EngineV<NC, true>; static constexpr int WAVES = 4; };   // generic stacks, inline-asm MFMAs: not used any more (tw_engine_generic.hpp)
-template <int NT, int NC, int DBG> struct Geom<NT, NC, DBG, -65> { using Eng = EngineV<NC, false>; static constexpr int WAVES = 4; }; // generic stacks (any Sequential depth)
+template <int NT, int NC, int NW> struct Geom { using Eng = Engine3<NT, NC, NW>; static constexpr int WAVES = NW; };
+template <int NT, int NC> struct Geom<NT, NC, -4> { using Eng = Engine3S<NT, NC, 4>; static constexpr int WAVES = 4; };
+template <int NT, int NC> struct Geom<NT, NC, -2> { using Eng = Engine3S<NT, NC, 2>; static constexpr int WAVES = 2; };
+template <int NT, int NC> struct Geom<NT, NC, -16> { using Eng = Engine3T<NT, NC>; static constexpr int WAVES = 4; };   // 16 episodes per workgroup
+template <int NT, int NC> struct Geom<NT, NC, -17> { using Eng = Engine3T<NT, NC, true>; static constexpr int WAVES = 4; };   // ... its scalar DMA operands forced (walker kernel, solve mode)
+template <int NT, int NC> struct Geom<NT, NC, -65> { using Eng = EngineV<NC>; static constexpr int WAVES = 4; };   // generic stacks (any Sequential depth)
 
 // geometry for n episodes: 8 = the throughput shape; below ~3/4 of a chip of 256-episode workgroups the split shape
 template <int NT> inline int geometry_for(uint64_t n)

@@ -67,14 +67,9 @@ struct Engine16 {
 
     PolicyDev pol;
     int tid, lane, wave, j, hh, n_kt, rp;
-#ifdef TW_ABLATE   // diagnostic build: per-wave cycle stamps (s_memtime), summed into tw::g_stamps16 at kernel end
-    unsigned long long st[8];      // 0 pre 1 prologue 2 stage bodies 3 vmcnt wait 4 stage barrier 5 heads 6 post 7 step barrier
-#define TW_STAMP(var) const unsigned long long var = __builtin_readcyclecounter()
-#define TW_ACC(i, a, b) st[i] += (b) - (a)
-#else
-#define TW_STAMP(var)
-#define TW_ACC(i, a, b)
-#endif
+    // cycle stamps (tw_common.hpp), summed into tw::g_stamps16 at kernel end:
+    // 0 pre 1 prologue 2 stage bodies 3 vmcnt wait 4 stage barrier 5 heads 6 post 7 step barrier
+    TW_STAMP_VARS(st[8] = {});
     uint8_t *lg_;                  // LDS base, generic
     uint32_t lds_u32, voff;        // LDS base as an M0 value; per-lane global byte offset of this wave's DMA piece
     lds_cu8 *L;                    // LDS base, address space 3
@@ -188,8 +183,7 @@ struct Engine16 {
     // The first MFMA of a chain takes the embedding bias (f32, accumulator-register order) as its C operand.
     static __device__ __forceinline__ void mfma_v(f32x16 &d, const h16x8 a, const h16x8 b, bool first, const f32x16 &c0)
     {
-        if constexpr (TW_MFMA_INTRIN & 8) d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, first ? c0 : d, 0, 0, 0);
-        else if (first) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c0));
+        if (first) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c0));
         else       asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
     }
     // one B register: accumulator registers (2q, 2q+1) of fragment m (+ bias), optional ReLU, to f16
@@ -346,7 +340,7 @@ struct Engine16 {
             TW_STAMP(t_w);
             __syncthreads();
             TW_STAMP(t_s);
-            TW_ACC(2, t_in, t_b); TW_ACC(3, t_b, t_w); TW_ACC(4, t_w, t_s);
+            TW_STAMP_ADD(st[2], t_in, t_b); TW_STAMP_ADD(st[3], t_b, t_w); TW_STAMP_ADD(st[4], t_w, t_s);
         }
     }
 
@@ -368,7 +362,7 @@ struct Engine16 {
         for (int d = 0; d < D; ++d) { pp.x0[d] = ld8(oh.a0[d]); pp.x1[d] = ld8(oh.a1[d]); pp.a[d] = ld8(O_T0 + lo + d * 1024); }
         phase<true, false, false, 1, false>(tile_of(1), O_T0 + lo, 0, slot_base(s0), 0, 0, oh, acc0, acc1, Ba0, Ba1, Ba0, Ba1, pp);
         TW_STAMP(t_p1);
-        TW_ACC(1, t_p0, t_p1);
+        TW_STAMP_ADD(st[1], t_p0, t_p1);
         // every stage but the last: embedding MFMAs of tile kt+1 interleaved with the common-layer MFMAs of tile kt;
         // two stages per loop trip: the B fragments ping-pong between (Ba) and (Bb) without copies.  The last stage
         // has only the common-layer part; it fetches its first operands itself (the stage before it prefetched for
@@ -424,11 +418,9 @@ struct Engine16 {
             }
         }
         out0 = h0; out1 = h1;
-#ifdef TW_ABLATE
-        asm volatile("" :: "v"(h0), "v"(h1));
-#endif
+        TW_STAMP_USE(h0); TW_STAMP_USE(h1);
         TW_STAMP(t_h1);
-        TW_ACC(5, t_h0, t_h1);
+        TW_STAMP_ADD(st[5], t_h0, t_h1);
     }
 };
 

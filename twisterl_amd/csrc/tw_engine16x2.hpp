@@ -51,9 +51,7 @@ struct EngineS {
 
     PolicyDev pol;
     int tid, lane, wave, j, hh, n_kt, rp, n_stages;
-#ifdef TW_ABLATE
-    unsigned long long st[8];      // (stamps are only taken around the forward in this engine)
-#endif
+    TW_STAMP_VARS(st[8] = {});     // cycle stamps as Engine16's (only taken around the forward in this engine)
     uint8_t *lg_;
     uint32_t lds_u32, voff;
     lds_cu8 *L;
@@ -152,8 +150,7 @@ struct EngineS {
     __device__ __forceinline__ h16x8 ld8(uint32_t off) const { return *(const __attribute__((address_space(3))) h16x8 *)(L + off); }
     static __device__ __forceinline__ void mfma_v(f32x16 &d, const h16x8 a, const h16x8 b, bool first, const f32x16 &c0)
     {   // accumulator in architectural VGPRs (see tw_engine16.hpp)
-        if constexpr (TW_MFMA_INTRIN & 16) d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, first ? c0 : d, 0, 0, 0);
-        else if (first) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c0));
+        if (first) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c0));
         else       asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
     }
     // accumulator registers (2q, 2q+1) of fragment m -> one register of the hi fragment and one of the lo fragment:
@@ -298,7 +295,7 @@ struct EngineS {
             TW_STAMP(t_w);
             __syncthreads();
             TW_STAMP(t_s);
-            TW_ACC(2, t_in, t_b); TW_ACC(3, t_b, t_w); TW_ACC(4, t_w, t_s);
+            TW_STAMP_ADD(st[2], t_in, t_b); TW_STAMP_ADD(st[3], t_b, t_w); TW_STAMP_ADD(st[4], t_w, t_s);
         }
     }
     // DMA ops issued up to and including position p (op o goes to the first position p with o*SPREAD/NOPS <= p)
@@ -396,14 +393,12 @@ struct EngineS {
                 }
             }
             out0 = h0; out1 = h1;
-#ifdef TW_ABLATE
-            asm volatile("" :: "v"(h0), "v"(h1));
-#endif
+            TW_STAMP_USE(h0); TW_STAMP_USE(h1);
             TW_STAMP(t_hb);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             TW_STAMP(t_hs);
-            TW_ACC(5, t_h0, t_hb); TW_ACC(4, t_hb, t_hs);
+            TW_STAMP_ADD(st[5], t_h0, t_hb); TW_STAMP_ADD(st[4], t_hb, t_hs);
             s0 = s1;
         }
         rp = s0;

@@ -21,15 +21,15 @@ constexpr int GEN_STRIDE = 17;             // floats per unit row of an activati
 typedef float fx4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) fx4 gfx4;
 
-// ASM_MFMA: the MFMAs as inline asm with the accumulators pinned to VGPRs (with the intrinsic the allocator shuttles them between VGPRs
-// and AGPRs around every k-group).  NO kernel uses that form any more (round 3).  hipcc pads the wait states an MFMA needs after a
+// The MFMAs are the intrinsic.  An inline-asm form with the accumulators pinned to VGPRs (with the intrinsic the allocator shuttles them
+// between VGPRs and AGPRs around every k-group) was dropped in round 3: hipcc pads the wait states an MFMA needs after a
 // vector-ALU write of one of its operands for its own MFMAs, not for an asm string: the accumulator's zero-initialisation (v_mov) or the
 // reload of a value the allocator parked in an AGPR can land right in front of the asm MFMA.  Seen twice as deterministic wrong sums:
 // the 9-cell rollout at two workgroups per CU, and self-play of a 6 x 4 board with a 32 -> 48 -> 32 stack (one visit count off in 14 of
 // 126 records; every other shape tested was right).  scripts/scan_mfma_hazards.py looks for the pattern in the compiled kernels (an
 // operand written by one of the two vector instructions in front of an MFMA, no s_nop between): none with the intrinsic form; the
 // asm MFMAs of the other engines (tw_engine.hpp) take their operands from LDS / global loads and ReLUs that carry their own s_nop.
-template <int NC, bool ASM_MFMA = false>
+template <int NC>
 struct EngineV {
     static constexpr int NW = 4, THREADS = 256, EPB = GEN_COLS, NS = 4;
     static constexpr bool SPLIT = true;
@@ -41,9 +41,7 @@ struct EngineV {
                                            // three adjacent members made the compiler index them in memory -- the whole engine went to scratch)
     int *lds_rows;                         // [16 columns][NC] obs ids of the forward (the embedding gather works on other columns than its lane's)
     const uint8_t *perm_obs, *perm_act;
-#ifdef TW_ABLATE
-    unsigned long long stq[6] = {0, 0, 0, 0, 0, 0};      // diagnostic build: cycles in embedding | common | value head | action head
-#endif
+    TW_STAMP_VARS(stq[4] = {});    // cycle stamps (tw_common.hpp): embedding | common | value head | action head
 
     // three activation buffers (the common output stays put while the two heads run), each as many rows as the widest layer it
     // ever holds (PolicyDev::gen_rows, laid out by tw_policy_create with the buffer choices of stack() below): the usual
@@ -143,8 +141,7 @@ struct EngineV {
                 for (int i = 0; i < PF; ++i) {
 #pragma unroll
                     for (int t = 0; t < TB; ++t) {
-                        if constexpr (ASM_MFMA) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[t]) : "v"(w[i][t]), "v"(xv[i]));
-                        else acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][t], xv[i], acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][t], xv[i], acc[t], 0, 0, 0);
                         if (t == TB - 1) xv[i] = xq[i * (4 * GEN_STRIDE)];            // (after the last MFMA that reads it was issued)
                     }
                     ldw(w[i]);
@@ -155,15 +152,9 @@ struct EngineV {
             for (int i = 0; i < PF; ++i) {
                 if (g0 + i < KG) {
 #pragma unroll
-                    for (int t = 0; t < TB; ++t) {
-                        if constexpr (ASM_MFMA) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[t]) : "v"(w[i][t]), "v"(xv[i]));
-                        else acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][t], xv[i], acc[t], 0, 0, 0);
-                    }
+                    for (int t = 0; t < TB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][t], xv[i], acc[t], 0, 0, 0);
                 }
             }
-            // (the MFMAs are inline asm with the accumulators pinned to VGPRs -- with the intrinsic the allocator shuttles them
-            //  between VGPRs and AGPRs around every group; the wait states between the last MFMA and the reads below are ours)
-            if constexpr (ASM_MFMA) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
             // D row 4kq + r of tile t is output (b * TB + t) * 16 + 4kq + r
 #pragma unroll
             for (int t = 0; t < TB; ++t) {
@@ -211,9 +202,7 @@ struct EngineV {
     __device__ __forceinline__ void forward(const int (&rowoff)[NC], float (&lg)[4], float &value)
     {
         // EmbeddingBag (layers.rs:56-62,82-84): bias + the rows of the cells, in cell order
-#ifdef TW_ABLATE
-        const unsigned long long c0 = __builtin_readcyclecounter();
-#endif
+        TW_STAMP(c0);
         const int E = pol.emb;
         const float *tab = pol.emb_rows;
         const float *bias = tab + (size_t)pol.obs_size * E;
@@ -301,14 +290,10 @@ struct EngineV {
         }
         }
         __syncthreads();
-#ifdef TW_ABLATE
-        const unsigned long long c1 = __builtin_readcyclecounter();
-#endif
+        TW_STAMP(c1);
         const LayerDev *ls = pol.layers;
         const int co = stack(ls, pol.n_common, 0, -1);                                         // policy.rs:86
-#ifdef TW_ABLATE
-        const unsigned long long c2 = __builtin_readcyclecounter();
-#endif
+        TW_STAMP(c2);
         int vo, ao;
         if (pol.n_value == 1 && pol.n_action == 1) {
             // single-Linear heads (BasicPolicy's default): both at once, the value head on waves 2..3, the action head on waves
@@ -327,9 +312,7 @@ struct EngineV {
             lds_out[j * 8 + 4] = s;
         }
         __syncthreads();
-#ifdef TW_ABLATE
-        const unsigned long long c3 = __builtin_readcyclecounter();
-#endif
+        TW_STAMP(c3);
         if (ao < 0) ao = stack(ls + pol.n_common, pol.n_action, co, co);                       // policy.rs:92
         if (g == 0) {
 #pragma unroll
@@ -339,10 +322,8 @@ struct EngineV {
 #pragma unroll
         for (int i = 0; i < 4; ++i) lg[i] = lds_out[j * 8 + i];
         value = lds_out[j * 8 + 4];
-#ifdef TW_ABLATE
-        const unsigned long long c4 = __builtin_readcyclecounter();
-        stq[0] += c1 - c0; stq[1] += c2 - c1; stq[2] += c3 - c2; stq[3] += c4 - c3;
-#endif
+        TW_STAMP(c4);
+        TW_STAMP_ADD(stq[0], c0, c1); TW_STAMP_ADD(stq[1], c1, c2); TW_STAMP_ADD(stq[2], c2, c3); TW_STAMP_ADD(stq[3], c3, c4);
         __syncthreads();           // (the buffers and lds_out are rewritten by the next forward)
     }
 };

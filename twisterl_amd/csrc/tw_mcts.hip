@@ -40,10 +40,20 @@ size_t mcts_node_bytes() { return sizeof(MctsNode) + 32; }
 
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr int PATH_DEPTH = 8;     // levels of the search path kept in LDS per episode (deeper paths fall back to parent chasing)
-#ifdef TW_ABLATE   // diagnostic build: per-wave cycle accounting (forward | tree phase | loop trips | searches consumed | max trips)
-__device__ unsigned long long g_mcts_stamps[24];
-#endif
+TW_STAMP_ARRAY(g_mcts_stamps, 22);   // cycle stamps (tw_common.hpp): per-wave cycle accounting, laid out at the kernel's end
 enum { PH_ROOT = 0, PH_LEAF = 1, PH_DONE = 2 };
+
+// (cycle stamps: the sum / max of a per-lane counter over the wave)
+__device__ inline unsigned long long wave_sum_u64(unsigned long long v)
+{
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ inline unsigned long long wave_max_u64(unsigned long long v)
+{
+    for (int o = 32; o; o >>= 1) { const unsigned long long w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
+    return v;
+}
 
 __device__ inline PuzzleLane lane_of(const MctsNode &n, const PuzzleConsts &c)
 {
@@ -53,9 +63,9 @@ __device__ inline PuzzleLane lane_of(const MctsNode &n, const PuzzleConsts &c)
 }
 
 template <int NT, int NC, int NW, bool PERSIST = false>
-__global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 2 : 1)) mcts_f32_kernel(const MctsArgs a)
+__global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), (NW == 8 ? 2 : 1)) mcts_f32_kernel(const MctsArgs a)
 {
-    using Eng = typename Geom<NT, NC, 0, NW>::Eng;
+    using Eng = typename Geom<NT, NC, NW>::Eng;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.begin1(a.pol, lds);
@@ -125,24 +135,13 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
 
     eng.begin2();
 
-#ifdef TW_ABLATE
-    unsigned long long c_fwd = 0, c_tree = 0, c_trips = 0, c_inner = 0, c_desc = 0, c_pre = 0, c_dsc = 0, c_bp = 0, c_wl = 0;
-#define TW_MS(var) const unsigned long long var = __builtin_readcyclecounter()
-#define TW_MA(acc, a, b) acc += (b) - (a)
-#else
-#define TW_MS(var)
-#define TW_MA(acc, a, b)
-#endif
-#ifdef TW_ABLATE
-    unsigned long long x_or = 0, x_rows = 0, x_eng = 0, x_soft = 0, x_own = 0, x_mir = 0;
-#endif
+    TW_STAMP_VARS(c_fwd = 0, c_tree = 0, c_trips = 0, c_inner = 0, c_desc = 0, c_pre = 0, c_dsc = 0, c_bp = 0,
+                  x_or = 0, x_rows = 0, x_eng = 0, x_own = 0, x_mir = 0);
     for (;;) {
-        TW_MS(z0);
+        TW_STAMP(z0);
         if (!__syncthreads_or(phase != PH_DONE ? 1 : 0)) break;
-#ifdef TW_ABLATE
-        const unsigned long long s0 = __builtin_readcyclecounter();
-        x_or += s0 - z0;
-#endif
+        TW_STAMP(s0);
+        TW_STAMP_ADD(x_or, z0, s0);
         // ---- (2) Policy::full_predict of the pending leaf (policy.rs:102-126) ------------------
         float lsum[4] = {0.0f, 0.0f, 0.0f, 0.0f}, vsum = 0.0f;
         const int n_pass = eng.pol.n_perms > 0 ? eng.pol.n_perms : 1;
@@ -150,13 +149,13 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
         for (int pass = 0; pass < n_pass; ++pass) {
             const int perm = eng.pol.n_perms > 0 ? pass : -1;
             int rowoff[NC];
-            TW_MS(z1);
+            TW_STAMP(z1);
             eng.rows_of(leaf.board, env.n_cells, perm, rowoff);
             float lg[4], v;
-            TW_MS(z2);
+            TW_STAMP(z2);
             eng.forward(rowoff, lg, v);
-            TW_MS(z3);
-            TW_MA(x_rows, z1, z2); TW_MA(x_eng, z2, z3);
+            TW_STAMP(z3);
+            TW_STAMP_ADD(x_rows, z1, z2); TW_STAMP_ADD(x_eng, z2, z3);
             eng.act_perm(perm, lg);
             if (eng.pol.n_perms > 0) {
                 vsum = vsum + v / np;                                            // policy.rs:111
@@ -172,11 +171,9 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
         masked_softmax4(lsum, puzzle_maskbits(leaf, env), probs);
         const float nn_value = vsum;
 
-#ifdef TW_ABLATE
-        const unsigned long long s1 = __builtin_readcyclecounter();
-        c_fwd += s1 - s0; ++c_trips;
-#endif
-        TW_MS(z4);
+        TW_STAMP(s1);
+        TW_STAMP_ADD(c_fwd, s0, s1); TW_STAMP_COUNT(c_trips, 1);
+        TW_STAMP(z4);
         // ---- (1) per-episode tree work on the owner lane ---------------------------------------
         if (owner && phase != PH_DONE) {
             ++evals;
@@ -223,7 +220,7 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
                 root_vs = root_vs + val; root_visit += 1u;
             };
 
-            TW_MS(m_pre0);
+            TW_STAMP(m_pre0);
             if (phase == PH_ROOT) {
                 // root node (search.rs:120-129): visit_count 1, then expand with the root priors
                 MctsNode r;
@@ -249,17 +246,15 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
                 ++expanded;
             }
 
-            TW_MS(m_pre1);
-            TW_MA(c_pre, m_pre0, m_pre1);
+            TW_STAMP(m_pre1);
+            TW_STAMP_ADD(c_pre, m_pre0, m_pre1);
             // run the search loop until a leaf needs the network or the move is finished
             bool resume_expand = (phase == PH_LEAF);
             MctsNode cur; bool have_cur = false;      // record of `node` when it was just read by the descent
             cur.board = 0; cur.value_sum = 0.0f; cur.visit = 0; cur.prior = 0.0f; cur.parent = NONE; cur.child_base = 0;
             cur.n_children = 0; cur.action = 0; cur.depth = 0;
             for (;;) {
-#ifdef TW_ABLATE
-                ++c_inner;
-#endif
+                TW_STAMP_COUNT(c_inner, 1);
                 if (!resume_expand) {
                     if (it == S) {
                         // ---- move finished: visit counts -> probs (search.rs:166-188) --------------
@@ -333,7 +328,7 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
                     }
                     // descend to a leaf by UCB (search.rs:133-138, next :77-91, ucb :29-39).  The chosen child's record is
                     // kept in registers: one dependent HBM round trip per level (its children) instead of two
-                    TW_MS(m_d0);
+                    TW_STAMP(m_d0);
                     node = 0;
                     cur.board = st.board; cur.value_sum = root_vs; cur.visit = root_visit; cur.prior = 0.0f; cur.parent = NONE;
                     cur.child_base = root_cb; cur.n_children = (uint8_t)root_nc; cur.action = 0xff; cur.depth = (uint16_t)st.depth;
@@ -363,14 +358,12 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
                         if (best == NONE) break;        // all-NaN UCB: the reference panics here
                         node = best; cur = bestn;
                         push(best, bestn.value_sum, bestn.visit);
-#ifdef TW_ABLATE
-                        ++c_desc;
-#endif
+                        TW_STAMP_COUNT(c_desc, 1);
                     }
                     value = 0.0f; expanded = 0;
                     have_cur = true;
-                    TW_MS(m_d1);
-                    TW_MA(c_dsc, m_d0, m_d1);
+                    TW_STAMP(m_d1);
+                    TW_STAMP_ADD(c_dsc, m_d0, m_d1);
                 }
                 resume_expand = false;
                 // leaf phase (search.rs:143-160)
@@ -385,14 +378,13 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
                     // expand with it, sample a child, go on (search.rs:154-159).  The grandparent is level plen-3 of the search path
                     // (level plen-1 is `node`) while the path fits its PATH_DEPTH levels; below that `push` stops recording -- plen
                     // stays at PATH_DEPTH and level plen-3 is an ancestor further up -- so it is found through the parent links.
-                    // a.reuse_mode (TW_OPT_AZ_REUSE, diagnostic): 0 as described, 1 no reuse, 2 the path level whatever the depth
-                    // (round 2's first form: WRONG below PATH_DEPTH levels, kept to show it), 3 parent links only, 4 counts how the
+                    // a.reuse_mode (TW_OPT_AZ_REUSE, diagnostic): 0 as described, 1 no reuse, 3 parent links only, 4 counts how the
                     // two ways of finding the grandparent disagree (eval_count[3..11]) and goes by the parent links
                     uint32_t g = NONE;
                     if (n.action != 0xffu && (n.action & ACT_UNDO) && a.reuse_mode != 1u) {
                         uint32_t g_path = NONE, g_link = NONE;
                         const bool deep_path = overflow;
-                        if (a.reuse_mode == 2u || a.reuse_mode == 4u || (a.reuse_mode == 0u && !deep_path))
+                        if (a.reuse_mode == 4u || (a.reuse_mode == 0u && !deep_path))
                             if (plen >= 3) g_path = p_idx[(plen - 3) * Eng::EPB];
                         if (a.reuse_mode == 3u || a.reuse_mode == 4u || (a.reuse_mode == 0u && deep_path))
                             if (n.parent != NONE && n.parent != 0u) g_link = nodes[n.parent].parent;
@@ -406,10 +398,10 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
                             if (!deep_path && (plen < 1 || p_idx[(plen - 1) * Eng::EPB] != node)) atomicAdd(a.eval_count + 10, 1ull);
                             if (!deep_path && (plen < 2 || p_idx[(plen - 2) * Eng::EPB] != n.parent)) atomicAdd(a.eval_count + 11, 1ull);
                         }
-                        g = (a.reuse_mode == 2u || (a.reuse_mode == 0u && !deep_path)) ? g_path : g_link;
+                        g = (a.reuse_mode == 0u && !deep_path) ? g_path : g_link;
                         // tripwire, not a filter: the grandparent's board IS this node's board (every child is a legal move, so the
                         // move back restores it) and it was expanded on the way down; a failure is counted and fails the collect
-                        if (g != NONE && a.reuse_mode != 2u && (nodes[g].board != n.board || nodes[g].n_children == 0)) { atomicAdd(a.eval_count + 12, 1ull); g = NONE; }
+                        if (g != NONE && (nodes[g].board != n.board || nodes[g].n_children == 0)) { atomicAdd(a.eval_count + 12, 1ull); g = NONE; }
                     }
                     if (g == NONE) { phase = PH_LEAF; leaf = s; need_nn = true; break; }       // :154 needs the network
                     const uint4 o2 = outs[2 * g], o3 = outs[2 * g + 1];
@@ -428,21 +420,15 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
                     ++expanded;
                 }
                 if (need_nn) break;
-                TW_MS(m_b0);
+                TW_STAMP(m_b0);
                 backprop(node, value);                                               // :163
                 ++it;
-                TW_MS(m_b1);
-                TW_MA(c_bp, m_b0, m_b1);
-#ifdef TW_ABLATE
-                ++c_wl;
-#endif
+                TW_STAMP(m_b1);
+                TW_STAMP_ADD(c_bp, m_b0, m_b1);
             }
         }
-#ifdef TW_ABLATE
-        c_tree += __builtin_readcyclecounter() - s1;
-#endif
-        TW_MS(z5);
-        TW_MA(x_own, z4, z5);
+        TW_STAMP(z5);
+        TW_STAMP_ADD(c_tree, s1, z5); TW_STAMP_ADD(x_own, z4, z5);
         // mirror what the other lanes of the episode need for the next collective evaluation
         if constexpr (Eng::SPLIT) {        // lanes j / j+32 of every wave of the workgroup: through LDS
             uint32_t *bc = reinterpret_cast<uint32_t *>(eng.lds_user) + j * 8;
@@ -461,8 +447,8 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
             leaf.zy    = __shfl(leaf.zy, j, 64);
             leaf.depth = __shfl(leaf.depth, j, 64);
         }
-        TW_MS(z6);
-        TW_MA(x_mir, z5, z6);
+        TW_STAMP(z6);
+        TW_STAMP_ADD(x_mir, z5, z6);
     }
     if (owner) {
         if (sv.on) {
@@ -474,54 +460,32 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
         atomicAdd(a.eval_count, evals);
         if (!sv.on && reused) atomicAdd(a.eval_count + 2, reused);
     }
-#ifdef TW_ABLATE
-    {   // wave-level: cycles from lane 0; per-lane counters: sum and max over the wave's owners
-        unsigned long long mx = c_inner, sm = owner ? c_inner : 0, ds = owner ? c_desc : 0;
-        unsigned long long own_work = c_pre + c_dsc + c_bp;      // wave-uniform clock: the max over the lanes is the wave's own tree work
-        for (int o = 32; o; o >>= 1) {
-            const unsigned long long w2 = ((unsigned long long)__shfl_xor((unsigned)(own_work >> 32), o, 64) << 32) | __shfl_xor((unsigned)own_work, o, 64);
-            own_work = w2 > own_work ? w2 : own_work;
-        }
-        for (int o = 32; o; o >>= 1) {
-            const unsigned long long m2 = ((unsigned long long)__shfl_xor((unsigned)(mx >> 32), o, 64) << 32) | __shfl_xor((unsigned)mx, o, 64);
-            mx = m2 > mx ? m2 : mx;
-            sm += ((unsigned long long)__shfl_xor((unsigned)(sm >> 32), o, 64) << 32) | __shfl_xor((unsigned)sm, o, 64);
-            ds += ((unsigned long long)__shfl_xor((unsigned)(ds >> 32), o, 64) << 32) | __shfl_xor((unsigned)ds, o, 64);
-        }
-        if (eng.lane == 0) {
-            atomicAdd(&g_mcts_stamps[0], c_fwd); atomicAdd(&g_mcts_stamps[1], c_tree); atomicAdd(&g_mcts_stamps[2], c_trips);
-            if constexpr (Eng::SPLIT) { for (int i = 0; i < 5; ++i) atomicAdd(&g_mcts_stamps[8 + i], eng.stq[i]); }
-            atomicAdd(&g_mcts_stamps[13], c_pre); atomicAdd(&g_mcts_stamps[14], c_dsc); atomicAdd(&g_mcts_stamps[15], c_bp);
-            atomicAdd(&g_mcts_stamps[3], sm); atomicAdd(&g_mcts_stamps[4], mx); atomicAdd(&g_mcts_stamps[5], ds); atomicAdd(&g_mcts_stamps[6], 1ull);
-            atomicAdd(&g_mcts_stamps[16], x_or); atomicAdd(&g_mcts_stamps[17], x_rows); atomicAdd(&g_mcts_stamps[18], x_eng);
-            atomicAdd(&g_mcts_stamps[19], x_own); atomicAdd(&g_mcts_stamps[20], x_mir); atomicAdd(&g_mcts_stamps[21], own_work);
-        }
-    }
-#endif
+    // wave-level: cycles from lane 0; per-lane counters: sum and max over the wave's owners; the wave's own tree work: the max over
+    // the lanes (a wave-uniform clock).  [0] fwd [1] tree [2] trips [3] inner sum [4] inner max [5] descents [6] waves | [8..12] split
+    // engine | [13] expand [14] descend [15] backprop [16] loop-top barrier [17] rows_of [18] forward [19] owner block [20] mirror [21] own work
+    TW_STAMP_VARS(inner_sum = wave_sum_u64(owner ? c_inner : 0), inner_max = wave_max_u64(c_inner), desc_sum = wave_sum_u64(owner ? c_desc : 0),
+                  own_work = wave_max_u64(c_pre + c_dsc + c_bp));
+    TW_STAMP_FLUSH(eng.lane == 0, g_mcts_stamps, c_fwd, c_tree, c_trips, inner_sum, inner_max, desc_sum, 1);
+    if constexpr (Eng::SPLIT && NW != -65)     // Engine3S / Engine3T (EngineV's four stamps are another layout: tw_engine_generic.hpp)
+        TW_STAMP_FLUSH(eng.lane == 0, g_mcts_stamps + 8, eng.stq[0], eng.stq[1], eng.stq[2], eng.stq[3], eng.stq[4]);
+    TW_STAMP_FLUSH(eng.lane == 0, g_mcts_stamps + 13, c_pre, c_dsc, c_bp, x_or, x_rows, x_eng, x_own, x_mir, own_work);
     eng.end();
 }
 
 template <int NT, int NC, int NW, bool PERSIST = false>
 static int launch_mcts_geom(const MctsArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads)
 {
-    using G = Geom<NT, NC, 0, NW>;
+    using G = Geom<NT, NC, NW>;
     constexpr int EPB = G::Eng::EPB;
     const uint64_t nb = PERSIST ? rollout_f32_resident_episodes(a.reserve_cus) / (8 * EPW) : (a.num_episodes + EPB - 1) / EPB;   // persistent: one workgroup per CU
     if (nb == 0 || nb > 0x7fffffffull) { set_error("mcts: bad episode count %llu", (unsigned long long)a.num_episodes); return TW_ERR_INVALID; }
     const size_t lds_bytes = (G::Eng::lds_floats(a.pol) + (size_t)3 * PATH_DEPTH * EPB) * sizeof(float);
     if (lds_bytes > 159 * 1024) { set_error("mcts: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&mcts_f32_kernel<NT, NC, NW, PERSIST>), lds_bytes)) return rc;
-#ifdef TW_ABLATE
-    unsigned long long zeros[24] = {0};
-    if (getenv("TW_STAMPS")) TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_mcts_stamps), zeros, sizeof(zeros)));
-#endif
+    TW_STAMPS_CLEAR(g_mcts_stamps);
     hipLaunchKernelGGL((mcts_f32_kernel<NT, NC, NW, PERSIST>), dim3((unsigned)nb), dim3(64 * G::WAVES), lds_bytes, s, a);
     TW_HIP(hipGetLastError());
-#ifdef TW_ABLATE
-    if (getenv("TW_STAMPS")) {
-        unsigned long long h[24];
-        TW_HIP(hipStreamSynchronize(s));
-        TW_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_mcts_stamps), sizeof(h)));
+    TW_STAMPS_REPORT(g_mcts_stamps, s, h, {
         const double w = (double)h[6];
         fprintf(stderr, "mcts stamps: waves %.0f | per wave: fwd %.0f cyc, tree %.0f cyc, trips %.1f | per trip: fwd %.0f, tree %.0f | inner per lane-trip %.2f, max-lane inner per trip %.2f, descents per inner %.2f\n",
                 w, h[0] / w, h[1] / w, h[2] / w, (double)h[0] / h[2], (double)h[1] / h[2], (double)h[3] / (32.0 * h[2]), (double)h[4] / h[2], (double)h[5] / (double)h[3]);
@@ -530,8 +494,7 @@ static int launch_mcts_geom(const MctsArgs &a, hipStream_t s, uint32_t *blocks, 
                 (double)h[16] / h[2], (double)h[17] / h[2], (double)h[18] / h[2], (double)h[19] / h[2], (double)h[21] / h[2], (double)h[20] / h[2]);
         fprintf(stderr, "  split engine per trip: prologue %.0f, chunk compute %.0f, vmcnt wait %.0f, barrier wait %.0f, heads %.0f\n",
                 (double)h[8] / h[2], (double)h[9] / h[2], (double)h[10] / h[2], (double)h[11] / h[2], (double)h[12] / h[2]);
-    }
-#endif
+    });
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = 64 * G::WAVES;
     return TW_OK;

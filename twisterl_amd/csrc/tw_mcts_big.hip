@@ -36,8 +36,8 @@ template <int NC>
 __global__ void __launch_bounds__(256, 1) mcts_big_kernel(const MctsArgs a, uint16_t *obs16)
 {
     // (the MFMAs as the intrinsic: this kernel parks registers in AGPRs, and a reload the allocator puts right in front of an
-    //  inline-asm MFMA comes without the wait states an MFMA needs after a VALU write -- tw_engine_generic.hpp, ASM_MFMA)
-    using Eng = EngineV<NC, false>;
+    //  inline-asm MFMA comes without the wait states an MFMA needs after a VALU write -- tw_engine_generic.hpp)
+    using Eng = EngineV<NC>;
     using Board = typename BoardOf<NC>::T;
     using Lane = BigLaneT<Board>;
     constexpr int BW = (int)(sizeof(Board) / 4);                      // dwords of a board
@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(256, 1) mcts_big_kernel(const MctsArgs a, uint
 template <int NC>
 static int launch_mcts_big_nc(const MctsArgs &a, uint16_t *obs16, hipStream_t s, uint32_t *blocks, uint32_t *threads)
 {
-    using Eng = EngineV<NC, false>;
+    using Eng = EngineV<NC>;
     using Board = typename BoardOf<NC>::T;
     const uint64_t nb = (a.num_episodes + Eng::EPB - 1) / Eng::EPB;
     if (nb == 0 || nb > 0x7fffffffull) { set_error("mcts (boards above 16 cells): bad episode count %llu", (unsigned long long)a.num_episodes); return TW_ERR_INVALID; }

@@ -113,10 +113,10 @@ __host__ __device__ inline size_t deep_extra_floats(int columns, uint32_t lds_no
            (size_t)walkers * ((size_t)lds_nodes * 6 + deep_pool(walkers) + deep_pool(walkers) * 8);
 }
 
-#ifdef TW_ABLATE
-__device__ unsigned long long g_deep_stamps[16];
-__device__ unsigned long long g_deep_extra[4];
-#endif
+// cycle stamps (tw_common.hpp): [0] fwd [1] tree [2] barrier / result wait [3] trips [4] search-loop passes [5] stored outputs consumed
+// [6] waves [7] assembly [8] pre [9] descents [10] leaf phase [11] backprops [12] move finish [13] resume [14] descent levels |
+// the walker waves' trips: [15] dead [16] yielded (no demand) [17] root evaluations [18] leaf demands | [19] columns evaluated ahead
+TW_STAMP_ARRAY(g_deep_stamps, 20);
 
 // DEC, the decoupled shape (round 4): the four engine waves ONLY run forwards, NWK more waves ONLY walk (4 + NWK waves per workgroup).
 // A walker that needs an output posts its columns and waits for THAT forward; a walker that needs none is never stopped -- in the
@@ -136,7 +136,7 @@ template <int NT, int NC, int NW, int NWK, bool SOLVE = false, bool DEC = false,
 __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK > 4 ? 512 : 256)), 1) mcts_deep_kernel(const MctsArgs a)
 {
     static_assert(!SPL || (DEC && !SOLVE), "the split shape is a decoupled self-play shape");
-    using Eng = typename Geom<NT, NC, 0, NW>::Eng;
+    using Eng = typename Geom<NT, NC, NW>::Eng;
     typedef unsigned int ux4 __attribute__((ext_vector_type(4)));
     typedef unsigned int ux2 __attribute__((ext_vector_type(2)));
     typedef __attribute__((address_space(3))) ux4 lds_u4;
@@ -147,7 +147,7 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
     constexpr int TWV = SPL ? NWK : DEC ? DEEP_WAVES + NWK : (NWK > DEEP_WAVES ? NWK : DEEP_WAVES);   // waves per workgroup
     constexpr bool PARK = !DEC && TWV > DEEP_WAVES;            // coupled eight-walker shape: the walker state waits in LDS during a forward
     constexpr int DEEP_POOL = deep_pool(NWK);
-    static_assert(Geom<NT, NC, 0, NW>::WAVES == DEEP_WAVES && NWK >= 1 && NWK <= (SPL ? 16 : 8) && CPW >= 2 && CPW <= 64, "one walker per wave");
+    static_assert(Geom<NT, NC, NW>::WAVES == DEEP_WAVES && NWK >= 1 && NWK <= (SPL ? 16 : 8) && CPW >= 2 && CPW <= 64, "one walker per wave");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     bool engw = true;                                          // this wave runs the forward
@@ -568,18 +568,11 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
         }
     }
 
-#ifdef TW_ABLATE
-    unsigned long long c_fwd = 0, c_tree = 0, c_bar = 0, c_trips = 0, c_search = 0, c_hits = 0, c_asm = 0, c_yield = 0, c_root = 0, c_dead = 0, c_nspec = 0;
-    unsigned long long c_pre = 0, c_desc = 0, c_leaf = 0, c_bp = 0, c_fin = 0, c_res = 0, c_lvl = 0;
-#define TW_DS(var) const unsigned long long var = __builtin_readcyclecounter()
-#define TW_DA(acc, x, y) acc += (y) - (x)
-#else
-#define TW_DS(var)
-#define TW_DA(acc, x, y)
-#endif
+    TW_STAMP_VARS(c_fwd = 0, c_tree = 0, c_bar = 0, c_trips = 0, c_search = 0, c_hits = 0, c_asm = 0, c_pre = 0, c_desc = 0, c_leaf = 0, c_bp = 0,
+                  c_fin = 0, c_res = 0, c_lvl = 0, c_dead = 0, c_yield = 0, c_root = 0, c_dem = 0, c_nspec = 0);
     // (decoupled shape: only the walker waves run this loop -- the engine waves have served their last forward above)
     if (!DEC || walker) for (;;) {
-        TW_DS(z0);
+        TW_STAMP(z0);
         if constexpr (DEC) {
             if (phase == DP_DEAD) break;                       // (marked dead where the last episode ended)
             wait_result();                                     // the forward that carries this walker's columns
@@ -587,8 +580,8 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
         } else {
             if (!__syncthreads_or(live)) break;
         }
-        TW_DS(z1);
-        TW_DA(c_bar, z0, z1);
+        TW_STAMP(z1);
+        TW_STAMP_ADD(c_bar, z0, z1);
         if constexpr (!DEC) {
             // ---- Policy::full_predict of the C requested boards (policy.rs:102-126) -------------------------------------
             if (engw) {
@@ -607,17 +600,18 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
         }
-        TW_DS(z2);
-        TW_DA(c_fwd, z1, z2);
-#ifdef TW_ABLATE
-        ++c_trips;
-        if (phase == DP_DEAD) { if (walker) ++c_dead; } else if (yielded) ++c_yield; else if (phase == DP_ROOT) ++c_root;
-        c_nspec += (unsigned long long)n_spec;
-#endif
+        TW_STAMP(z2);
+        TW_STAMP_ADD(c_fwd, z1, z2);
+        TW_STAMP_COUNT(c_trips, 1);
+        TW_STAMP_COUNT(c_dead, walker && phase == DP_DEAD);                        // a walker's trip: dead | yielded | root | leaf demand
+        TW_STAMP_COUNT(c_yield, walker && phase != DP_DEAD && yielded);
+        TW_STAMP_COUNT(c_root, walker && phase == DP_ROOT && !yielded);
+        TW_STAMP_COUNT(c_dem, walker && phase == DP_LEAF && !yielded);
+        TW_STAMP_COUNT(c_nspec, n_spec);
 
         // ---- tree phase of this wave's walker ------------------------------------------------------------------------
         if (phase != DP_DEAD) {
-            TW_DS(y0);
+            TW_STAMP(y0);
             if constexpr (!DEC) wait_f[wave] = 0;              // (every lane stores: a lane-0 branch here costs the walk its scalar branches)
             // outputs evaluated ahead of the search -> their nodes (arena) and the LDS pool; the node's hot quad gets the flag
             if (my_take) {
@@ -783,8 +777,8 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                 phase = DP_LEAF;
             };
             bool resume = false;
-            TW_DS(y1);
-            TW_DA(c_pre, y0, y1);
+            TW_STAMP(y1);
+            TW_STAMP_ADD(c_pre, y0, y1);
             const unsigned long long tree_t0 = __builtin_readcyclecounter();
             if (yielded) {
                 yielded = false;                                 // stopped between two searches: go on searching
@@ -795,11 +789,9 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
             }
 
             for (;;) {
-#ifdef TW_ABLATE
-                ++c_search;
-#endif
+                TW_STAMP_COUNT(c_search, 1);
                 bool need_nn = false;
-                TW_DS(y2);
+                TW_STAMP(y2);
                 if (!resume) {
                     if (!DEC && it != S && (NWK > 1 || a.tree_budget != 0xffffffffu)) { // (a lone walker keeps nobody waiting; decoupled walkers never do)
                         const unsigned long long walked = __builtin_readcyclecounter() - tree_t0;
@@ -872,7 +864,7 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                             }
                             if ((uint64_t)got < E) take(nth((uint64_t)got));
                             else { more = false; phase = DP_DEAD; }
-                            TW_DS(y9); TW_DA(c_fin, y2, y9);
+                            TW_STAMP(y9); TW_STAMP_ADD(c_fin, y2, y9);
                             break;
                         }
                         if (!sv_on) { puzzle_step(st, env, action); ++t; }                               // az.rs:89
@@ -884,12 +876,12 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                             if (tbl_get(st.board, rp, rv)) {
                                 start_move(rp);
                                 ++reused;
-                                TW_DS(y9); TW_DA(c_fin, y2, y9);
+                                TW_STAMP(y9); TW_STAMP_ADD(c_fin, y2, y9);
                                 continue;
                             }
                         }
                         phase = DP_ROOT;
-                        TW_DS(y9); TW_DA(c_fin, y2, y9);
+                        TW_STAMP(y9); TW_STAMP_ADD(c_fin, y2, y9);
                         break;
                     }
                     // ---- descend to a leaf by UCB (search.rs:133-138, next :77-91, ucb :29-39): four lanes score the four
@@ -903,13 +895,11 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                         node = b & LK_CB;
                         puzzle_step_legal(cur, env, (int)((b >> 27) & 3u));
                         push(node);
-#ifdef TW_ABLATE
-                        ++c_lvl;
-#endif
+                        TW_STAMP_COUNT(c_lvl, 1);
                     }
                     if (node != 0u) cur_link = uniu(hot_ld_link(node));       // the leaf's flags and action
                     value = 0.0f; expanded = 0;
-                    TW_DS(y3); TW_DA(c_desc, y2, y3);
+                    TW_STAMP(y3); TW_STAMP_ADD(c_desc, y2, y3);
                 } else {
                     // ---- the demanded leaf's output has arrived (search.rs:154-159): expand, sample a child by the priors ---
                     resume = false;
@@ -919,10 +909,10 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                     if (nch > 0) sample_child(cb, nch);
                     value = nn_value;
                     ++expanded;
-                    TW_DS(y5); TW_DA(c_res, y2, y5);
+                    TW_STAMP(y5); TW_STAMP_ADD(c_res, y2, y5);
                 }
                 {
-                    TW_DS(y3);
+                    TW_STAMP(y3);
                     // leaf phase (search.rs:143-160); after a demand: the further expansion levels of the same search (max_expand_depth > 1)
                     while (expanded < MED) {
                         value = puzzle_reward(cur, env);                                  // :146
@@ -951,9 +941,7 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                             ++reused;
                         }
                         ++evals;
-#ifdef TW_ABLATE
-                        ++c_hits;
-#endif
+                        TW_STAMP_COUNT(c_hits, 1);
                         const uint32_t cb = n_nodes;
                         const uint32_t nch = expand(node, cur_link, cur, lp);             // :156
                         cur_link &= ~LK_OUT;                                              // (no children: the same node is looked at again)
@@ -961,18 +949,18 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
                         value = lv;                                                       // :158
                         ++expanded;
                     }
-                    TW_DS(y4); TW_DA(c_leaf, y3, y4);
+                    TW_STAMP(y4); TW_STAMP_ADD(c_leaf, y3, y4);
                 }
                 if (need_nn) { dem_idx = node; break; }
-                TW_DS(y6);
+                TW_STAMP(y6);
                 backprop(node, value);                                                    // :163
                 ++it;
-                TW_DS(y7); TW_DA(c_bp, y6, y7);
+                TW_STAMP(y7); TW_STAMP_ADD(c_bp, y6, y7);
             }
             if constexpr (!DEC) wait_f[wave] = (phase != DP_DEAD && !yielded) ? 1 : 0;    // stopped in front of a forward it needs
         }
-        TW_DS(z3);
-        TW_DA(c_tree, z2, z3);
+        TW_STAMP(z3);
+        TW_STAMP_ADD(c_tree, z2, z3);
         assemble();
         if constexpr (DEC) {
             if (phase != DP_DEAD) post(); else mark_dead();
@@ -980,23 +968,14 @@ __global__ void __launch_bounds__((SPL ? 64 * NWK : DEC ? 64 * (4 + NWK) : (NWK 
             live = phase != DP_DEAD ? 1 : 0;
             park();
         }
-        TW_DS(z4);
-        TW_DA(c_asm, z3, z4);
+        TW_STAMP(z4);
+        TW_STAMP_ADD(c_asm, z3, z4);
     }
     if constexpr (DEC) { if (walker && aborted) mark_dead(); }     // (a walker that left through the watchdog must not keep the engine waves waiting)
     unpark();
     if (lane == 0) { atomicAdd(a.eval_count, evals); atomicAdd(a.eval_count + 1, spec_evals); atomicAdd(a.eval_count + 2, reused); }
-#ifdef TW_ABLATE
-    if (lane == 0) {
-        atomicAdd(&g_deep_stamps[0], c_fwd); atomicAdd(&g_deep_stamps[1], c_tree); atomicAdd(&g_deep_stamps[2], c_bar);
-        atomicAdd(&g_deep_stamps[3], c_trips); atomicAdd(&g_deep_stamps[4], c_search); atomicAdd(&g_deep_stamps[5], c_hits);
-        if (wave < NWK) { atomicAdd(&g_deep_stamps[15], c_yield); }
-        atomicAdd(&g_deep_extra[0], c_root); atomicAdd(&g_deep_extra[1], c_dead); atomicAdd(&g_deep_extra[2], c_nspec); atomicAdd(&g_deep_extra[3], wave < NWK ? c_trips : 0ull);
-        atomicAdd(&g_deep_stamps[6], 1ull); atomicAdd(&g_deep_stamps[7], c_asm);
-        atomicAdd(&g_deep_stamps[8], c_pre); atomicAdd(&g_deep_stamps[9], c_desc); atomicAdd(&g_deep_stamps[10], c_leaf);
-        atomicAdd(&g_deep_stamps[11], c_bp); atomicAdd(&g_deep_stamps[12], c_fin); atomicAdd(&g_deep_stamps[13], c_res); atomicAdd(&g_deep_stamps[14], c_lvl);
-    }
-#endif
+    TW_STAMP_FLUSH(lane == 0, g_deep_stamps, c_fwd, c_tree, c_bar, c_trips, c_search, c_hits, 1, c_asm, c_pre, c_desc, c_leaf, c_bp, c_fin, c_res, c_lvl,
+                   c_dead, c_yield, c_root, c_dem, c_nspec);
     if (engw) eng.end();
 }
 
@@ -1200,9 +1179,6 @@ void mcts_deep_disable_split() { g_split_disabled.store(1); }
 // and at 100 searches per move a walker spends more time waiting for outputs than walking (tree 43 k cycles per demand, wait 74 k).
 static int split_walkers_per_group(uint32_t num_searches)
 {
-#ifdef TW_ABLATE
-    if (const char *e = getenv("TW_SPLIT_WALKERS")) { const int n = atoi(e); if (n == 8 || n == 12 || n == 16) return n; }
-#endif
     return num_searches >= 400 ? 16 : 12;              // 1 x 16 walker waves per CU for long searches, 2 x 12 for short ones
 }
 static int split_groups_per_cu(int walkers_per_group) { return walkers_per_group <= 12 ? 2 : 1; }
@@ -1249,9 +1225,6 @@ static DeepShape deep_shape(uint64_t num_episodes, int reserve_cus, uint32_t num
     // The split shape (walkers and engine as two kernels): from eight episodes per CU on.  Four engine workgroups per XCD serve the walker
     // workgroups on the other CUs.  TW_OPT_AZ_VARIANT + 512 pins it on, + 1024 off.
     sh.engines = (int)avail / 2;
-#ifdef TW_ABLATE
-    if (const char *e = getenv("TW_SPLIT_ENGINES")) { const int n = atoi(e); if (n >= 1 && n < (int)avail) sh.engines = n; }
-#endif
     sh.split = !solve && !sh.wide && (v & 7) == 0 && avail >= 16 && num_episodes >= 8 * avail && !(v & 256);
     if ((v & 1024) || g_split_disabled.load()) sh.split = false;
     if ((v & 512) && !solve && avail >= 16 && !g_split_disabled.load()) { sh.split = true; sh.wide = false; }
@@ -1273,6 +1246,18 @@ uint64_t mcts_deep_walkers(uint64_t num_episodes, int reserve_cus, uint32_t num_
 }
 bool mcts_deep_split(uint64_t num_episodes, int reserve_cus, uint32_t num_searches, bool solve) { return deep_shape(num_episodes, reserve_cus, num_searches, solve).split; }
 
+#ifdef TW_ABLATE   // the lines both launchers print from g_deep_stamps (TW_STAMPS=1)
+static void print_walker_stamps(const unsigned long long (&h)[20])
+{
+    const double tr = (double)h[3];
+    fprintf(stderr, "  walker trips %llu: dead %llu, yielded (no demand) %llu, root evaluations %llu, leaf demands %llu | columns evaluated ahead %llu, consumed %llu\n",
+            h[15] + h[16] + h[17] + h[18], h[15], h[16], h[17], h[18], h[19], h[5]);
+    fprintf(stderr, "  tree phase per trip: store ahead-outputs + read demand %.0f | descents %.0f (%.2f levels per trip) | leaf phase incl. stored-output expansions %.0f | "
+                    "resume (expand demanded leaf) %.0f | backprops %.0f | move finish %.0f\n",
+            h[8] / tr, h[9] / tr, h[14] / tr, h[10] / tr, h[13] / tr, h[11] / tr, h[12] / tr);
+}
+#endif
+
 // The split shape: mcts_engine_kernel on a side stream (first: its workgroups are resident before the walkers need them; it ends when every
 // walker has said it is done), mcts_deep_kernel<.., SPL> on the caller's stream, which then waits for the engine's end.  Walker workgroups
 // + engine workgroups <= CUs: every one of them is resident whatever the placement (neither kind fits twice beside the other: 127 KB and
@@ -1283,7 +1268,7 @@ static hipEvent_t g_split_ready[64] = {}, g_split_done[64] = {};
 template <int NT, int NC, int NWK>
 static int launch_deep_split(const MctsArgs &a, const DeepShape &sh, hipStream_t s, uint32_t *blocks, uint32_t *threads)
 {
-    using G = Geom<NT, NC, 0, -16>;
+    using G = Geom<NT, NC, -16>;
     if (!a.mailbox) { set_error("mcts (deep, split): no mailboxes"); return TW_ERR_INVALID; }
     const uint64_t walkers = mcts_deep_walkers(a.num_episodes, a.reserve_cus, a.num_searches, false);
     const uint64_t nb = walkers / NWK;
@@ -1314,9 +1299,7 @@ static int launch_deep_split(const MctsArgs &a, const DeepShape &sh, hipStream_t
         }
         es = g_split_stream[dev]; ready = g_split_ready[dev]; done = g_split_done[dev];
     }
-#ifdef TW_ABLATE
-    { unsigned long long zeros[16] = {0}; if (getenv("TW_STAMPS")) { TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_deep_stamps), zeros, sizeof(zeros))); TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_deep_extra), zeros, 32)); } }
-#endif
+    TW_STAMPS_CLEAR(g_deep_stamps);
     // (TW_OPT_AZ_VARIANT + 2048, a test hook: both kernels on the caller's stream, ONE AFTER THE OTHER -- what a tool that serialises kernel
     //  launches does to them; both then run into their watchdogs and tw_az_collect falls back to the single-kernel shapes)
     if (launch_options().az_variant & 2048) es = s;
@@ -1329,20 +1312,13 @@ static int launch_deep_split(const MctsArgs &a, const DeepShape &sh, hipStream_t
     hipLaunchKernelGGL((mcts_deep_kernel<NT, NC, -16, NWK, false, true, true>), dim3((unsigned)nb), dim3(64 * NWK), lds_w, s, b);
     TW_HIP(hipGetLastError());
     TW_HIP(hipStreamWaitEvent(s, done, 0));                 // the collect goes on when both kernels have ended
-#ifdef TW_ABLATE
-    if (getenv("TW_STAMPS")) {
-        unsigned long long h[16];
-        TW_HIP(hipStreamSynchronize(s));
-        TW_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_deep_stamps), sizeof(h)));
+    TW_STAMPS_REPORT(g_deep_stamps, s, h, {
         const double w = (double)h[6], tr = (double)h[3];
         fprintf(stderr, "split stamps: walkers %.0f (x %d per workgroup, %llu engines), lds nodes %u | per walker: tree %.0f, assembly %.0f, waiting for results %.0f cycles, trips %.1f | per trip: tree %.0f, wait %.0f | "
                         "search-loop passes per trip %.2f, stored outputs consumed per trip %.2f\n",
                 w, NWK, (unsigned long long)ne, b.lds_nodes, h[1] / w, h[7] / w, h[2] / w, tr / w, h[1] / tr, h[2] / tr, (double)h[4] / tr, (double)h[5] / tr);
-        fprintf(stderr, "  tree phase per trip: store ahead-outputs + read demand %.0f | descents %.0f (%.2f levels per trip) | leaf phase incl. stored-output expansions %.0f | "
-                        "resume (expand demanded leaf) %.0f | backprops %.0f | move finish %.0f\n",
-                h[8] / tr, h[9] / tr, h[14] / tr, h[10] / tr, h[13] / tr, h[11] / tr, h[12] / tr);
-    }
-#endif
+        print_walker_stamps(h);
+    });
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = 64 * NWK;
     return TW_OK;
@@ -1352,7 +1328,7 @@ static int launch_deep_split(const MctsArgs &a, const DeepShape &sh, hipStream_t
 template <int NT, int NC, int NW, int NWK, bool SOLVE = false, bool DEC = false>
 static int launch_deep_nwk(const MctsArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads)
 {
-    using G = Geom<NT, NC, 0, NW>;
+    using G = Geom<NT, NC, NW>;
     constexpr int C = G::Eng::EPB;
     constexpr unsigned THREADS = DEC ? 64u * (DEEP_WAVES + NWK) : (NWK > DEEP_WAVES ? 64u * NWK : 64u * DEEP_WAVES);
     const uint64_t nb = mcts_deep_walkers(a.num_episodes, a.reserve_cus, a.num_searches, SOLVE) / NWK;
@@ -1375,30 +1351,16 @@ static int launch_deep_nwk(const MctsArgs &a, hipStream_t s, uint32_t *blocks, u
     if (NWK == 8 && launch_options().az_tree_budget_min == 0 && b.tree_budget > 56000u) b.tree_budget_min = 56000u;
     const size_t lds_bytes = (eng_floats + deep_extra_floats(C, b.lds_nodes, NWK, DEC)) * sizeof(float);
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&mcts_deep_kernel<NT, NC, NW, NWK, SOLVE, DEC>), lds_bytes)) return rc;
-#ifdef TW_ABLATE
-    unsigned long long zeros[16] = {0};
-    if (getenv("TW_STAMPS")) { TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_deep_stamps), zeros, sizeof(zeros))); TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_deep_extra), zeros, 32)); }
-#endif
+    TW_STAMPS_CLEAR(g_deep_stamps);
     hipLaunchKernelGGL((mcts_deep_kernel<NT, NC, NW, NWK, SOLVE, DEC>), dim3((unsigned)nb), dim3(THREADS), lds_bytes, s, b);
     TW_HIP(hipGetLastError());
-#ifdef TW_ABLATE
-    if (getenv("TW_STAMPS")) {
-        unsigned long long h[16];
-        TW_HIP(hipStreamSynchronize(s));
-        TW_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_deep_stamps), sizeof(h)));
-        unsigned long long x[4];
-        TW_HIP(hipMemcpyFromSymbol(x, HIP_SYMBOL(g_deep_extra), sizeof(x)));
-        fprintf(stderr, "  walker trips %llu: dead %llu, yielded (no demand) %llu, root evaluations %llu, leaf demands %llu | columns evaluated ahead %llu, consumed %llu\n",
-                x[3], x[1], h[15], x[0], x[3] - x[1] - h[15] - x[0], x[2], h[5]);
+    TW_STAMPS_REPORT(g_deep_stamps, s, h, {
         const double w = (double)h[6], tr = (double)h[3];
         fprintf(stderr, "deep stamps: waves %.0f, lds nodes %u | per wave: fwd %.0f, tree %.0f, assembly %.0f, barrier wait %.0f cycles, trips %.1f | per trip: fwd %.0f, tree %.0f, assembly %.0f, barrier %.0f | "
                         "search-loop passes per trip %.2f, stored outputs consumed per trip %.2f\n",
                 w, b.lds_nodes, h[0] / w, h[1] / w, h[7] / w, h[2] / w, tr / w, h[0] / tr, h[1] / tr, h[7] / tr, h[2] / tr, (double)h[4] / tr, (double)h[5] / tr);
-        fprintf(stderr, "  tree phase per trip: store ahead-outputs + read demand %.0f | descents %.0f (%.2f levels per trip) | leaf phase incl. stored-output expansions %.0f | "
-                        "resume (expand demanded leaf) %.0f | backprops %.0f | move finish %.0f\n",
-                h[8] / tr, h[9] / tr, h[14] / tr, h[10] / tr, h[13] / tr, h[11] / tr, h[12] / tr);
-    }
-#endif
+        print_walker_stamps(h);
+    });
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = THREADS;
     return TW_OK;

@@ -180,16 +180,14 @@ int launch_episode_order(const PuzzleConsts &env, const uint64_t *boards, uint64
     return TW_OK;
 }
 
-#ifdef TW_ABLATE   // diagnostic build: cycle stamps of the generic engine (TW_STAMPS=1 prints them per launch)
-__device__ unsigned long long g_gen_stamps[8];
-#endif
+TW_STAMP_ARRAY(g_gen_stamps, 8);   // cycle stamps of the generic engine and the 32- and 16-episode shapes (tw_common.hpp)
 
 // (the generic engine's workgroups are small -- 256 threads, exact-size activation buffers: two of them share a CU, and while one
 //  gathers its embeddings from L2 the other one keeps the matrix cores busy)
-template <int NT, int NC, int DBG = 0, int NW = 8, bool PERSIST = false>
-__global__ void __launch_bounds__((Geom<NT, NC, DBG, NW>::WAVES * 64), ((NW == 8 || NW == -65 || NW == -5) ? 2 : 1)) rollout_f32_kernel(const RolloutArgs a)
+template <int NT, int NC, int NW = 8, bool PERSIST = false>
+__global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || NW == -65) ? 2 : 1)) rollout_f32_kernel(const RolloutArgs a)
 {
-    using Eng = typename Geom<NT, NC, DBG, NW>::Eng;       // NW < 0: -NW waves share 32 episodes (Engine3S); all carry the same state
+    using Eng = typename Geom<NT, NC, NW>::Eng;       // NW < 0: -NW waves share 32 episodes (Engine3S); all carry the same state
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.begin1(a.pol, lds);                               // first weight chunks stream in while the scramble runs
@@ -218,15 +216,11 @@ __global__ void __launch_bounds__((Geom<NT, NC, DBG, NW>::WAVES * 64), ((NW == 8
 
     eng.begin2();
     // (the barrier inside __syncthreads_or publishes the first two ring slots and the LDS constants)
-#ifdef TW_ABLATE
-    const unsigned long long q_loop = __builtin_readcyclecounter();
-    unsigned long long n_fwd = 0;
-#endif
+    TW_STAMP(q_loop);
+    TW_STAMP_VARS(n_fwd = 0);
 
     while (__syncthreads_or(alive ? 1 : 0)) {
-#ifdef TW_ABLATE
-        ++n_fwd;
-#endif
+        TW_STAMP_COUNT(n_fwd, 1);
         // ---- observe (puzzle.rs:183-185) + twist of the obs ids (policy.rs:67-83) -------------
         int perm = -1;
         if (eng.pol.n_perms > 0) {
@@ -241,17 +235,15 @@ __global__ void __launch_bounds__((Geom<NT, NC, DBG, NW>::WAVES * 64), ((NW == 8
 
         PuzzleLane st; st.board = board; st.depth = depth;
         { const int z = blank_cell(board); st.zx = z % env.width; st.zy = z / env.width; }
-        float rew = 0.0f; int action = t & 3;
-        if constexpr (!(DBG & 8)) {
-            eng.act_perm(perm, lg);
-            const uint32_t mb = puzzle_maskbits(st, env);
+        eng.act_perm(perm, lg);
+        const uint32_t mb = puzzle_maskbits(st, env);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) lg[i] = ((mb >> i) & 1u) ? lg[i] : -1e10f;   // policy.rs:62
-            rew = puzzle_reward(st, env);
-            const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
-            if constexpr (NW == 8) action = gumbel_argmax4_halves(lg, gw, h != 0);   // (lanes j and j+32: one episode)
-            else action = gumbel_argmax4(lg, gw);
-        }
+        for (int i = 0; i < 4; ++i) lg[i] = ((mb >> i) & 1u) ? lg[i] : -1e10f;   // policy.rs:62
+        const float rew = puzzle_reward(st, env);
+        const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
+        int action;
+        if constexpr (NW == 8) action = gumbel_argmax4_halves(lg, gw, h != 0);   // (lanes j and j+32: one episode)
+        else action = gumbel_argmax4(lg, gw);
         // ---- push the record (ppo.rs:71-76), then is_final / step (ppo.rs:78-79) --------------
         if (alive) {
             if (writer) {
@@ -287,16 +279,12 @@ __global__ void __launch_bounds__((Geom<NT, NC, DBG, NW>::WAVES * 64), ((NW == 8
     }
     if constexpr (!PERSIST) { if (valid && writer) a.out.ep_len[e_local] = (uint32_t)t + 1u; }
     eng.end();
-#ifdef TW_ABLATE
-    if constexpr (NW == -64 || NW == -65) {
-        if (eng.lane == 0 && (eng.wave == 0 || eng.wave == 3)) for (int i = 0; i < 4; ++i) atomicAdd(&g_gen_stamps[(eng.wave ? 4 : 0) + i], eng.stq[i]);
+    if constexpr (NW == -65)                              // waves 0 and 3: embed | common | value | action
+        TW_STAMP_FLUSH(eng.lane == 0 && (eng.wave == 0 || eng.wave == 3), g_gen_stamps + (eng.wave ? 4 : 0), eng.stq[0], eng.stq[1], eng.stq[2], eng.stq[3]);
+    if constexpr (NW == -16 || NW == -4) {                // wave 0: prologue | chunk loop | - | - | heads; forwards; cycles in the step loop
+        TW_STAMP(q_end);
+        TW_STAMP_FLUSH(eng.lane == 0 && eng.wave == 0, g_gen_stamps, eng.stq[0], eng.stq[1], eng.stq[2], eng.stq[3], eng.stq[4], n_fwd, q_end - q_loop);
     }
-    if constexpr (NW == -16 || NW == -4 || NW == -5) {      // wave 0: prologue | chunk loop | - | - | heads; forwards; cycles in the step loop
-        if (eng.lane == 0 && eng.wave == 0) for (int i = 0; i < 5; ++i) atomicAdd(&g_gen_stamps[i], eng.stq[i]);
-        if (eng.lane == 0 && eng.wave == 0) atomicAdd(&g_gen_stamps[5], n_fwd);
-        if (eng.lane == 0 && eng.wave == 0) atomicAdd(&g_gen_stamps[6], __builtin_readcyclecounter() - q_loop);
-    }
-#endif
 }
 
 // persistent mode: one 256-episode workgroup per CU of the current device (256 on an MI355X; every rollout kernel needs
@@ -330,43 +318,32 @@ uint64_t f32_resident_episodes(uint64_t num_episodes, int hidden, bool selfplay,
     const uint64_t full = rollout_f32_resident_episodes(reserve_cus), small = full / 8;
     const bool in_range = selfplay ? num_episodes * 4 <= full * 3 : waves_per_group(num_episodes) != 8;
     if (hidden >= 128 && num_episodes > small && in_range && !launch_options().force_geom) {
-#ifdef TW_ABLATE   // diagnostic build, TW_MID_G=1: two 32-episode workgroups per CU (Engine3G; measured no faster -- profiles/r03_mid_rollout_two_groups_per_cu.txt)
-        if (!selfplay && num_episodes >= 2 * small && getenv("TW_MID_G")) return 2 * small;
-#endif
         return small;
     }
     return full;
 }
 
-template <int NT, int NC, int DBG = 0, int NW = 8, bool PERSIST = false>
+template <int NT, int NC, int NW = 8, bool PERSIST = false>
 static int launch_geom(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads)
 {
-    using G = Geom<NT, NC, DBG, NW>;
+    using G = Geom<NT, NC, NW>;
     constexpr int EPB = G::Eng::EPB, THREADS = 64 * G::WAVES;
-    const uint64_t nb = PERSIST ? persist_blocks(a.reserve_cus) * (NW == -65 ? generic_groups_per_cu(a.pol, a.env.n_cells) : (NW == -5 ? 2 : 1)) : (a.num_episodes + EPB - 1) / EPB;
+    const uint64_t nb = PERSIST ? persist_blocks(a.reserve_cus) * (NW == -65 ? generic_groups_per_cu(a.pol, a.env.n_cells) : 1) : (a.num_episodes + EPB - 1) / EPB;
     if (nb == 0 || nb > 0x7fffffffull) { set_error("rollout: bad episode count %llu", (unsigned long long)a.num_episodes); return TW_ERR_INVALID; }
     const size_t lds_bytes = G::Eng::lds_floats(a.pol) * sizeof(float);
     if (lds_bytes > 159 * 1024) { set_error("rollout: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&rollout_f32_kernel<NT, NC, DBG, NW, PERSIST>), lds_bytes)) return rc;
-#ifdef TW_ABLATE
-    const bool stamps = (NW == -64 || NW == -65 || NW == -16 || NW == -4 || NW == -5) && getenv("TW_STAMPS");
-    if (stamps) { unsigned long long z[8] = {0}; TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_gen_stamps), z, sizeof(z))); }
-    { const char *d = getenv("TW_ENG_DBG"); const int v = d ? atoi(d) : 0; TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_eng_dbg), &v, sizeof(v))); }
-#endif
-    hipLaunchKernelGGL((rollout_f32_kernel<NT, NC, DBG, NW, PERSIST>), dim3((unsigned)nb), dim3(THREADS), lds_bytes, s, a);
-#ifdef TW_ABLATE
-    if (stamps) {
-        unsigned long long g[8];
-        TW_HIP(hipStreamSynchronize(s));
-        TW_HIP(hipMemcpyFromSymbol(g, HIP_SYMBOL(g_gen_stamps), sizeof(g)));
-        if (NW == -64 || NW == -65)
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&rollout_f32_kernel<NT, NC, NW, PERSIST>), lds_bytes)) return rc;
+    constexpr bool STAMPED = NW == -65 || NW == -16 || NW == -4;      // the shapes that take cycle stamps
+    if constexpr (STAMPED) TW_STAMPS_CLEAR(g_gen_stamps);
+    hipLaunchKernelGGL((rollout_f32_kernel<NT, NC, NW, PERSIST>), dim3((unsigned)nb), dim3(THREADS), lds_bytes, s, a);
+    if constexpr (STAMPED) TW_STAMPS_REPORT(g_gen_stamps, s, g, {
+        if (NW == -65)
             fprintf(stderr, "[generic engine stamps, cycles summed over %llu workgroups] wave0: embed %llu common %llu value %llu action %llu | wave3: %llu %llu %llu %llu\n",
                     (unsigned long long)nb, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7]);
         else
             fprintf(stderr, "[geometry %d, wave 0, cycles per forward] prologue %.0f chunk loop %.0f heads %.0f | whole step %.0f (%llu forwards)\n",
                     NW, (double)g[0] / g[5], (double)g[1] / g[5], (double)g[4] / g[5], (double)g[6] / g[5], g[5]);
-    }
-#endif
+    });
     TW_HIP(hipGetLastError());
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = THREADS;
@@ -376,37 +353,22 @@ static int launch_geom(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, ui
 template <int NT, int NC>
 static int launch_one(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads)
 {
-#ifdef TW_ABLATE   // timing-only ablation builds: TW_ROLLOUT_DBG = 1 | 2 | 4 | 8 (see tw_engine.hpp)
-    if constexpr (NT == 8 && NC == 16) {
-        const char *d = getenv("TW_ROLLOUT_DBG");
-        switch (d ? atoi(d) : 0) {
-            case 1: return launch_geom<NT, NC, 1>(a, s, blocks, threads);
-            case 2: return launch_geom<NT, NC, 2>(a, s, blocks, threads);
-            case 4: return launch_geom<NT, NC, 4>(a, s, blocks, threads);
-            case 8: return launch_geom<NT, NC, 8>(a, s, blocks, threads);
-            default: break;
-        }
-    }
-#endif
     // small batches: fewer waves per workgroup, so that the episodes spread over more CUs
     const uint64_t resident = f32_resident_episodes(a.num_episodes, a.pol.hidden, false, a.reserve_cus);
     if (a.queue && a.init_boards && a.num_episodes > resident) {
         if constexpr (NT >= 4) {
             const uint64_t full = rollout_f32_resident_episodes(a.reserve_cus);
-#ifdef TW_ABLATE
-            if (resident == full / 4) return launch_geom<NT, NC, 0, -5, true>(a, s, blocks, threads);
-#endif
-            if (resident < full) return launch_geom<NT, NC, 0, -4, true>(a, s, blocks, threads);
+            if (resident < full) return launch_geom<NT, NC, -4, true>(a, s, blocks, threads);
         }
-        return launch_geom<NT, NC, 0, 8, true>(a, s, blocks, threads);
+        return launch_geom<NT, NC, 8, true>(a, s, blocks, threads);
     }
     const int nw = geometry_for<NT>(a.num_episodes);
-    if constexpr (NT >= 4) { if (nw == -16) return launch_geom<NT, NC, 0, -16>(a, s, blocks, threads); }
-    if constexpr (NT >= 4) { if (nw == -4) return launch_geom<NT, NC, 0, -4>(a, s, blocks, threads); }
-    else if constexpr (NT == 2) { if (nw == -2) return launch_geom<NT, NC, 0, -2>(a, s, blocks, threads); }
+    if constexpr (NT >= 4) { if (nw == -16) return launch_geom<NT, NC, -16>(a, s, blocks, threads); }
+    if constexpr (NT >= 4) { if (nw == -4) return launch_geom<NT, NC, -4>(a, s, blocks, threads); }
+    else if constexpr (NT == 2) { if (nw == -2) return launch_geom<NT, NC, -2>(a, s, blocks, threads); }
     else {
-        if (nw == 1) return launch_geom<NT, NC, 0, 1>(a, s, blocks, threads);
-        if (nw == 2) return launch_geom<NT, NC, 0, 2>(a, s, blocks, threads);
+        if (nw == 1) return launch_geom<NT, NC, 1>(a, s, blocks, threads);
+        if (nw == 2) return launch_geom<NT, NC, 2>(a, s, blocks, threads);
     }
     return launch_geom<NT, NC>(a, s, blocks, threads);
 }
@@ -430,13 +392,13 @@ int launch_rollout_f32(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, ui
         }
         const int nc = a.env.n_cells;
         if (a.queue) {            // more episodes than one 16-episode workgroup per CU: persistent lanes + episode queue
-            if (nc <= 4) return launch_geom<0, 4, 0, -65, true>(a, s, blocks, threads);
-            if (nc <= 9) return launch_geom<0, 9, 0, -65, true>(a, s, blocks, threads);
-            return launch_geom<0, 16, 0, -65, true>(a, s, blocks, threads);
+            if (nc <= 4) return launch_geom<0, 4, -65, true>(a, s, blocks, threads);
+            if (nc <= 9) return launch_geom<0, 9, -65, true>(a, s, blocks, threads);
+            return launch_geom<0, 16, -65, true>(a, s, blocks, threads);
         }
-        if (nc <= 4) return launch_geom<0, 4, 0, -65>(a, s, blocks, threads);
-        if (nc <= 9) return launch_geom<0, 9, 0, -65>(a, s, blocks, threads);
-        return launch_geom<0, 16, 0, -65>(a, s, blocks, threads);
+        if (nc <= 4) return launch_geom<0, 4, -65>(a, s, blocks, threads);
+        if (nc <= 9) return launch_geom<0, 9, -65>(a, s, blocks, threads);
+        return launch_geom<0, 16, -65>(a, s, blocks, threads);
     }
     // host-side shape checks: everything the kernel indexes with is validated here
     if (a.env.n_cells < 1 || a.env.n_cells > 16 || a.pol.obs_size != a.env.n_cells * a.env.n_cells ||

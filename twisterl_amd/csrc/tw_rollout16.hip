@@ -13,17 +13,13 @@
 
 namespace tw {
 
-#ifdef TW_ABLATE
-__device__ unsigned long long g_stamps16[8];
-#endif
+TW_STAMP_ARRAY(g_stamps16, 8);
 
 template <class Eng, int NC, bool PERSIST = false>
 __global__ void __launch_bounds__(256, 1) rollout_f16_kernel(const RolloutArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds16[];
-#ifdef TW_ABLATE
-    const unsigned long long t_kernel0 = __builtin_readcyclecounter();
-#endif
+    TW_STAMP(t_kernel0);
     Eng eng;
     eng.begin1(a.pol, lds16);
 
@@ -72,15 +68,10 @@ __global__ void __launch_bounds__(256, 1) rollout_f16_kernel(const RolloutArgs a
     for (int i = 0; i < 5; ++i) bh[i] = a.pol.bh16[i];          // uniform: scalar loads, live in SGPRs
 
     eng.begin2();
-#ifdef TW_ABLATE
-    for (int i = 0; i < 8; ++i) eng.st[i] = 0;
-    unsigned long long t_prev = __builtin_readcyclecounter();
-#endif
+    TW_STAMP_VARS(t_prev = __builtin_readcyclecounter());
     while (__syncthreads_or((alive0 || alive1) ? 1 : 0)) {
-#ifdef TW_ABLATE
-        const unsigned long long t_top = __builtin_readcyclecounter();
-        eng.st[7] += t_top - t_prev;
-#endif
+        TW_STAMP(t_top);
+        TW_STAMP_ADD(eng.st[7], t_prev, t_top);
         // ---- twist draw for the own tile (policy.rs:67-77), exchanged with the other half --------
         int perm_own = -1;
         if (eng.pol.n_perms > 0) {
@@ -93,16 +84,12 @@ __global__ void __launch_bounds__(256, 1) rollout_f16_kernel(const RolloutArgs a
         eng.onehots(st0.board, perm0, oh.a0);
         eng.onehots(st1.board, perm1, oh.a1);
 
-#ifdef TW_ABLATE
-        asm volatile("" :: "v"(oh.a0[0]), "v"(oh.a1[0]));
-        const unsigned long long t_fw = __builtin_readcyclecounter();
-        eng.st[0] += t_fw - t_top;
-#endif
+        TW_STAMP_USE(oh.a0[0]); TW_STAMP_USE(oh.a1[0]);
+        TW_STAMP(t_fw);
+        TW_STAMP_ADD(eng.st[0], t_top, t_fw);
         f32x16 out0, out1;
         eng.forward(oh, out0, out1);
-#ifdef TW_ABLATE
-        const unsigned long long t_po = __builtin_readcyclecounter();
-#endif
+        TW_STAMP(t_po);
 
         // ---- own tile: head bias, act-perm, mask, reward, Gumbel-max (policy.rs:56-65,169-172) ---
         // (everything below is select-based: one wave per SIMD has nothing to hide a branch behind)
@@ -161,15 +148,12 @@ __global__ void __launch_bounds__(256, 1) rollout_f16_kernel(const RolloutArgs a
             if (t0) { st0 = n0; alive0 = true; }
             if (t1) { st1 = n1; alive1 = true; }
         }
-#ifdef TW_ABLATE
-        t_prev = __builtin_readcyclecounter();
-        eng.st[6] += t_prev - t_po;
-#endif
+        TW_RESTAMP(t_prev);
+        TW_STAMP_ADD(eng.st[6], t_po, t_prev);
     }
-#ifdef TW_ABLATE
-    eng.st[3] = __builtin_readcyclecounter() - t_kernel0;      // (slot 3 reused: whole wave lifetime)
-    if (eng.lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_stamps16[i], eng.st[i]);
-#endif
+    TW_STAMP(t_kernel1);
+    TW_STAMP_FLUSH(eng.lane == 0, g_stamps16, eng.st[0], eng.st[1], eng.st[2], t_kernel1 - t_kernel0,   // (slot 3: whole wave lifetime)
+                   eng.st[4], eng.st[5], eng.st[6], eng.st[7]);
     if constexpr (!PERSIST) { if (v_own) a.out.ep_len[e_own] = len_own; }
     eng.end();
 }
@@ -181,22 +165,14 @@ static int launch16p(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint
     if (nb == 0 || nb > 0x7fffffffull) { set_error("rollout16: bad episode count %llu", (unsigned long long)a.num_episodes); return TW_ERR_INVALID; }
     if (lds_bytes > 159 * 1024) { set_error("rollout16: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&rollout_f16_kernel<Eng, NC, PERSIST>), lds_bytes)) return rc;
-#ifdef TW_ABLATE
-    static const unsigned long long zeros[8] = {};
-    if (getenv("TW_STAMPS")) TW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps16), zeros, sizeof(zeros)));
-#endif
+    TW_STAMPS_CLEAR(g_stamps16);
     hipLaunchKernelGGL((rollout_f16_kernel<Eng, NC, PERSIST>), dim3((unsigned)nb), dim3(Eng::THREADS), lds_bytes, s, a);
     TW_HIP(hipGetLastError());
-#ifdef TW_ABLATE
-    if (getenv("TW_STAMPS")) {
-        unsigned long long h[8];
-        TW_HIP(hipStreamSynchronize(s));
-        TW_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamps16), sizeof(h)));
+    TW_STAMPS_REPORT(g_stamps16, s, h, {
         const double nw = (double)nb * 4.0;
         fprintf(stderr, "[stamps16] per wave (cycles x100MHz ticks): pre %.0f prologue %.0f stage-body %.0f vmcnt %.0f stage-barrier %.0f heads %.0f post %.0f step-barrier %.0f\n",
                 h[0] / nw, h[1] / nw, h[2] / nw, h[3] / nw, h[4] / nw, h[5] / nw, h[6] / nw, h[7] / nw);
-    }
-#endif
+    });
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = Eng::THREADS;
     return TW_OK;

@@ -11,9 +11,9 @@
 namespace tw {
 
 template <int NT, int NC, int NW>
-__global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 2 : 1)) solve_f32_kernel(const SolveArgs a)
+__global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), (NW == 8 ? 2 : 1)) solve_f32_kernel(const SolveArgs a)
 {
-    using Eng = typename Geom<NT, NC, 0, NW>::Eng;
+    using Eng = typename Geom<NT, NC, NW>::Eng;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.begin1(a.pol, lds);
@@ -82,7 +82,7 @@ __global__ void __launch_bounds__((Geom<NT, NC, 0, NW>::WAVES * 64), (NW == 8 ? 
 template <int NT, int NC, int NW>
 static int launch_solve_geom(const SolveArgs &a, hipStream_t s)
 {
-    using G = Geom<NT, NC, 0, NW>;
+    using G = Geom<NT, NC, NW>;
     constexpr int EPB = G::Eng::EPB;
     const uint64_t nb = (a.num_attempts + EPB - 1) / EPB;
     if (nb == 0 || nb > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)a.num_attempts); return TW_ERR_INVALID; }
