@@ -1,0 +1,116 @@
+// twisterl_device_env.hpp -- write your own environment and collect it on the device.
+//
+// The reference's extension story is `trait Env` (rust/src/rl/env.rs:18-68, its README's "Creating your own environment",
+// examples/grid_world).  Here an environment is a C++ struct whose methods are all __host__ __device__: the SAME code runs inside
+// the fused PPO rollout / evaluate kernels (twisterl_amd/csrc/tw_rollout_env.hpp, one GPU lane group per episode) and behind a host
+// tw_env_vtable (the host-stepped collectors, and the reference oracle in the tests).  A module is built with
+//
+//     twisterl_amd.build.build_device_env("my_env.hpp", "MyEnv", "my_env")      # -> libtw_env_my_env.so
+//
+// which compiles `#include "my_env.hpp"` + `TW_DEVICE_ENV(MyEnv, my_env)` with the library's own flags, and loaded with
+// twisterl_amd.env.DeviceEnv(path, "my_env", params=[...]).  The contract (checked by static_assert below):
+//
+//   struct MyEnv {                                      // trivially copyable, default-constructible, at most 1 KiB: the prototype AND
+//                                                       // the per-episode state
+//       static constexpr int NUM_ACTIONS = 4;           // 1..4 (EngineV's head has four action columns)
+//       static constexpr int N_OBS       = 25;          // observe() writes EXACTLY this many ids, 1..64
+//       __host__ __device__ int      obs_size() const;  // every id < obs_size() <= 65535 (the policy's obs_size)
+//       __host__ __device__ int      difficulty() const;
+//       __host__            void     set_difficulty(int d);
+//       __host__ __device__ void     reset(uint64_t seed, uint64_t episode);   // Env::reset; episode = the GLOBAL episode index
+//       __host__ __device__ void     step(int action);
+//       __host__ __device__ void     observe(int *ids) const;                  // N_OBS ids
+//       __host__ __device__ uint32_t masks() const;                            // bit i = action i allowed
+//       __host__ __device__ float    reward() const;
+//       __host__ __device__ bool     is_final() const;
+//       __host__ __device__ bool     success() const;
+//       __host__            bool     init(const double *params, int n);        // the prototype from constructor parameters
+//   };
+//
+// Randomness: tw::env_draw(seed, episode, index) -> four 32-bit words (Philox4x32-10 on stream 6).  The environment
+// chooses its own `index` values, e.g. the draw number in reset() and (t << 8) | k in step(); tw::u32_below(word, n) gives an
+// integer in [0, n), tw::u32_to_unit(word) a float in [0, 1).  Everything a method reads must be in the struct: no pointers to host
+// memory, no globals, no virtual functions.  An id outside [0, obs_size()) fails the collect ("index out of bounds: obs id ..."), an
+// episode that has not ended within the collect's max_records_per_episode records fails it too -- as on the host-stepped path.  A
+// collect whose max_records_per_episode is above 1,820 (what the finalize step's LDS tile holds) runs on the host-stepped path.
+#pragma once
+
+#include "twisterl_hip.h"
+#include "tw_rollout_env.hpp"
+
+#include <new>
+#include <type_traits>
+
+namespace tw {
+
+template <class T>
+struct DeviceEnvModule {
+    static_assert(std::is_trivially_copyable<T>::value, "twisterl device environment: the struct must be trivially copyable (the kernels clone it by value)");
+    static_assert(std::is_default_constructible<T>::value, "twisterl device environment: the struct must be default-constructible (init() fills a default-constructed one)");
+    static_assert(sizeof(T) <= 1024, "twisterl device environment: the struct must be at most 1 KiB (it lives in registers on the device)");
+    static_assert(T::NUM_ACTIONS >= 1 && T::NUM_ACTIONS <= 4, "twisterl device environment: NUM_ACTIONS must be 1..4 (EngineV's head has four action columns)");
+    static_assert(T::N_OBS >= 1 && T::N_OBS <= 64, "twisterl device environment: N_OBS must be 1..64");
+    static constexpr int A = T::NUM_ACTIONS, NO = T::N_OBS;
+
+    // tw_env_vtable over T (the host-stepped collectors and solve run the same code on the CPU)
+    static void *clone(void *e) { return new (std::nothrow) T(*static_cast<const T *>(e)); }
+    static void destroy(void *e) { delete static_cast<T *>(e); }
+    static void reset(void *e, uint64_t seed, uint64_t episode) { static_cast<T *>(e)->reset(seed, episode); }
+    static void step(void *e, uint32_t action) { static_cast<T *>(e)->step((int)action); }
+    static void observe(void *e, int32_t *out)
+    {
+        int ids[NO];
+        static_cast<const T *>(e)->observe(ids);
+        for (int i = 0; i < NO; ++i) out[i] = (int32_t)ids[i];
+    }
+    static void masks(void *e, uint8_t *out)
+    {
+        const uint32_t b = static_cast<const T *>(e)->masks();
+        for (int i = 0; i < A; ++i) out[i] = (uint8_t)((b >> i) & 1u);
+    }
+    static float reward(void *e) { return static_cast<const T *>(e)->reward(); }
+    static int is_final(void *e) { return static_cast<const T *>(e)->is_final() ? 1 : 0; }
+    static int success(void *e) { return static_cast<const T *>(e)->success() ? 1 : 0; }
+
+    static void *create(const double *params, int n)
+    {
+        T *t = new (std::nothrow) T();
+        if (t && !t->init(params, n)) { delete t; t = nullptr; }
+        return t;
+    }
+    static int get_difficulty(const void *e) { return static_cast<const T *>(e)->difficulty(); }
+    static void set_difficulty(void *e, int d) { static_cast<T *>(e)->set_difficulty(d); }
+    static int obs_size(const void *e) { return static_cast<const T *>(e)->obs_size(); }
+    static void fill_vtable(tw_env_vtable *v)
+    {
+        *v = tw_env_vtable{};
+        v->num_actions = (uint32_t)A; v->n_obs = (uint32_t)NO;
+        v->clone = clone; v->destroy = destroy; v->reset = reset; v->step = step; v->observe = observe; v->masks = masks;
+        v->reward = reward; v->is_final = is_final; v->success = success;
+    }
+
+    static const tw_device_env *descriptor(const char *type_name)
+    {
+        static const tw_device_env d = [type_name]() {
+            tw_device_env x{};
+            tw_device_env_layout(x.layout);
+            x.num_actions = (uint32_t)A; x.n_obs = (uint32_t)NO; x.state_bytes = (uint32_t)sizeof(T); x.engine_nc = (uint32_t)env_engine_nc(NO);
+            x.type_name = type_name;
+            x.launch_rollout = launch_rollout_env<T>; x.launch_solve = launch_solve_env<T>;
+            x.create = create; x.get_difficulty = get_difficulty; x.set_difficulty = set_difficulty; x.obs_size = obs_size;
+            x.fill_vtable = fill_vtable;
+            return x;
+        }();
+        return &d;
+    }
+};
+
+}  // namespace tw
+
+// Instantiates the rollout and evaluate kernels, their launchers and the host adapter of `Type`, and exports
+// `extern "C" const tw_device_env *tw_device_env_<name>(void)`.  Once per module.
+#define TW_DEVICE_ENV(Type, name)                                                                           \
+    extern "C" __attribute__((visibility("default"))) const tw_device_env *tw_device_env_##name(void)      \
+    {                                                                                                       \
+        return ::tw::DeviceEnvModule<Type>::descriptor(#Type);                                              \
+    }

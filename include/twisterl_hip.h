@@ -309,6 +309,21 @@ int tw_solve_env(const tw_env_vtable *env, const tw_policy *policy, const tw_sol
 int tw_solve_env32(const tw_env_vtable *env, const tw_policy *policy, const tw_solve_params *params, uint32_t max_steps,
                    float *success, float *reward, uint32_t *solution_out, uint32_t solution_cap, uint32_t *n_solution);
 
+/* ---- a user-written environment ON THE DEVICE: a C++ struct (include/twisterl_device_env.hpp) compiled into a module
+ * (twisterl_amd.build.build_device_env) that exports `const tw_device_env *tw_device_env_<name>(void)`.  `proto` points to the
+ * environment struct (proto_bytes = its size), the prototype every episode clones and resets.  The library refuses a descriptor
+ * built against another layout.  tw_ppo_collect_device_env / tw_evaluate_device_env run the whole loop in one kernel (the policy on
+ * EngineV, f32); what that kernel does not take -- a policy of the MFMA shape, another precision, evaluate with MCTS -- runs on the
+ * host-stepped path over the module's own vtable (tw_ppo_collect_env / tw_evaluate_env: same bytes, same errors). */
+typedef struct tw_device_env tw_device_env;
+/* fills `out` with the module's host methods over `proto` (borrowed: it must outlive every use of `out`); no device needed */
+int tw_device_env_host_vtable(const tw_device_env *env, const void *proto, size_t proto_bytes, tw_env_vtable *out);
+int tw_ppo_collect_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                              const tw_ppo_params *params, uint32_t max_records_per_episode, tw_collected **out);
+int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                           const tw_solve_params *params, uint64_t num_episodes, uint64_t episode_offset, uint32_t max_steps,
+                           float *success_rate, float *mean_reward);
+
 /* Fields of the result (device-resident, compact, in the order params.merge_order asked for) */
 enum {
     TW_F_OBS       = 0,  /* uint8  [n][n_cells]    obs ids (< 256)                             */

@@ -133,6 +133,76 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
+DEVICE_ENV_DIR = os.path.join(LIB_DIR, "device_envs")     # (git-ignored with the rest of lib/)
+
+
+def _scan_asm(paths, who: str) -> int:
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    try:
+        import scan_mfma_hazards as scan
+    finally:
+        sys.path.pop(0)
+    report, mfmas = [], 0
+    for f in paths:
+        hits, counts = scan.scan_file(f)
+        mfmas += sum(counts.values())
+        report += [f"{os.path.basename(f)}: {h}" for h in hits]
+    if report:
+        raise RuntimeError(f"MFMA hazards in {who} (scripts/scan_mfma_hazards.py):\n" + "\n".join(report[:40]))
+    return mfmas
+
+
+def build_device_env(header: str, type_name: str, name: str, out_dir: str = None, force: bool = False) -> str:
+    """Compiles a user-written device environment (include/twisterl_device_env.hpp) into a loadable module:
+    `#include "<header>"` + `TW_DEVICE_ENV(<type_name>, <name>)` with the library's own FLAGS (-ffp-contract=off: bit parity with the
+    host path), the device assembly kept beside the module (<out_dir>/libtw_env_<name>.s) and scanned for MFMA hazards like the
+    library's -- a hazard is a build error.  Returns the path of libtw_env_<name>.so (exports tw_device_env_<name>); rebuilt when the
+    header or a library header is newer."""
+    if not name.isidentifier() or not all(p.isidentifier() for p in type_name.split("::") if p) or not type_name.strip(":"):
+        raise ValueError(f"build_device_env: name {name!r} / type {type_name!r} must be C identifiers (a template: give it an alias)")
+    header = os.path.abspath(header)
+    if not os.path.exists(header):
+        raise FileNotFoundError(header)
+    out_dir = os.path.abspath(out_dir or DEVICE_ENV_DIR)
+    os.makedirs(out_dir, exist_ok=True)
+    stem = f"libtw_env_{name}"
+    so, asm, src = (os.path.join(out_dir, stem + ext) for ext in (".so", ".s", ".hip"))
+    text = f'// generated by twisterl_amd.build.build_device_env\n#include "{header}"\nTW_DEVICE_ENV({type_name}, {name})\n'
+    deps = [header] + HEADERS + sorted(glob.glob(os.path.join(ROOT, "include", "*.hpp")))
+    if not force and os.path.exists(src) and open(src).read() == text and not _stale(so, deps + [src]) and os.path.exists(asm):
+        return so
+    with open(src, "w") as f:
+        f.write(text)
+    tmp = so + f".{os.getpid()}.tmp"
+    cmd = [hipcc(), *FLAGS, "-shared", "-save-temps=obj", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-I", os.path.dirname(header),
+           src, "-o", tmp]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=out_dir)
+    # -save-temps=obj: the gfx950 assembly goes next to the module, the other intermediates go
+    base = os.path.basename(tmp)
+    for f in os.listdir(out_dir):
+        if not (f.startswith(base + "-") or f.startswith(stem + "-") or f.startswith(stem + ".hip-") or f.startswith(base + ".")) or f == base:
+            continue
+        p = os.path.join(out_dir, f)
+        if f.endswith("-hip-amdgcn-amd-amdhsa-gfx950.s"):
+            os.replace(p, asm)
+        elif os.path.isfile(p) and not f.endswith((".so", ".hip")):
+            os.remove(p)
+    if r.returncode != 0:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise RuntimeError(f"hipcc failed on the device environment {type_name} ({header}):\n{r.stdout}")
+    if not os.path.exists(asm):
+        os.remove(tmp)
+        raise RuntimeError(f"build_device_env: no device assembly for {name}")
+    try:
+        _scan_asm([asm], f"the device environment module {name}")
+    except RuntimeError:
+        os.remove(tmp)
+        raise
+    os.replace(tmp, so)
+    return so
+
+
 def build_c_example() -> str:
     """examples/collect_from_c.c: a compiled host over the C ABI alone (gcc, links the library built above)."""
     src = os.path.join(ROOT, "examples", "collect_from_c.c")

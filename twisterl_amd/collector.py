@@ -14,7 +14,7 @@ import ctypes as _c
 import numpy as np
 
 from . import _lib
-from .env import PyEnv, get_env_desc
+from .env import DeviceEnv, PyEnv, get_env_desc
 from .nn import Policy
 
 ctypes_u8 = _c.c_uint8
@@ -314,6 +314,8 @@ class PPOCollector(PyBaseCollector):
     def collect(self, py_env, policy: Policy, *, seed=None) -> CollectedData:
         if isinstance(py_env, PyEnv):
             return self._collect_foreign(py_env, policy, seed)
+        if isinstance(py_env, DeviceEnv):
+            return self._collect_device_env(py_env, policy, seed)
         desc = self._check(py_env, policy)
         prm = _lib.PPOParams(self.num_episodes, self.episode_offset, self.gamma, self.lambda_,
                              (int(seed) & (2**64 - 1)) if seed is not None else self._next_seed(),
@@ -476,6 +478,33 @@ def _collect_foreign(self, py_env: PyEnv, policy: Policy, seed) -> CollectedData
 PPOCollector._collect_foreign = _collect_foreign
 
 
+def _collect_device_env(self, env: DeviceEnv, policy: Policy, seed) -> CollectedData:
+    """PPOCollector.collect of a device environment: the whole loop on the device (tw_ppo_collect_device_env; the library hands what
+    its kernel does not take to the host-stepped path over the same struct).  AZCollector.collect: self-play steps the struct's host
+    code (tw_az_collect_env over the module's vtable)."""
+    if not isinstance(policy, Policy):
+        raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
+    h = policy._handle()
+    sd = (int(seed) & (2**64 - 1)) if seed is not None else self._next_seed()
+    desc, proto, nbytes = env._args()
+    out = C.c_void_p()
+    L = _lib.lib()
+    if self._IS_PPO:
+        prm = _lib.PPOParams(self.num_episodes, self.episode_offset, self.gamma, self.lambda_, sd, _lib.PRECISIONS[self.precision],
+                             int(self.merge_order), 0)
+        _lib.check(L.tw_ppo_collect_device_env(desc, proto, nbytes, h, C.byref(prm), env.max_records, C.byref(out)))
+    else:
+        vt = _lib.EnvVTable()
+        _lib.check(L.tw_device_env_host_vtable(desc, proto, nbytes, C.byref(vt)))
+        prm = _lib.AZParams(self.num_episodes, self.episode_offset, self.num_mcts_searches, self.C, self.max_expand_depth, sd,
+                            _lib.PRECISIONS[self.precision], int(self.merge_order), 0)
+        _lib.check(L.tw_az_collect_env(C.byref(vt), h, C.byref(prm), env.max_records, C.byref(out)))
+    return CollectedData._from_device(_DeviceResult(out.value))
+
+
+PPOCollector._collect_device_env = _collect_device_env
+
+
 class AZCollector(PyBaseCollector):
     """AZCollector(num_episodes, num_mcts_searches, C, max_expand_depth, num_cores) (collector.rs:172-187)."""
 
@@ -497,10 +526,13 @@ class AZCollector(PyBaseCollector):
 
     _next_seed = PPOCollector._next_seed
     _collect_foreign = _collect_foreign
+    _collect_device_env = _collect_device_env
 
     def collect(self, py_env, policy: Policy, *, seed=None) -> CollectedData:
         if isinstance(py_env, PyEnv):
             return self._collect_foreign(py_env, policy, seed)
+        if isinstance(py_env, DeviceEnv):
+            return self._collect_device_env(py_env, policy, seed)
         desc = self._check(py_env, policy)
         prm = _lib.AZParams(self.num_episodes, self.episode_offset, self.num_mcts_searches, self.C,
                             self.max_expand_depth,
@@ -536,6 +568,15 @@ def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches
         s, r, n = _c.c_float(), _c.c_float(), _c.c_uint32()
         br.finish(_lib.lib().tw_solve_env32(_c.byref(br.vt), policy._handle(), _c.byref(prm), br.max_records, _c.byref(s), _c.byref(r), acts, cap, _c.byref(n)))
         return (float(s.value), float(r.value)), [int(acts[i]) for i in range(n.value)]
+    if isinstance(py_env, DeviceEnv):                                           # the struct's host code (solve.rs:73-101)
+        vt = _lib.EnvVTable()
+        _lib.check(_lib.lib().tw_device_env_host_vtable(*py_env._args(), _c.byref(vt)))
+        cap = py_env.max_records + 1
+        acts = (_c.c_uint32 * cap)()
+        s, r, n = _c.c_float(), _c.c_float(), _c.c_uint32()
+        _lib.check(_lib.lib().tw_solve_env32(_c.byref(vt), policy._handle(), _c.byref(prm), py_env.max_records, _c.byref(s), _c.byref(r), acts, cap,
+                                             _c.byref(n)))
+        return (float(s.value), float(r.value)), [int(acts[i]) for i in range(n.value)]
     get_env_desc(py_env)
     cap = int(py_env.depth) + 2
     acts = (ctypes_u8 * cap)()
@@ -559,6 +600,10 @@ def evaluate(py_env, policy: Policy, num_episodes, deterministic, num_searches, 
         br = _PyEnvBridge(py_env)
         br.finish(_lib.lib().tw_evaluate_env(_c.byref(br.vt), policy._handle(), _c.byref(prm), _u("num_episodes", num_episodes), 0, br.max_records,
                                              _c.byref(s), _c.byref(r)))
+        return float(s.value), float(r.value)
+    if isinstance(py_env, DeviceEnv):                                           # one kernel (tw_evaluate_device_env)
+        _lib.check(_lib.lib().tw_evaluate_device_env(*py_env._args(), policy._handle(), _c.byref(prm), _u("num_episodes", num_episodes), 0,
+                                                     py_env.max_records, _c.byref(s), _c.byref(r)))
         return float(s.value), float(r.value)
     desc = get_env_desc(py_env)
     _lib.check(_lib.lib().tw_evaluate(_c.byref(desc), policy._handle(), _c.byref(prm), _u("num_episodes", num_episodes), 0,

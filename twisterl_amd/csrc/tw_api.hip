@@ -1040,6 +1040,11 @@ int collected_describe(const tw_collected *c, int *is_ppo, uint32_t *n_cells, ui
     return TW_OK;
 }
 const void *collected_field(const tw_collected *c, int field) { return c->field_ptr[field]; }
+// the trajectory workspace and the result-arena pool for the device-environment collectors (tw_device_env.hip)
+std::mutex &workspace_mutex() { return g_ws_mutex; }
+int workspace_reserve(size_t bytes, void **out) { return ws_reserve(bytes, out); }
+int result_arena_acquire(size_t bytes, void **out, size_t *cap) { return arena_acquire(bytes, out, cap); }
+void collected_adopt_stats(tw_collected *c, const tw_collect_stats &st) { c->stats = st; }
 int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uint32_t n_cells, uint32_t n_actions, uint64_t n_records,
                     uint64_t n_episodes, void *const (&field_ptr)[TW_F_COUNT], const size_t (&field_bytes)[TW_F_COUNT], tw_collected **out)
 {

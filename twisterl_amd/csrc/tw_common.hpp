@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <cstdio>
 #include <cstdlib>
+#include <mutex>
 
 #include "twisterl_hip.h"
 
@@ -126,7 +127,8 @@ enum : uint32_t {
     STREAM_PERM     = 2,  // Policy::get_perm_id                 (policy.rs:67-77)
     STREAM_AZ_ACT   = 3,  // AZCollector root action sample      (az.rs:72)
     STREAM_MCTS     = 4,  // MCTSTree::next_sample               (search.rs:94-100)
-    STREAM_SOLVE    = 5   // single_solve action sample          (solve.rs:50-54)
+    STREAM_SOLVE    = 5,  // single_solve action sample          (solve.rs:50-54)
+    STREAM_ENV      = 6   // a device environment's own draws    (env_draw, include/twisterl_device_env.hpp)
 };
 
 struct u32x4 { uint32_t x, y, z, w; };
@@ -151,6 +153,14 @@ __host__ __device__ inline u32x4 rng_draw(uint64_t seed, uint64_t episode, uint3
 {
     return philox4x32_10((uint32_t)episode, (uint32_t)(episode >> 32), index, stream,
                          (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// The draws of a device environment (Env::reset / Env::step of a user's struct, include/twisterl_device_env.hpp): keyed by the
+// collect's seed and the GLOBAL episode index, as the reset of tw_env_vtable is; `index` is the environment's own (e.g. the draw
+// number in reset, (t << 8) | k in step).  Same words on the host and the device.
+__host__ __device__ inline u32x4 env_draw(uint64_t seed, uint64_t episode, uint32_t index)
+{
+    return rng_draw(seed, episode, index, STREAM_ENV);
 }
 
 // integer in [0,n): high half of word*n
@@ -541,6 +551,7 @@ int launch_rollout_f16x2(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, 
 int launch_scan(const uint32_t *ep_len, uint64_t n_episodes, int merge_order, uint64_t *ep_start,
                 uint64_t *total /*device*/, void *scratch, size_t scratch_bytes, hipStream_t s);
 size_t scan_scratch_bytes(uint64_t n_episodes);
+int finalize_ppo_max_t_pad(int n_cells);            // the longest horizon (t_pad) launch_finalize_ppo takes
 int launch_finalize_ppo(const PaddedTraj &in, const uint64_t *ep_start, uint64_t n_episodes, int n_cells,
                         float gamma, float lambda, const CompactTraj &out, hipStream_t s);
 struct SolveArgs {
@@ -669,6 +680,11 @@ const void *collected_field(const tw_collected *c, int field);
 // wraps device memory the caller allocated with hipMalloc into a result object (which frees it through the arena pool)
 int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uint32_t n_cells, uint32_t n_actions, uint64_t n_records,
                     uint64_t n_episodes, void *const (&field_ptr)[TW_F_COUNT], const size_t (&field_bytes)[TW_F_COUNT], tw_collected **out);
+// the cached trajectory workspace (held under workspace_mutex() while in use) and the pooled result arenas (tw_api.hip)
+std::mutex &workspace_mutex();
+int workspace_reserve(size_t bytes, void **out);
+int result_arena_acquire(size_t bytes, void **out, size_t *cap);
+void collected_adopt_stats(tw_collected *c, const tw_collect_stats &st);
 int launch_policy_eval(const PolicyDev &pol, int mode, const int32_t *obs_d, uint32_t n, uint32_t n_obs,
                        const uint8_t *masks_d, const int32_t *perms_d, float *out_actions_d, float *out_values_d,
                        hipStream_t s);

@@ -1,0 +1,318 @@
+// tw_device_env.hip -- PPO collect and evaluate of a user-written environment ON THE DEVICE (include/twisterl_device_env.hpp).
+//
+// A device-environment module (twisterl_amd.build.build_device_env) holds the environment's kernels -- rollout_env_kernel /
+// solve_env_kernel of tw_rollout_env.hpp instantiated over the user's struct -- their launchers and a host adapter.  Everything
+// else is here: the checks, the workspace, the scan / GAE / compaction of the Puzzle path (tw_finalize.hip), the error messages.
+// What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
+// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error),
+// evaluate with MCTS, self-play and solve (the Python layer routes those).  The result is an ordinary tw_collected, byte-equal to
+// tw_ppo_collect_env over the same vtable.
+#include "tw_rollout_env.hpp"
+
+#include <cstring>
+#include <vector>
+
+using namespace tw;
+
+namespace {
+
+// obs ids of the padded trajectories -> the compact one-byte result (environments with at most 256 ids; one wave per episode)
+__global__ void __launch_bounds__(256) compact_env_obs8_kernel(const uint16_t *obs16, const uint32_t *ep_len, const uint64_t *ep_start, uint64_t E,
+                                                               int t_pad, int n_obs, uint8_t *out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint64_t e = (uint64_t)blockIdx.x * 4 + wave; e < E; e += (uint64_t)gridDim.x * 4) {
+        const uint64_t n = (uint64_t)ep_len[e] * (uint64_t)n_obs;
+        const uint16_t *src = obs16 + e * (uint64_t)t_pad * (uint64_t)n_obs;
+        uint8_t *dst = out + ep_start[e] * (uint64_t)n_obs;
+        for (uint64_t i = lane; i < n; i += 64) dst[i] = (uint8_t)src[i];
+    }
+}
+
+// logits of the compact records, four per record -> the environment's A < 4 columns
+__global__ void __launch_bounds__(256) narrow_logits_kernel(const float *lg4, uint64_t n, int A, float *out)
+{
+    const uint64_t total = n * (uint64_t)A;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = i / (uint64_t)A, c = i - r * (uint64_t)A;
+        out[i] = lg4[r * 4 + c];
+    }
+}
+
+unsigned grid_for(uint64_t items, uint64_t per_block)
+{
+    uint64_t b = (items + per_block - 1) / per_block;
+    if (b > 256ull * 16) b = 256ull * 16;
+    return (unsigned)(b ? b : 1);
+}
+
+int check_descriptor(const tw_device_env *d, const void *proto, size_t proto_bytes, const char *who)
+{
+    if (!d || !proto) { set_error("%s: null argument", who); return TW_ERR_INVALID; }
+    uint32_t mine[TW_DEVICE_ENV_LAYOUT_WORDS];
+    tw_device_env_layout(mine);
+    if (memcmp(d->layout, mine, sizeof(mine)) != 0) {
+        set_error("%s: the device environment module was built against another library layout (module: tag %08x ABI %u, %u/%u/%u/%u/%u/%u bytes; "
+                  "this library: tag %08x ABI %u, %u/%u/%u/%u/%u/%u bytes) -- rebuild it with twisterl_amd.build.build_device_env", who,
+                  d->layout[0], d->layout[1], d->layout[2], d->layout[3], d->layout[4], d->layout[5], d->layout[6], d->layout[7],
+                  mine[0], mine[1], mine[2], mine[3], mine[4], mine[5], mine[6], mine[7]);
+        return TW_ERR_INVALID;
+    }
+    if (!d->launch_rollout || !d->launch_solve || !d->create || !d->get_difficulty || !d->set_difficulty || !d->obs_size || !d->fill_vtable) {
+        set_error("%s: the device environment descriptor lacks a function", who); return TW_ERR_INVALID;
+    }
+    if (d->num_actions < 1 || d->num_actions > 4 || d->n_obs < 1 || d->n_obs > 64 || d->engine_nc != (uint32_t)env_engine_nc((int)d->n_obs)) {
+        set_error("%s: descriptor with %u actions, %u obs ids, %u engine columns", who, d->num_actions, d->n_obs, d->engine_nc); return TW_ERR_INVALID;
+    }
+    if (proto_bytes != d->state_bytes) {
+        set_error("%s: the prototype has %zu bytes, the module's environment %u", who, proto_bytes, d->state_bytes); return TW_ERR_INVALID;
+    }
+    const int os = d->obs_size(proto);
+    if (os < 1 || os > 65535) { set_error("%s: obs_size() is %d (1..65535)", who, os); return TW_ERR_INVALID; }
+    return TW_OK;
+}
+
+tw_env_vtable host_table(const tw_device_env *d, const void *proto)
+{
+    tw_env_vtable vt{};
+    d->fill_vtable(&vt);
+    vt.prototype = const_cast<void *>(proto);          // the collectors clone it and never write to it
+    vt.obs_size = (uint32_t)d->obs_size(proto);
+    return vt;
+}
+
+size_t engine_lds_bytes(uint32_t nc, const PolicyDev &p)
+{
+    switch (nc) {
+        case 4:  return EngineV<4>::lds_floats(p) * sizeof(float);
+        case 9:  return EngineV<9>::lds_floats(p) * sizeof(float);
+        case 16: return EngineV<16>::lds_floats(p) * sizeof(float);
+        case 25: return EngineV<25>::lds_floats(p) * sizeof(float);
+        case 36: return EngineV<36>::lds_floats(p) * sizeof(float);
+        default: return EngineV<64>::lds_floats(p) * sizeof(float);
+    }
+}
+
+// the checks of the host path (tw_env_generic.hip), with its messages
+int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
+{
+    if ((int)vt.num_actions != pd->n_actions) { set_error("environment has %u actions, policy has %d (at most 31)", vt.num_actions, pd->n_actions); return TW_ERR_INVALID; }
+    if ((int)vt.obs_size != pd->obs_size) { set_error("index out of bounds: policy obs_size %d != environment obs ids %u", pd->obs_size, vt.obs_size); return TW_ERR_INVALID; }
+    return TW_OK;
+}
+
+}  // namespace
+
+extern "C" int tw_device_env_host_vtable(const tw_device_env *env, const void *proto, size_t proto_bytes, tw_env_vtable *out)
+{
+    if (!out) { set_error("tw_device_env_host_vtable: null argument"); return TW_ERR_INVALID; }
+    int rc = check_descriptor(env, proto, proto_bytes, "tw_device_env_host_vtable"); if (rc) return rc;
+    *out = host_table(env, proto);
+    return TW_OK;
+}
+
+extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                                         const tw_ppo_params *prm, uint32_t max_records_per_episode, tw_collected **out)
+{
+    if (!policy || !prm || !out) { set_error("tw_ppo_collect_device_env: null argument"); return TW_ERR_INVALID; }
+    *out = nullptr;
+    int rc = check_descriptor(env, proto, proto_bytes, "tw_ppo_collect_device_env"); if (rc) return rc;
+    const tw_env_vtable vt = host_table(env, proto);
+    const PolicyDev *pd = policy_dev(policy);
+    // what the kernel does not take: the host-stepped path over the module's own vtable (same bytes; its messages).  Episodes
+    // longer than the finalize step's LDS tile holds (finalize_ppo_max_t_pad: 1,820 records) go there too.
+    if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > (uint32_t)finalize_ppo_max_t_pad(0))
+        return tw_ppo_collect_env(&vt, policy, prm, max_records_per_episode, out);
+    if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
+    rc = check_env_policy(vt, pd); if (rc) return rc;
+    if (max_records_per_episode == 0) { set_error("tw_ppo_collect_env: max_records_per_episode must be positive"); return TW_ERR_INVALID; }
+    if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_ppo_collect_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }
+    rc = require_device(); if (rc) return rc;
+
+    const uint64_t E = prm->num_episodes;
+    const uint32_t A = env->num_actions, NO = env->n_obs, OW = pd->obs_size > 256 ? 2u : 1u;
+    const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
+    const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;
+    if (blocks > 0x7fffffffull || t_pad > 0x7fffffffull) { set_error("tw_ppo_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
+    const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
+    if (lds_bytes > 159 * 1024) { set_error("rollout: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
+
+    std::lock_guard<std::mutex> lock(workspace_mutex());
+    hipStream_t s = current_stream();
+    size_t cur = 0;
+    auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
+    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(16), o_scan = seg(scan_scratch_bytes(E)),
+                 o_obs16 = seg(R * NO * 2);
+    void *wsp = nullptr;
+    rc = workspace_reserve(cur, &wsp); if (rc) return rc;
+    uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
+    EnvRolloutArgs ra{};
+    ra.pol = *pd;
+    ra.out.rec = reinterpret_cast<PaddedRec *>(ws + o_rec); ra.out.ep_len = reinterpret_cast<uint32_t *>(ws + o_len); ra.out.t_pad = (int32_t)t_pad;
+    ra.obs16 = reinterpret_cast<uint16_t *>(ws + o_obs16);
+    ra.err = reinterpret_cast<uint32_t *>(ws + o_total + 8);
+    ra.num_episodes = E; ra.episode_offset = prm->episode_offset; ra.seed = prm->seed;
+    uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
+
+    struct Events { hipEvent_t ev[5] = {}; ~Events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); } } ev;
+    for (auto &e : ev.ev) TW_HIP(hipEventCreate(&e));
+    TW_HIP(hipMemsetAsync(ws + o_total, 0, 16, s));
+    TW_HIP(hipEventRecord(ev.ev[0], s));
+    const int lr = env->launch_rollout(&ra, proto, (unsigned)blocks, lds_bytes, s);
+    if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment rollout launch", __FILE__, __LINE__);
+    TW_HIP(hipEventRecord(ev.ev[1], s));
+    rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
+    if (rc) return rc;
+    TW_HIP(hipEventRecord(ev.ev[2], s));
+    uint64_t hv[2] = {0, 0};
+    TW_HIP(hipMemcpyAsync(hv, ws + o_total, 16, hipMemcpyDeviceToHost, s));
+    TW_HIP(hipStreamSynchronize(s));
+    const uint64_t total = hv[0];
+    const uint32_t err = (uint32_t)hv[1];
+    if (err & 1u) {
+        // the id the host path reports: the first it meets -- the smallest record index, then the smallest episode (the kernel
+        // flagged each such episode in ep_len and left the id in that record's value field)
+        std::vector<uint32_t> len(E);
+        TW_HIP(hipMemcpy(len.data(), ra.out.ep_len, E * 4, hipMemcpyDeviceToHost));
+        uint64_t first = E;
+        for (uint64_t e = 0; e < E; ++e)
+            if ((len[e] & 0x80000000u) && (first == E || (len[e] & 0x7fffffffu) < (len[first] & 0x7fffffffu))) first = e;
+        int32_t id = 0;
+        if (first < E) {
+            PaddedRec r;
+            TW_HIP(hipMemcpy(&r, ra.out.rec + first * t_pad + ((len[first] & 0x7fffffffu) - 1u), sizeof(r), hipMemcpyDeviceToHost));
+            id = __builtin_bit_cast(int32_t, r.value);
+        }
+        set_error("index out of bounds: obs id %d, obs_size %d", (int)id, pd->obs_size);
+        return TW_ERR_INVALID;
+    }
+    if (err & 2u) { set_error("tw_ppo_collect_env: an episode did not end within %u records", max_records_per_episode); return TW_ERR_INVALID; }
+    if (total == 0 || total > R) { set_error("collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
+
+    // ---- compact result: the fields of tw_ppo_collect_env, then (A < 4) the four-column logits the finalize kernel writes ------------
+    size_t ccur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
+    auto put = [&](int f, size_t b) { bytes[f] = b; off[f] = ccur; ccur = (ccur + b + 255) / 256 * 256; };
+    put(TW_F_OBS, total * NO * OW); put(TW_F_LOGITS, total * A * 4); put(TW_F_PERMS, total); put(TW_F_VALUES, total * 4); put(TW_F_REWARDS, total * 4);
+    put(TW_F_ACTIONS, total); put(TW_F_ADVS, total * 4); put(TW_F_RETS, total * 4); put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
+    const size_t o_lg4 = ccur;
+    if (A < 4) ccur += total * 16;
+    void *arena = nullptr; size_t cap = 0;
+    rc = result_arena_acquire(ccur, &arena, &cap); if (rc) return rc;
+    uint8_t *ca = reinterpret_cast<uint8_t *>(arena);
+    void *fp[TW_F_COUNT] = {};
+    for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) fp[f] = ca + off[f];
+    int dev_id = 0; (void)hipGetDevice(&dev_id);
+    tw_collected *c = nullptr;
+    rc = collected_adopt(arena, cap, dev_id, 1, NO, A, total, E, fp, bytes, &c);
+    if (rc) { (void)hipFree(arena); return rc; }
+    collected_adopt_obs_width(c, OW);
+#define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
+    CompactTraj ct{};
+    ct.obs = nullptr;                                                          // (0 cells: the ids have their own array)
+    ct.logits = reinterpret_cast<float *>(A < 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]); ct.perms = reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]);
+    ct.values = reinterpret_cast<float *>(ca + off[TW_F_VALUES]); ct.rewards = reinterpret_cast<float *>(ca + off[TW_F_REWARDS]);
+    ct.actions = ca + off[TW_F_ACTIONS]; ct.advs = reinterpret_cast<float *>(ca + off[TW_F_ADVS]); ct.rets = reinterpret_cast<float *>(ca + off[TW_F_RETS]);
+    TW_HIP_C(hipEventRecord(ev.ev[3], s));
+    rc = launch_finalize_ppo(ra.out, ep_start_ws, E, 0, prm->gamma, prm->lambda, ct, s);
+    if (rc == TW_OK && OW == 2)
+        rc = launch_compact_obs16(ra.obs16, ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s);
+    if (rc) { tw_collected_free(c); return rc; }
+    if (OW == 1) {
+        hipLaunchKernelGGL(compact_env_obs8_kernel, dim3(grid_for(E, 4)), dim3(256), 0, s, ra.obs16, ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO,
+                           ca + off[TW_F_OBS]);
+        TW_HIP_C(hipGetLastError());
+    }
+    if (A < 4) {
+        hipLaunchKernelGGL(narrow_logits_kernel, dim3(grid_for(total * A, 256)), dim3(256), 0, s, reinterpret_cast<const float *>(ca + o_lg4), total,
+                           (int)A, reinterpret_cast<float *>(ca + off[TW_F_LOGITS]));
+        TW_HIP_C(hipGetLastError());
+    }
+    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_LEN], ra.out.ep_len, E * 4, hipMemcpyDeviceToDevice, s));
+    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_START], ep_start_ws, E * 8, hipMemcpyDeviceToDevice, s));
+    TW_HIP_C(hipEventRecord(ev.ev[4], s));
+    TW_HIP_C(hipStreamSynchronize(s));
+    tw_collect_stats st{};
+    float ms = 0;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1])); st.ms_rollout = ms;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[1], ev.ev[2])); st.ms_scan = ms;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[3], ev.ev[4])); st.ms_finalize = ms;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[4])); st.ms_total = ms;
+#undef TW_HIP_C
+    st.records = total; st.episodes = E; st.padded_bytes = cur; st.forward_evals = total;
+    st.rollout_blocks = (uint32_t)blocks; st.rollout_threads = 256;
+    collected_adopt_stats(c, st);
+    *out = c;
+    return TW_OK;
+}
+
+extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                                      const tw_solve_params *prm, uint64_t num_episodes, uint64_t episode_offset, uint32_t max_steps,
+                                      float *success_rate, float *mean_reward)
+{
+    if (!policy || !prm || !success_rate || !mean_reward) { set_error("tw_evaluate_device_env: null argument"); return TW_ERR_INVALID; }
+    int rc = check_descriptor(env, proto, proto_bytes, "tw_evaluate_device_env"); if (rc) return rc;
+    const tw_env_vtable vt = host_table(env, proto);
+    const PolicyDev *pd = policy_dev(policy);
+    if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_mcts_searches != 0 || prm->num_searches == 0 || num_episodes == 0 ||
+        max_steps > 0x7fffffffu)
+        return tw_evaluate_env(&vt, policy, prm, num_episodes, episode_offset, max_steps, success_rate, mean_reward);
+    rc = check_env_policy(vt, pd); if (rc) return rc;
+    if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_evaluate_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }
+    rc = require_device(); if (rc) return rc;
+    const uint64_t N = prm->num_searches, NA = num_episodes * N;
+    const uint64_t blocks = (NA + GEN_COLS - 1) / GEN_COLS;
+    if (NA / N != num_episodes || blocks > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
+    const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
+    if (lds_bytes > 159 * 1024) { set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
+
+    std::vector<float> succ(NA), tot(NA);
+    std::vector<uint32_t> steps(NA);
+    uint64_t hv[2] = {0, 0};
+    {
+        std::lock_guard<std::mutex> lock(workspace_mutex());
+        hipStream_t s = current_stream();
+        size_t cur = 0;
+        auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
+        const size_t o_s = seg(NA * 4), o_t = seg(NA * 4), o_n = seg(NA * 4), o_err = seg(16);
+        void *wsp = nullptr;
+        rc = workspace_reserve(cur, &wsp); if (rc) return rc;
+        uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
+        EnvSolveArgs sa{};
+        sa.pol = *pd; sa.num_attempts = NA; sa.episode_offset = episode_offset; sa.seed = prm->seed;
+        sa.num_searches = (uint32_t)N; sa.deterministic = prm->deterministic ? 1u : 0u; sa.max_steps = max_steps ? max_steps : 1u;
+        sa.success = reinterpret_cast<float *>(ws + o_s); sa.total = reinterpret_cast<float *>(ws + o_t);
+        sa.n_steps = reinterpret_cast<uint32_t *>(ws + o_n); sa.err = reinterpret_cast<uint32_t *>(ws + o_err);
+        TW_HIP(hipMemsetAsync(ws + o_err, 0, 16, s));
+        const int lr = env->launch_solve(&sa, proto, (unsigned)blocks, lds_bytes, s);
+        if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment evaluate launch", __FILE__, __LINE__);
+        TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
+        TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
+        TW_HIP(hipMemcpyAsync(steps.data(), ws + o_n, NA * 4, hipMemcpyDeviceToHost, s));
+        TW_HIP(hipMemcpyAsync(hv, ws + o_err, 8, hipMemcpyDeviceToHost, s));
+        TW_HIP(hipStreamSynchronize(s));
+    }
+    const uint32_t err = (uint32_t)hv[0];
+    if (err & 1u) {       // the first bad id the host path meets: the smallest move, then the smallest attempt (its total holds the id)
+        uint64_t first = NA;
+        for (uint64_t i = 0; i < NA; ++i)
+            if ((steps[i] & 0x80000000u) && (first == NA || (steps[i] & 0x7fffffffu) < (steps[first] & 0x7fffffffu))) first = i;
+        const int32_t id = first < NA ? __builtin_bit_cast(int32_t, tot[first]) : 0;
+        set_error("index out of bounds: obs id %d, obs_size %d", (int)id, pd->obs_size);
+        return TW_ERR_INVALID;
+    }
+    if (err & 4u) { set_error("solve: an attempt did not end within %u steps", max_steps ? max_steps : 1u); return TW_ERR_INVALID; }
+    // best of N per episode (solve.rs:84-98: `if next_val.0 > best.0` on (success, total) tuples), then the means in episode order
+    // (evaluate.rs:36-52) -- tw_evaluate_env's reduction
+    float successes = 0.0f, rewards = 0.0f;
+    for (uint64_t ep = 0; ep < num_episodes; ++ep) {
+        float bs = 0.0f, br = -__builtin_inff();
+        for (uint64_t k = 0; k < N; ++k) {
+            const float sc = succ[ep * N + k], tr = tot[ep * N + k];
+            if (sc > bs || (sc == bs && tr > br)) { bs = sc; br = tr; }
+        }
+        successes = successes + bs; rewards = rewards + br;
+    }
+    *success_rate = successes / (float)num_episodes;
+    *mean_reward = rewards / (float)num_episodes;
+    return TW_OK;
+}

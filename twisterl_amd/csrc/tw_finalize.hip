@@ -311,6 +311,14 @@ static int launch_fin_group(const PaddedTraj &in, const uint64_t *ep_start, uint
     return TW_OK;
 }
 
+// the longest horizon launch_finalize_ppo takes: its one-wave form must fit the episode's tile in 64 KiB of LDS
+int finalize_ppo_max_t_pad(int n_cells)
+{
+    int t = 1;
+    while (fin_wave_bytes(t + 1, n_cells) <= 64 * 1024) ++t;
+    return t;
+}
+
 int launch_finalize_ppo(const PaddedTraj &in, const uint64_t *ep_start, uint64_t E, int n_cells, float gamma,
                         float lambda, const CompactTraj &out, hipStream_t s)
 {

@@ -1,0 +1,293 @@
+// tw_rollout_env.hpp -- the fused PPO rollout and evaluate loop of tw_rollout_big.hip as templates over a user-written device
+// environment (include/twisterl_device_env.hpp), and the argument structs a device-environment module shares with the library.
+//
+// A module (twisterl_amd.build.build_device_env) instantiates rollout_env_kernel<Env, NC> / solve_env_kernel<Env, NC> and their
+// launchers through TW_DEVICE_ENV; the library (tw_device_env.hip) owns everything around them: the checks, the workspace, the scan,
+// GAE and compaction, the error messages, the hand-off to the host-stepped path for what the kernels do not take.  Per record, in the
+// order of PPOCollector::single_collect (collector/ppo.rs:69-80): observe -> twist of the ids -> EngineV::forward -> act_perm -> mask
+// -> reward -> Gumbel arg-max over the environment's actions; store the record and the ids, then is_final / step.  Same RNG keys and
+// the same arithmetic as tw_ppo_collect_env / tw_evaluate_env over the environment's host vtable: bit-equal to them.
+#pragma once
+#include "tw_engine_generic.hpp"
+
+#include <type_traits>
+
+namespace tw {
+
+// What one launch of the rollout kernel needs besides the prototype (which travels by value as the kernel's second argument).
+struct EnvRolloutArgs {
+    PolicyDev  pol;
+    PaddedTraj out;                  // records [E][t_pad]: obs bytes zero (the ids have their own array), logits, value, reward, action | twist
+    uint16_t  *obs16;                // [E][t_pad][n_obs] obs ids as the environment wrote them (before the twist)
+    uint32_t  *err;                  // |= 1: an obs id outside [0, obs_size); |= 2: an episode did not end within t_pad records;
+                                     // zeroed by the library before the launch.  An episode that met a bad id at record t ends
+                                     // there: its ep_len is (t + 1) | 1 << 31 and record t's value field holds the id (bits)
+    uint64_t   num_episodes, episode_offset, seed;
+};
+
+// evaluate(): one column = one attempt (episode, search), as solve_big_kernel
+struct EnvSolveArgs {
+    PolicyDev pol;
+    uint64_t  num_attempts, episode_offset, seed;
+    uint32_t  num_searches, deterministic, max_steps, pad;
+    float    *success, *total;       // [num_attempts]
+    uint32_t *n_steps;               // [num_attempts]; an attempt that met a bad id at move t: t | 1 << 31, its total = the id (bits)
+    uint32_t *err;                   // as EnvRolloutArgs::err (bit 2: an attempt did not end within max_steps steps)
+};
+
+// EngineV column count for an environment of n_obs ids: the smallest instantiation the Puzzle kernels already use
+constexpr int env_engine_nc(int n_obs) { return n_obs <= 4 ? 4 : n_obs <= 9 ? 9 : n_obs <= 16 ? 16 : n_obs <= 25 ? 25 : n_obs <= 36 ? 36 : 64; }
+
+}  // namespace tw
+
+// The descriptor a module exports (tw_device_env_<name>()).  `layout` = what the module was compiled against; the library refuses a
+// descriptor whose layout differs from its own (tw_device_env_layout()).
+enum { TW_DEVICE_ENV_MAGIC = 0x45445754u, TW_DEVICE_ENV_LAYOUT_WORDS = 8 };    // "TWDE"
+struct tw_device_env {
+    uint32_t layout[TW_DEVICE_ENV_LAYOUT_WORDS];
+    uint32_t num_actions, n_obs, state_bytes, engine_nc;
+    const char *type_name;
+    // launchers: hipFuncSetAttribute (dynamic LDS) + the launch; a hipError_t
+    int (*launch_rollout)(const tw::EnvRolloutArgs *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s);
+    int (*launch_solve)(const tw::EnvSolveArgs *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s);
+    // host side of the same struct: a new object from constructor parameters (null if init() refuses them), the accessors the
+    // Python surface needs, and the tw_env_vtable methods over the type (prototype, obs_size left to the caller)
+    void *(*create)(const double *params, int n);
+    int   (*get_difficulty)(const void *env);
+    void  (*set_difficulty)(void *env, int d);
+    int   (*obs_size)(const void *env);
+    void  (*fill_vtable)(tw_env_vtable *out);
+};
+
+inline void tw_device_env_layout(uint32_t (&out)[TW_DEVICE_ENV_LAYOUT_WORDS])
+{
+    out[0] = TW_DEVICE_ENV_MAGIC; out[1] = TW_ABI_VERSION; out[2] = (uint32_t)sizeof(tw_device_env); out[3] = (uint32_t)sizeof(tw::PolicyDev);
+    out[4] = (uint32_t)sizeof(tw::EnvRolloutArgs); out[5] = (uint32_t)sizeof(tw::EnvSolveArgs); out[6] = (uint32_t)sizeof(tw::PaddedRec);
+    out[7] = (uint32_t)sizeof(tw_env_vtable);
+}
+
+namespace tw {
+
+// sample_from_logits (policy.rs:169-172) over the environment's A <= 4 actions: the words of ONE draw (t, STREAM_GUMBEL) as the
+// host path takes them (tw_env_generic.hip), first maximum wins, NaN never; A = 4 is gumbel_argmax4
+template <int A>
+__device__ __forceinline__ int gumbel_argmax_n(const float (&l)[4], const u32x4 w)
+{
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+    int best = 0; float bv = 0.0f;
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+        const float a1 = tw_logf(u32_to_unit(ww[i]));
+        const float gi = l[i] - tw_logf(__builtin_fabsf(a1));
+        if (i == 0) { bv = gi; best = 0; } else if (gi > bv) { bv = gi; best = i; }
+    }
+    return best;
+}
+
+// act_perm of a twist over A actions (EngineV::act_perm reads a table of four per twist): lg[i] = lg[act_perms[perm][i]]
+template <int A>
+__device__ __forceinline__ void env_act_perm(const PolicyDev &pol, int perm, float (&lg)[4])
+{
+    if (perm < 0) return;
+    const float l0 = lg[0], l1 = lg[1], l2 = lg[2], l3 = lg[3];
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+        const int src = pol.act_perms[perm * A + i];
+        lg[i] = src == 0 ? l0 : (src == 1 ? l1 : (src == 2 ? l2 : l3));
+    }
+}
+
+// observe + guard + twist: rows of the forward (-1 = no row) and the raw ids.  An id outside [0, obs_size) is never used as an
+// index: its row is -1, `bad` is set and `bad_id` is the FIRST such id of the observation (the one the host path reports; the
+// caller ends the episode and flags the collect).
+template <class Env, int NC>
+__device__ __forceinline__ void env_rows(const Env &st, const PolicyDev &pol, int perm, int (&ids)[Env::N_OBS], int (&rowoff)[NC], bool &bad, int &bad_id)
+{
+    st.observe(ids);
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        int row = -1;
+        if (i < Env::N_OBS) {
+            const int id = ids[i];
+            if ((unsigned)id >= (unsigned)pol.obs_size) { if (!bad) bad_id = id; bad = true; }
+            else row = perm < 0 ? id : (pol.obs_size > 256 ? (int)pol.obs_perms16[(size_t)perm * pol.obs_size + id]
+                                                            : (int)pol.obs_perms[(size_t)perm * pol.obs_size + id]);
+        }
+        rowoff[i] = row;
+    }
+}
+
+template <class Env, int NC>
+__global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArgs a, const Env proto)
+{
+    using Eng = EngineV<NC>;
+    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    Eng eng;
+    eng.begin1(a.pol, lds);
+    const int j = eng.j;
+    // every lane group of every wave carries the state of column j (the engine's mapping); lanes 0-15 of wave 0 store
+    const uint64_t e_local = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+    const bool valid  = e_local < a.num_episodes;
+    const bool writer = eng.h == 0 && eng.primary();
+    const uint64_t e_global = a.episode_offset + e_local;
+    Env st = proto;                                                                   // clone of the prototype (ppo.rs:59)
+    if (valid) st.reset(a.seed, e_global);                                            // ppo.rs:60
+    bool alive = valid, failed = false;
+    int  t = 0;
+    eng.begin2();
+    while (__syncthreads_or(alive ? 1 : 0)) {
+        int perm = -1;
+        if (eng.pol.n_perms > 0) {                                                    // get_perm_id (policy.rs:67-77)
+            const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_PERM);
+            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
+        }
+        int ids[NO], rowoff[NC];
+        bool bad = false; int bad_id = 0;
+        if (alive) env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+        else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
+        }
+        float lg[4]; float value;
+        eng.forward(rowoff, lg, value);
+        env_act_perm<A>(eng.pol, perm, lg);
+        const uint32_t mb = alive ? st.masks() : 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lg[i] = (i < A && ((mb >> i) & 1u)) ? lg[i] : -1e10f;    // policy.rs:62
+        const float rew = alive ? st.reward() : 0.0f;
+        const u32x4 gw = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_GUMBEL);
+        const int action = gumbel_argmax_n<A>(lg, gw);
+        if (alive) {
+            if (bad) {                                                                // (the host path fails the collect here)
+                if (writer) {                                                         // the library names the first one (t, episode)
+                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
+                    store_rec(a.out.rec + e_local * (uint64_t)a.out.t_pad + (uint64_t)t, zero4, lg, __builtin_bit_cast(float, bad_id), 0.0f, 0, -1);
+                    atomicOr(a.err, 1u);
+                }
+                failed = true;
+                alive = false;
+            } else {
+                if (writer) {                                                         // push the record (ppo.rs:71-76)
+                    const uint64_t rec = e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
+                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
+                    store_rec(a.out.rec + rec, zero4, lg, value, rew, action, perm);
+                    uint16_t *o = a.obs16 + rec * (uint64_t)NO;
+#pragma unroll
+                    for (int i = 0; i < NO; ++i) o[i] = (uint16_t)ids[i];
+                }
+                if (st.is_final()) alive = false;                                     // ppo.rs:78
+                else if (t + 1 >= a.out.t_pad) {                                      // the host path's max_records_per_episode
+                    if (writer) atomicOr(a.err, 2u);
+                    alive = false;
+                } else { st.step(action); ++t; }                                      // ppo.rs:79
+            }
+        }
+    }
+    if (valid && writer) a.out.ep_len[e_local] = ((uint32_t)t + 1u) | (failed ? 0x80000000u : 0u);
+    eng.end();
+}
+
+// evaluate() (rust/src/rl/evaluate.rs:22-89 over single_solve, rl/solve.rs:17-71), as solve_big_kernel: one column = one attempt
+// (episode e, search a): reset, then while !is_final { total += reward; probs = Policy::predict (masked softmax, random twist);
+// action = argmax | weighted sample; step }.  Best-of-N and the means are reduced on the host.
+template <class Env, int NC>
+__global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a, const Env proto)
+{
+    using Eng = EngineV<NC>;
+    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    Eng eng;
+    eng.begin1(a.pol, lds);
+    const uint64_t att = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)eng.j;
+    const bool valid = att < a.num_attempts, writer = eng.h == 0 && eng.primary();
+    const uint64_t ep  = a.episode_offset + att / a.num_searches;                    // episode: keys the start state
+    const uint64_t key = ep * (uint64_t)a.num_searches + att % a.num_searches;       // keys this attempt's draws
+    Env st = proto;                                                                   // evaluate.rs:39
+    if (valid) st.reset(a.seed, ep);
+    bool  alive = valid && !st.is_final(), failed = false;                            // solve.rs:29
+    float total = 0.0f;
+    int   bad_first = 0;
+    int   t = 0;
+    eng.begin2();
+    while (__syncthreads_or(alive ? 1 : 0)) {
+        int perm = -1;
+        if (eng.pol.n_perms > 0) {
+            const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_PERM);
+            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
+        }
+        int ids[NO], rowoff[NC];
+        bool bad = false; int bad_id = 0;
+        if (alive) env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+        else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
+        }
+        float lg[4], value;
+        eng.forward(rowoff, lg, value);
+        env_act_perm<A>(eng.pol, perm, lg);
+        const uint32_t mb = (alive ? st.masks() : 0u) & ((1u << A) - 1u);
+        float probs[4];
+        masked_softmax4(lg, mb, probs);                                               // policy.rs:43-47 (masked entries add +0.0)
+        if (alive) {
+            if (bad) {
+                if (writer) atomicOr(a.err, 1u);
+                failed = true; bad_first = bad_id;
+                alive = false;
+            } else {
+                total = total + st.reward();                                          // solve.rs:31
+                int action = 0;
+                if (a.deterministic) {
+                    float bv = probs[0];
+#pragma unroll
+                    for (int i = 1; i < A; ++i) if (probs[i] > bv) { bv = probs[i]; action = i; }
+                } else {
+                    const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE);
+                    action = sample_weighted4(probs, A, u32_to_unit(w.x));
+                }
+                st.step(action);                                                      // solve.rs:56
+                ++t;
+                if (st.is_final()) alive = false;
+                else if ((uint32_t)t >= a.max_steps) {                                // the host path's max_steps
+                    if (writer) atomicOr(a.err, 4u);
+                    alive = false;
+                }
+            }
+        }
+    }
+    if (valid && writer) {
+        total = total + st.reward();                                                  // solve.rs:65-66
+        a.success[att] = st.success() ? 1.0f : 0.0f;                                  // solve.rs:68
+        a.total[att]   = failed ? __builtin_bit_cast(float, bad_first) : total;
+        a.n_steps[att] = (uint32_t)t | (failed ? 0x80000000u : 0u);
+    }
+    eng.end();
+}
+
+template <class Env>
+int launch_rollout_env(const EnvRolloutArgs *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
+{
+    constexpr int NC = env_engine_nc(Env::N_OBS);
+    Env p;
+    __builtin_memcpy(&p, proto, sizeof(Env));
+    const void *k = reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((rollout_env_kernel<Env, NC>), dim3(blocks), dim3(EngineV<NC>::THREADS), lds_bytes, s, *a, p);
+    return (int)hipGetLastError();
+}
+
+template <class Env>
+int launch_solve_env(const EnvSolveArgs *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
+{
+    constexpr int NC = env_engine_nc(Env::N_OBS);
+    Env p;
+    __builtin_memcpy(&p, proto, sizeof(Env));
+    const void *k = reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((solve_env_kernel<Env, NC>), dim3(blocks), dim3(EngineV<NC>::THREADS), lds_bytes, s, *a, p);
+    return (int)hipGetLastError();
+}
+
+}  // namespace tw

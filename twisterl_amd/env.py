@@ -216,3 +216,153 @@ def get_env_desc(py_env) -> "_lib.PuzzleDesc":
         raise TypeError("Expected environment of type twisterl_amd.env.Puzzle "
                         "(the HIP collectors cannot run a foreign Box<dyn Env>)")
     return py_env._desc()
+
+
+class DeviceEnvDesc(C.Structure):
+    """struct tw_device_env (twisterl_amd/csrc/tw_rollout_env.hpp): what a device-environment module exports."""
+    _fields_ = [("layout", C.c_uint32 * 8), ("num_actions", C.c_uint32), ("n_obs", C.c_uint32), ("state_bytes", C.c_uint32),
+                ("engine_nc", C.c_uint32), ("type_name", C.c_char_p), ("launch_rollout", C.c_void_p), ("launch_solve", C.c_void_p),
+                ("create", C.CFUNCTYPE(C.c_void_p, C.POINTER(C.c_double), C.c_int)),
+                ("get_difficulty", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("set_difficulty", C.CFUNCTYPE(None, C.c_void_p, C.c_int)),
+                ("obs_size", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("fill_vtable", C.c_void_p)]
+
+
+class DeviceEnv:
+    """DeviceEnv(module_path, name, params=[...]): a user-written environment that runs ON THE DEVICE -- a C++ struct
+    (include/twisterl_device_env.hpp) compiled by twisterl_amd.build.build_device_env into `module_path`, which exports
+    tw_device_env_<name>.  `params` go to the struct's init() (the environment's constructor arguments).
+
+    PPOCollector.collect and evaluate run its episodes inside one kernel each (tw_ppo_collect_device_env / tw_evaluate_device_env);
+    AZCollector.collect and solve step the same struct's host code (tw_az_collect_env / tw_solve_env32).  The object itself is a
+    host copy of the struct with the PyBaseEnv surface (reset / step / masks / observe / reward / is_final); collectors clone
+    it and reset the clones, as the reference does (collector/ppo.rs:59-60).
+
+    `max_records`: the longest episode a collect accepts (a longer one fails it, as on the host-stepped path).  Set it to the
+    environment's own bound (GridWorld: max_steps + 1): the device collect's padded workspace holds num_episodes x max_records x
+    (48 + 2 x n_obs) bytes -- 65,536 GridWorld 5 x 5 episodes at the default 256: 1.6 GB.  Above 1,820 records the collect runs on
+    the host-stepped path (the finalize step's LDS tile)."""
+
+    def __init__(self, module_path: str, name: str, params=(), *, max_records: int = 256):
+        import os
+        L = _lib.lib()                           # (loads the HIP runtime torch uses first; the module binds to it)
+        path = os.path.abspath(module_path)
+        try:
+            self._mod = C.CDLL(path)
+        except OSError as e:
+            raise RuntimeError(f"cannot load the device environment module {path}: {e}") from e
+        fn = getattr(self._mod, f"tw_device_env_{name}", None)
+        if fn is None:
+            raise ValueError(f"{path} exports no tw_device_env_{name}")
+        fn.restype, fn.argtypes = C.c_void_p, []
+        self._desc_ptr = fn()
+        self._desc = DeviceEnvDesc.from_address(self._desc_ptr)
+        p = [float(x) for x in params]
+        self._obj = self._desc.create((C.c_double * max(len(p), 1))(*p), len(p))
+        if not self._obj:
+            raise ValueError(f"{self._desc.type_name.decode()}: init() refused the parameters {p}")
+        self._vt = _lib.EnvVTable()
+        rc = L.tw_device_env_host_vtable(self._desc_ptr, self._obj, self._desc.state_bytes, C.byref(self._vt))
+        if rc != _lib.TW_OK:
+            msg = _lib.last_error()
+            self._free()
+            raise ValueError(msg)
+        self.max_records = int(max_records)
+        if not 1 <= self.max_records <= 0x7fffffff:
+            raise ValueError("max_records must be positive")
+
+    def _free(self):
+        obj, self._obj = getattr(self, "_obj", None), None
+        if obj:
+            # the module's destroy (the vtable may not be filled yet: free through the one the module fills)
+            vt = _lib.EnvVTable()
+            C.CFUNCTYPE(None, C.POINTER(_lib.EnvVTable))(self._desc.fill_vtable)(C.byref(vt))
+            vt.destroy(obj)
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:
+            pass
+
+    # -- PyBaseEnv surface on the host copy ------------------------------------------------------
+    @property
+    def name(self) -> str:
+        return self._desc.type_name.decode()
+
+    def num_actions(self) -> int:
+        return int(self._desc.num_actions)
+
+    @property
+    def n_obs(self) -> int:
+        return int(self._desc.n_obs)
+
+    @property
+    def obs_size(self) -> int:
+        return int(self._desc.obs_size(self._obj))
+
+    def obs_shape(self) -> list:
+        """[n_obs, obs_size / n_obs] when that divides (GridWorld: [w*h, w*h], lib.rs obs_shape), else [obs_size]."""
+        n, s = self.n_obs, self.obs_size
+        return [n, s // n] if s % n == 0 else [s]
+
+    @property
+    def difficulty(self) -> int:
+        return int(self._desc.get_difficulty(self._obj))
+
+    @difficulty.setter
+    def difficulty(self, value: int) -> None:
+        if int(value) < 0:
+            raise OverflowError("can't convert negative int to unsigned")
+        self._desc.set_difficulty(self._obj, int(value))
+
+    def reset(self, seed: int = None, episode: int = 0) -> None:
+        """Env::reset keyed by (seed, episode) as in the collectors; seed=None picks a fresh OS seed."""
+        if seed is None:
+            import os
+            seed = int.from_bytes(os.urandom(8), "little")
+        self._vt.reset(self._obj, int(seed) & (2**64 - 1), int(episode) & (2**64 - 1))
+
+    def step(self, action: int) -> None:
+        if not 0 <= int(action) < self.num_actions():
+            raise ValueError(f"action {action} outside [0, {self.num_actions()})")
+        self._vt.step(self._obj, int(action))
+
+    def masks(self) -> list:
+        out = (C.c_uint8 * self.num_actions())()
+        self._vt.masks(self._obj, out)
+        return [bool(x) for x in out]
+
+    def observe(self) -> list:
+        out = (C.c_int32 * self.n_obs)()
+        self._vt.observe(self._obj, out)
+        return [int(x) for x in out]
+
+    def reward(self) -> float:
+        return float(self._vt.reward(self._obj))
+
+    def is_final(self) -> bool:
+        return bool(self._vt.is_final(self._obj))
+
+    def success(self) -> bool:
+        return bool(self._vt.success(self._obj))
+
+    def twists(self):
+        """Env::twists default (rl/env.rs:59): none; a policy with twists is built by the host, as for any environment."""
+        return ([], [])
+
+    def state_bytes(self) -> bytes:
+        """The struct as it is (it is trivially copyable: this IS the environment's state)."""
+        return C.string_at(self._obj, self._desc.state_bytes)
+
+    def set_state_bytes(self, data: bytes) -> None:
+        if len(data) != self._desc.state_bytes:
+            raise ValueError(f"{len(data)} bytes for a {self._desc.state_bytes}-byte environment")
+        C.memmove(self._obj, bytes(data), len(data))
+
+    def __extract_env__(self) -> int:
+        """Address of the host copy of the struct (the prototype the collectors clone)."""
+        return int(self._obj)
+
+    # -- used by the collectors ------------------------------------------------------------------
+    def _args(self):
+        return self._desc_ptr, self._obj, self._desc.state_bytes
