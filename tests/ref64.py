@@ -113,3 +113,135 @@ def gae_f64_episodes(rews, vals, ep_len, gamma, lam):
         advs[idx] = rets[idx] - v[idx]
         nxt_v[live], nxt_a[live] = v[idx], advs[idx]
     return advs, rets
+
+
+# ---------------------------------------------------------------------------------------------- a-priori error bounds
+# Forward error of one Linear y = W^T x + b computed in a mode with rounded operands and f32 accumulation, against float64
+# on the exact inputs:  |y^ - y| <= |W|^T err_in + gamma(k) (|W|^T |x| + |b|) + eta (|W|^T 1 + sum |x|),   k = fan_in + 1.
+# ReLU is non-expansive, so the bound of a layer's output is the bound of its input to the next.  Per mode:
+#   "f32"    (ARITH_REF / ARITH_CHAIN, Engine3, EngineV): operands exact, gamma = k u / (1 - k u), u = 2^-24, eta = 0;
+#   "fp16x2" (EngineS): x = hi + lo + r with |r| <= 2^-22 |x| (+ a subnormal lo's 2^-25 at the x16 scale, 2^-29 unscaled),
+#            lo * lo dropped (<= 2^-22 |W||x|); per product 3 x 2^-22 + 2^-44, three products per term accumulated in f32;
+#   "fp16"   (ARITH_F16, Engine16): weights and activations rounded to binary16, 2^-11 each (+ 2^-25 below 2^-14).
+# Valid while no operand overflows its format: |x| < 65504 in fp16; the split's range (tw_engine16x2.hpp) in fp16x2.
+U32 = 2.0 ** -24
+MODES = {
+    #          relative error per product of two operands, absolute error per operand, accumulated terms per input
+    "f32":    (0.0, 0.0, 1),
+    "fp16x2": (3 * 2.0 ** -22 + 2.0 ** -44, 2.0 ** -29, 3),
+    "fp16":   (2 * 2.0 ** -11 + 2.0 ** -22, 2.0 ** -25, 1),
+}
+
+
+def _gamma(mode, k):
+    rel, _, per = MODES[mode]
+    n = per * k
+    return rel + n * U32 / (1 - n * U32) + rel * n * U32
+
+
+def _layer_bound(mode, W, b, x, err):
+    """float64 |W|^T err + gamma (|W|^T |x| + |b|) + eta (|W|^T 1 + sum |x|) for a batch x [n, in]."""
+    aW, ax = np.abs(W), np.abs(x)
+    eta = MODES[mode][1]
+    out = err @ aW + _gamma(mode, W.shape[0] + 1) * (ax @ aW + np.abs(b))
+    if eta:
+        out += eta * (aW.sum(axis=0)[None, :] + ax.sum(axis=1, keepdims=True))
+    return out
+
+
+def forward_f64_bound(arrs, obs_perms, act_perms, obs, masks, perms, mode, emb_relu=True, chunk=8192):
+    """forward_f64 plus an a-priori bound of |mode's result - float64| per logit and value (0 where the logit is masked).
+    -> logits, values, err_logits, err_values.  Holds only inside the mode's range: see max_activations()."""
+    emb, eb, common, action, value = arrs
+    V = np.asarray(emb, np.float64)
+    obs = np.asarray(obs, np.int64).reshape(len(obs), -1)
+    n = obs.shape[0]
+    masks = np.asarray(masks, bool).reshape(n, -1)
+    perms = np.asarray(perms, np.int64).reshape(n)
+    OP = np.asarray(obs_perms, np.int64) if len(obs_perms) else None
+    AP = np.asarray(act_perms, np.int64) if len(act_perms) else None
+    lay = lambda ls: [(np.asarray(w, np.float64).reshape(-1, np.asarray(b).size), np.asarray(b, np.float64), r) for (w, b, r) in ls]
+    common, action, value = lay(common), lay(action), lay(value)
+    ebias = np.asarray(eb, np.float64)
+    rel, eta, _ = MODES[mode]
+    A = action[-1][1].size
+    logits, values = np.empty((n, A)), np.empty(n)
+    el, ev = np.zeros((n, A)), np.empty(n)
+
+    def seq(layers, x, e):
+        for W, b, r in layers:
+            e = _layer_bound(mode, W, b, x, e)
+            x = x @ W + b
+            if r:
+                x = np.maximum(x, 0.0)
+        return x, e
+
+    for s in range(0, n, chunk):
+        ids, p = obs[s:s + chunk], perms[s:s + chunk]
+        tw = p >= 0
+        if tw.any():
+            ids = ids.copy()
+            ids[tw] = np.take_along_axis(OP[p[tw]], ids[tw], axis=1)
+        rows = V[ids]                                                    # [m, cells, emb]
+        h = ebias + rows.sum(axis=1)
+        # EmbeddingBag: the table entries are the rounded operands (one-hot x table), the bias an f32 addend
+        e = _gamma(mode, ids.shape[1] + 1) * (np.abs(rows).sum(axis=1) + np.abs(ebias)) + eta * ids.shape[1]
+        if emb_relu:
+            h = np.maximum(h, 0.0)
+        h, e = seq(common, h, e)
+        v, evv = seq(value, h, e)
+        la, ela = seq(action, h, e)
+        m = slice(s, s + len(ids))
+        values[m], ev[m] = v.sum(axis=1), evv.sum(axis=1)
+        if tw.any():
+            la[tw] = np.take_along_axis(la[tw], AP[p[tw]], axis=1)
+            ela[tw] = np.take_along_axis(ela[tw], AP[p[tw]], axis=1)
+        logits[m] = np.where(masks[m], la, MASKED)
+        el[m] = np.where(masks[m], ela, 0.0)
+    return logits, values, el, ev
+
+
+def gae_bound_episodes(rews, vals, err_vals, ep_len, gamma, lam):
+    """A bound of |f32 GAE of values v^ (|v^ - vals| <= err_vals) - gae_f64_episodes(rews, vals)| per record -> (err_advs,
+    err_rets): the value errors carried through the recurrence plus f32 rounding (three roundings per step)."""
+    advs, rets = gae_f64_episodes(rews, vals, ep_len, gamma, lam)
+    L = np.asarray(ep_len, np.int64)
+    starts = np.concatenate([[0], np.cumsum(L)[:-1]])
+    r, v, dv = (np.asarray(x, np.float64) for x in (rews, vals, err_vals))
+    ea, er = np.empty(r.size), np.empty(r.size)
+    nxt_a = np.zeros(L.size)
+    for k in range(int(L.max()) if L.size else 0):
+        live = L > k
+        idx = starts[live] + L[live] - 1 - k
+        if k == 0:
+            er[idx] = 0.0
+        else:
+            nxt = idx + 1
+            er[idx] = gamma * (dv[nxt] + lam * nxt_a[live]) + 3 * U32 * (np.abs(r[idx]) + gamma * (np.abs(v[nxt]) + lam * np.abs(advs[nxt]))
+                                                                           + np.abs(rets[idx])) * 1.01
+        ea[idx] = er[idx] + dv[idx] + U32 * np.abs(advs[idx]) * 1.01
+        nxt_a[live] = ea[idx]
+    return ea, er
+
+
+def max_activations(arrs, obs_perms, act_perms, obs, perms, emb_relu=True):
+    """Largest |embedding output| and |hidden-layer output| (after the activation: common layers and the heads' hidden
+    layers) over the records: what the f16 modes' ranges are stated in (fp16: 65504; fp16x2: 4095 and 255.94)."""
+    emb, eb, common, action, value = arrs
+    obs = np.asarray(obs, np.int64).reshape(len(obs), -1)
+    p = np.asarray(perms, np.int64).reshape(-1)
+    if (p >= 0).any():
+        OP = np.asarray(obs_perms, np.int64)
+        obs = obs.copy()
+        obs[p >= 0] = np.take_along_axis(OP[p[p >= 0]], obs[p >= 0], axis=1)
+    h = embedding_bag_f64(emb, eb, emb_relu, obs)
+    m0, m1 = float(np.abs(h).max()), 0.0
+    for w, b, r in common:
+        h = linear_f64(w, b, r, h)
+        m1 = max(m1, float(np.abs(h).max()))
+    for head in (action, value):
+        x = h
+        for w, b, r in head[:-1]:
+            x = linear_f64(w, b, r, x)
+            m1 = max(m1, float(np.abs(x).max()))
+    return m0, m1

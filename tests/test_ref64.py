@@ -171,3 +171,117 @@ def test_known_answers_of_the_reference(oracle):
     a32, r32 = oracle.gae(c["rewards"], c["values"], c["gamma"], c["lambda"])
     np.testing.assert_allclose(r32, r64, rtol=0, atol=1e-6)
     np.testing.assert_allclose(a32, a64, rtol=0, atol=1e-6)
+
+
+# ---------------------------------------------------------------------------------------------- a-priori error bounds
+def _scaled(arrs, k):
+    f = np.float32(2.0 ** k)
+    emb, eb, common, action, value = arrs
+    sc = lambda ls: [(np.asarray(w, np.float32) * f, np.asarray(b, np.float32) * f, r) for (w, b, r) in ls]
+    return (np.asarray(emb, np.float32) * f, np.asarray(eb, np.float32) * f, sc(common), sc(action), sc(value))
+
+
+BOUND_FIXTURES = ["synthetic_scale1", "trained_puzzle8", "deep"]
+
+
+@pytest.mark.parametrize("name", BOUND_FIXTURES)
+def test_oracle_forwards_stay_inside_their_a_priori_bounds(oracle, name):
+    """ARITH_REF and ARITH_CHAIN inside the f32 bound, ARITH_F16 inside the fp16 bound (where no activation reaches 65504),
+    with every weight scaled by 2^k, k = -12 .. 6."""
+    from tests.ref64 import forward_f64_bound, max_activations
+    n2, arrs0, op, ap = _policies()[name]
+    obs, masks, perms = _records(n2, 300, seed=11)
+    checked_f16 = 0
+    for k in range(-12, 7):
+        arrs = _scaled(arrs0, k)
+        pol = oracle.Policy(*arrs, op, ap)
+        for arith, mode in ((oracle.ARITH_REF, "f32"), (oracle.ARITH_CHAIN, "f32"), (oracle.ARITH_F16, "fp16")):
+            if mode == "fp16" and max(max_activations(arrs, op, ap, obs, perms)) >= 65504 / 2:
+                continue                                           # outside fp16's range: it overflows there as its spec says
+            l64, v64, el, ev = forward_f64_bound(arrs, op, ap, obs, masks, perms, mode)
+            lg, v = pol.forward_batch(obs, masks, perms, arith=arith, num_threads=4)
+            dl = np.abs(lg.astype(np.float64) - l64)[masks]
+            dv = np.abs(v.astype(np.float64) - v64)
+            assert np.all(dl <= el[masks]) and np.all(dv <= ev), (name, k, arith, float(np.max(dl - el[masks])), float(np.max(dv - ev)))
+            checked_f16 += mode == "fp16"
+            # the bound is a bound, not a blanket: within three orders of magnitude of the largest deviation seen at scale 1
+            if k == 0 and mode == "f32":
+                assert float(np.max(el[masks])) < 1e-3 * max(1.0, float(np.max(np.abs(l64[masks]))))
+    assert checked_f16 >= 10, checked_f16
+
+
+def _split(x):
+    """x16 split of f32 values into binary16 hi / lo terms (tw_engine16x2.hpp), back in f64 and unscaled."""
+    sx = np.asarray(x, np.float32) * np.float32(16)
+    hi = sx.astype(np.float16)
+    lo = (sx - hi.astype(np.float32)).astype(np.float16)
+    return hi.astype(np.float64) / 16, lo.astype(np.float64) / 16
+
+
+def _split_forward(arrs, obs, drop_wlo_hhi):
+    """numpy emulation of EngineS on one-common-layer policies, no twists: logits and values in f64 from the split terms."""
+    emb, eb, common, action, value = arrs
+    (w1, b1, _), = common
+    (wa, ba, _), = action
+    (wv, bv, _), = value
+    H = np.asarray(b1).size
+    Th, Tl = _split(emb)
+    h0 = np.maximum(Th[obs].sum(axis=1) + Tl[obs].sum(axis=1) + np.asarray(eb, np.float64), 0)
+    h0 = h0.astype(np.float32)
+
+    def lin(x, w, b):
+        Wh, Wl = _split(np.asarray(w).reshape(-1, np.asarray(b).size))
+        xh, xl = _split(x)
+        y = xh @ Wh + xl @ Wh + (0 if drop_wlo_hhi else xh @ Wl)
+        return y + np.asarray(b, np.float64)
+    h1 = np.maximum(lin(h0, w1, b1), 0).astype(np.float32)
+    Wh = np.concatenate([np.asarray(wa).reshape(H, -1), np.asarray(wv).reshape(H, 1)], axis=1)
+    out = lin(h1, Wh.reshape(-1), np.concatenate([np.asarray(ba), np.asarray(bv)]))
+    return out[:, :-1], out[:, -1]
+
+
+def _coherent_policy():
+    """make_policy_arrays(16, seed=0, emb=64, hidden=32) with every common and head weight set to (1/3) / sqrt(fan_in): all
+    products of a layer are positive (ReLU outputs times positive weights) and every W_lo has the same sign, so an error in
+    the split terms adds up instead of averaging out."""
+    emb, eb, common, action, value = make_policy_arrays(16, seed=0, emb=64, hidden=32)
+    third = lambda ls, fan: [(np.full_like(w, np.float32(1 / 3) / np.float32(np.sqrt(fan))), b, r) for (w, b, r) in ls]
+    return emb, eb, third(common, 64), third(action, 32), third(value, 32)
+
+
+def test_split_emulation_inside_the_fp16x2_bound_and_the_bound_can_fail():
+    """The fp16x2 bound holds for a numpy emulation of the split on a random policy and on the coherent one, and the
+    emulation with the W_lo * h_hi product dropped exceeds it on the coherent one (500 Puzzle-15 boards, no twists)."""
+    from tests.ref64 import forward_f64_bound
+    obs, masks, _ = _records(16, 500, seed=5, all_legal=True)
+    perms = np.full(500, -1)
+    arrs = make_policy_arrays(16, seed=0, emb=128, hidden=64)
+    l64, v64, el, ev = forward_f64_bound(arrs, [], [], obs, masks, perms, "fp16x2")
+    lg, v = _split_forward(arrs, obs, drop_wlo_hhi=False)
+    assert np.all(np.abs(lg - l64) <= el) and np.all(np.abs(v - v64) <= ev)
+    arrs = _coherent_policy()
+    perms = np.full(500, -1)
+    l64, v64, el, ev = forward_f64_bound(arrs, [], [], obs, masks, perms, "fp16x2")
+    lg, v = _split_forward(arrs, obs, drop_wlo_hhi=False)
+    assert np.all(np.abs(lg - l64) <= el) and np.all(np.abs(v - v64) <= ev)
+    lg, v = _split_forward(arrs, obs, drop_wlo_hhi=True)
+    assert np.any(np.abs(lg - l64) > el) and np.any(np.abs(v - v64) > ev)
+
+
+def test_gae_bound_holds_for_perturbed_values(oracle):
+    """The GAE bound carries a value error through the recurrence: the oracle's f32 GAE of values moved by up to `err` stays
+    inside it, at the benchmark's horizon."""
+    from tests.ref64 import gae_bound_episodes, gae_f64_episodes
+    rng = np.random.default_rng(3)
+    lens = [257, 1, 2, 100]
+    rews = np.concatenate([_episode(n, s)[0] for s, n in enumerate(lens)])
+    vals = np.concatenate([_episode(n, s)[1] for s, n in enumerate(lens)]).astype(np.float64)
+    err = np.full(vals.size, 3e-6)
+    moved = (vals + rng.uniform(-1, 1, vals.size) * err).astype(np.float32)
+    a64, r64 = gae_f64_episodes(rews, vals, lens, 0.995, 0.995)
+    ea, er = gae_bound_episodes(rews, vals, err + 2.0 ** -24, lens, 0.995, 0.995)       # (+ the rounding of the moved values)
+    s = 0
+    for n in lens:
+        a32, r32 = oracle.gae(rews[s:s + n], moved[s:s + n], 0.995, 0.995)
+        assert np.all(np.abs(a32 - a64[s:s + n]) <= ea[s:s + n]) and np.all(np.abs(r32 - r64[s:s + n]) <= er[s:s + n])
+        s += n

@@ -10,6 +10,7 @@
 #include "tw_common.hpp"
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -639,7 +640,8 @@ extern "C" tw_policy *tw_policy_create(const tw_policy_desc *d)
     // split-f16 image (EngineS, tw_engine16x2.hpp)
     const uint32_t SPS = f16_ok ? ((std::max(nc16 + 2 * NT, 4 * NT) + 3) / 4 * 4) : 0;
     const bool split_ok = f16_ok && NKT >= 2;
-    const Seg s_stS = seg(split_ok ? (size_t)(2 * NKT + 1) * SPS * 1024 : 0), s_t0S = seg(split_ok ? (size_t)2 * nc16 * 1024 : 0);
+    const Seg s_stS = seg(split_ok ? (size_t)(2 * NKT + 1) * SPS * 1024 : 0), s_t0S = seg(split_ok ? (size_t)2 * nc16 * 1024 : 0),
+              s_srng = seg(split_ok ? 4 : 0);
     std::vector<uint8_t> img(cur, 0);
     float *emb = reinterpret_cast<float *>(img.data() + s_emb.off);
     memcpy(emb, d->emb_vectors, (size_t)OS * E * 4);
@@ -728,10 +730,13 @@ extern "C" tw_policy *tw_policy_create(const tw_policy_desc *d)
         memcpy(img.data() + s_src16.off, srcmap.data(), srcmap.size());
         memcpy(img.data() + s_vm16.off, vmap.data(), vmap.size());
         if (split_ok) {
-            // x = x_hi + x_lo with both terms binary16, operands pre-scaled by 16 (exact): hi = f16(16x), lo = f16(16x - hi)
+            // x = x_hi + x_lo with both terms binary16, operands pre-scaled by 16 (exact): hi = f16(16x), lo = f16(16x - hi);
+            // |x| >= 4095 (or a NaN) has no finite pair: split_range says so, and the split mode then runs in f32
+            uint32_t out_of_range = 0;
             auto put2 = [&](size_t off_hi, size_t off_lo, float x) {
                 const float sx = 16.0f * x;
                 const _Float16 hi = (_Float16)sx, lo = (_Float16)(sx - (float)hi);
+                if (!std::isfinite((float)hi) || !std::isfinite((float)lo)) out_of_range = 1;
                 memcpy(img.data() + off_hi, &hi, 2); memcpy(img.data() + off_lo, &lo, 2);
             };
             for (uint32_t kt = 0; kt < NKT; ++kt) {
@@ -767,6 +772,7 @@ extern "C" tw_policy *tw_policy_create(const tw_policy_desc *d)
                             const size_t po = (size_t)(ht * 2 + m) * 1024 + l * 16 + jx * 2;
                             put2(bh + po, bh + (size_t)2 * NT * 1024 + po, x);
                         }
+            memcpy(img.data() + s_srng.off, &out_of_range, 4);
         }
     }
 
@@ -804,6 +810,7 @@ extern "C" tw_policy *tw_policy_create(const tw_policy_desc *d)
     pd.bh16 = reinterpret_cast<const float *>(base + s_bh16.off);
     pd.srcmap16 = base + s_src16.off; pd.vmap16 = base + s_vm16.off;
     pd.stageS = split_ok ? base + s_stS.off : nullptr; pd.t0S = split_ok ? base + s_t0S.off : nullptr;
+    pd.split_range = split_ok ? reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(base) + s_srng.off) : nullptr;
     pol->n16 = n16; pol->sp16 = SP16; pol->sps = split_ok ? SPS : 0;
     return pol;
 }
@@ -825,9 +832,10 @@ extern "C" int tw_policy_update_device(tw_policy *p, const float *emb_w, const f
     a.ba_nat = (float *)w(d.ba); a.wv_nat = (float *)w(d.wv); a.bv_nat = (float *)w(d.bv);
     a.stage16 = (uint8_t *)w(d.stage16); a.head16 = (uint8_t *)w(d.head16); a.ebias16 = (float *)w(d.ebias16);
     a.b1img16 = (float *)w(d.b1img16); a.bh16 = (float *)w(d.bh16);
-    a.stageS = (uint8_t *)w(d.stageS); a.t0S = (uint8_t *)w(d.t0S); a.SPS = (int)p->sps;
+    a.stageS = (uint8_t *)w(d.stageS); a.t0S = (uint8_t *)w(d.t0S); a.SPS = (int)p->sps; a.split_range = d.split_range;
     const bool f16 = d.f16_nc != 0;
-    const bool split = f16 && p->sps != 0 && d.stageS && d.t0S;
+    const bool split = f16 && p->sps != 0 && d.stageS && d.t0S && d.split_range;
+    if (split) TW_HIP(hipMemsetAsync(d.split_range, 0, 4, current_stream()));      // (the sync kernel sets it again for an out-of-range term)
     const unsigned long long cnt[18] = {
         (unsigned long long)(a.OS + 2) * a.E, (unsigned long long)a.E * a.NQ * 128, (unsigned long long)(a.E / 16) * 21 * 256,
         (unsigned long long)a.H, (unsigned long long)a.H * 8, 8ull, (unsigned long long)a.E * a.H, (unsigned long long)a.H * a.A,
@@ -1167,9 +1175,32 @@ static int collect_big_board(const tw_puzzle_desc *env, const tw_policy *policy,
     return rc;
 }
 
+static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, const tw_ppo_params *prm, tw_collected **out, bool *out_of_range);
+
+// The split-f16 mode computes what the f32 mode computes only while every operand has a finite pair of f16 terms
+// (tw_engine16x2.hpp, "Range"): a weight of 4095 or more, an embedding activation of 4095 or more, a hidden activation of
+// 255.94 or more.  The kernel flags a collect that left that range; the library then says so once on stderr and returns
+// the f32 mode's collect instead -- never results the f32 mode would not have given.
 extern "C" int tw_ppo_collect(const tw_puzzle_desc *env, const tw_policy *policy, const tw_ppo_params *prm,
                               tw_collected **out)
 {
+    bool out_of_range = false;
+    int rc = ppo_collect_once(env, policy, prm, out, &out_of_range);
+    if (rc != TW_OK && out_of_range) {
+        static std::atomic<bool> said{false};
+        if (!said.exchange(true))
+            fprintf(stderr, "[twisterl_hip] precision fp16x2: a weight or an activation is outside the range of the split-f16 terms "
+                            "(|weight| < 4095, |embedding| < 4095, |hidden| < 255.9): such collects run in fp32\n");
+        tw_ppo_params p32 = *prm;
+        p32.precision = TW_PREC_F32_EXACT;
+        rc = ppo_collect_once(env, policy, &p32, out, &out_of_range);
+    }
+    return rc;
+}
+
+static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, const tw_ppo_params *prm, tw_collected **out, bool *out_of_range)
+{
+    *out_of_range = false;
     if (!env || !policy || !prm || !out) { set_error("tw_ppo_collect: null argument"); return TW_ERR_INVALID; }
     *out = nullptr;
     if (prm->num_episodes == 0) {
@@ -1214,7 +1245,7 @@ extern "C" int tw_ppo_collect(const tw_puzzle_desc *env, const tw_policy *policy
                             : prm->precision == TW_PREC_F32_EXACT ? f32_resident_episodes(E, (int)ra.pol.hidden, false, ra.reserve_cus)
                                                                   : rollout_f32_resident_episodes(ra.reserve_cus);
     const bool persist = E > resident && !launch_options().no_persist && !big;
-    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(8),
+    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(16),     // (+8: range_flag)
                  o_scan = seg(scan_scratch_bytes(E)), o_init = seg(persist ? E * 16 : 0), o_queue = seg(persist ? 4 : 0),
                  o_obs16 = seg(big ? R * cells * 2 : 0), o_boards = seg(persist ? E * 8 : 0), o_ordscr = seg(persist ? episode_order_scratch_bytes(E) : 0);
     void *wsp = nullptr;
@@ -1227,6 +1258,10 @@ extern "C" int tw_ppo_collect(const tw_puzzle_desc *env, const tw_policy *policy
 
     EventSet ev; rc = ev.init(); if (rc) return rc;
     tw_collect_stats st{};
+    if (prm->precision == TW_PREC_F16X2 && ra.pol.split_range) {   // the weight images' own flag, then whatever the kernel adds
+        ra.range_flag = reinterpret_cast<uint32_t *>(ws + o_total + 8);
+        TW_HIP(hipMemcpyAsync(ra.range_flag, ra.pol.split_range, 4, hipMemcpyDeviceToDevice, s));
+    }
     if (persist) {
         ra.init_boards = reinterpret_cast<const uint4 *>(ws + o_init);
         ra.queue = reinterpret_cast<unsigned int *>(ws + o_queue);
@@ -1255,9 +1290,15 @@ extern "C" int tw_ppo_collect(const tw_puzzle_desc *env, const tw_policy *policy
     rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;
     TW_HIP(hipEventRecord(ev.ev[2], s));
-    uint64_t total = 0;
-    TW_HIP(hipMemcpyAsync(&total, total_d, 8, hipMemcpyDeviceToHost, s));
+    uint64_t total_and_flag[2] = {0, 0};          // {record count, range_flag}: one copy
+    TW_HIP(hipMemcpyAsync(total_and_flag, total_d, ra.range_flag ? 16 : 8, hipMemcpyDeviceToHost, s));
     TW_HIP(hipStreamSynchronize(s));
+    const uint64_t total = total_and_flag[0];
+    if (total_and_flag[1] & 0xffffffffull) {
+        *out_of_range = true;
+        set_error("precision fp16x2: an operand outside the range of the split-f16 terms");
+        return TW_ERR_UNSUPPORTED;
+    }
     if (total == 0 || total > R) { set_error("collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
 
     // ---- compact result ----------------------------------------------------------------------

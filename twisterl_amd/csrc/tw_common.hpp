@@ -434,6 +434,7 @@ struct PolicyDev {
     // split-f16 image (TW_PREC_F16X2, EngineS in tw_engine16x2.hpp): operands x16, hi / lo binary16 terms
     const uint8_t *stageS;    // [2*emb/32 + 1][SP KiB]: stage 2k = [T_hi(k+1) | W1_hi(k)], 2k+1 = lo terms, last = [head_hi | head_lo]
     const uint8_t *t0S;       // [2*f16_nc KiB]: table tile 0, hi chunks then lo chunks
+    uint32_t      *split_range;   // [1]: nonzero while a term of the split images is not a finite f16 (tw_policy_create, policy_sync_kernel)
     // generic stacks (any Sequential depth; EngineV): layers = common | action | value; hidden == 0 marks such a policy
     int32_t generic, n_common, n_action, n_value, value_out;
     int32_t gen_rows0, gen_rows1, gen_rows2;   // rows ([unit][column]) of EngineV's three activation buffers: the widest layer each one ever holds
@@ -516,6 +517,9 @@ struct RolloutArgs {
                                    //   (one array, one pointer: a second one for the order cost the 8-wave kernel 0.6 %)
     unsigned int   *queue;         // next unassigned entry of init_boards, or null
     int32_t         reserve_cus;   // persistent mode: CUs left without a workgroup (room for RCCL's send/recv kernels, dist.py)
+    // split-f16 mode: starts as the policy's split_range word; the kernel ORs in 1 when an activation leaves the range of the
+    // split (EngineS::out_of_range) -- the host then runs the collect again in f32 (tw_ppo_collect)
+    uint32_t       *range_flag;
 };
 
 // Waves per workgroup of the f32 engine for a batch of n columns (episodes / attempts): 8 (two per SIMD, 256 columns) is
@@ -651,6 +655,7 @@ struct SyncArgs {
     float *emb_rows, *w1p, *t_img16, *b1_d, *wh8, *bh8, *w1_nat, *wa_nat, *ba_nat, *wv_nat, *bv_nat;
     uint8_t *stage16, *head16; float *ebias16, *b1img16, *bh16;
     uint8_t *stageS, *t0S; int SPS;     // split-f16 images (tw_engine16x2.hpp); SPS = KiB per stage
+    uint32_t *split_range;               // zeroed before the launch; a term that is not a finite f16 sets it
     // element counts per segment (prefix sums in seg_end)
     unsigned long long seg_end[18];
 };

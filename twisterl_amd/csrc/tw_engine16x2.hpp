@@ -16,6 +16,15 @@
 // ring stages: stage 2k holds [T_hi(k+1) | W_hi(k)], stage 2k+1 holds [T_lo(k+1) | W_lo(k)]; the embedding
 // accumulators of tile k+1 are carried across the pair; stage 2*n_kt holds the head images [hi | lo].
 // 160 MFMAs per embedding tile instead of 64 -- against 16x fewer cycles per MFMA than the f32 path.
+//
+// Range.  A term is a finite f16 only below 65520 (f16(u) rounds to inf from there on, and hi = inf makes lo = -inf and
+// every product with them inf or NaN).  With the x16 / x256 scales that is |table entry|, |embedding bias|, |W1|, |head
+// weight| < 4095 (checked where the images are built: PolicyDev::split_range) and, for the activations, 16*|h0| and 256*|h1|
+// below 65520: |h0| < 4095, |h1| < 255.94.  Outside it a term is +-inf, and the conversions carry that to the heads: the
+// ReLU of split_unit is a NaN-propagating maximum (v_maximum3_f32, as cheap as v_max), so an embedding term that overflowed
+// (its column's common accumulators inf or NaN, 0 * inf included) is not turned into 0 by fmaxf(NaN, 0), and an inf hi / lo
+// pair makes the head products NaN.  Every violation therefore ends as a non-finite logit or value of its column, which
+// the kernel checks on the five outputs per forward (SPLIT_RANGE, tw_rollout16.hip); the host then runs the collect in f32.
 #pragma once
 #include "tw_engine16.hpp"
 
@@ -40,6 +49,7 @@ struct EngineS {
     static constexpr int NOPS   = (SP + NW - 1) / NW;
     static constexpr int SBYTES = NOPS * NW * 1024;
     static constexpr float OUT_SCALE = 1.0f / 4096.0f;       // head accumulator -> logit - bias
+    static constexpr bool SPLIT_RANGE = true;                // a non-finite output means an operand left the split's range (Range above)
     static constexpr uint32_t O_OH = 0, O_SRC = 160, O_VMAP = O_SRC + (E16_MAXP + 1) * 16, O_ACT = O_VMAP + (E16_MAXP + 1) * 256,
                               O_OHB = O_ACT + 32, O_BH = O_OHB + 2 * (E16_MAXP + 1) * 256, O_B1 = O_BH + 64, O_EBIAS = O_B1 + NHT * 128,
                               O_T0 = O_EBIAS + E16_MAX_KT * 128, O_RING = O_T0 + 2 * NC * 1024;
@@ -154,10 +164,10 @@ struct EngineS {
         else       asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
     }
     // accumulator registers (2q, 2q+1) of fragment m -> one register of the hi fragment and one of the lo fragment:
-    // u = max(x, lim); hi = f16(u); lo = f16(u - f32(hi))
+    // u = max(x, lim) (NaN stays NaN: Range above); hi = f16(u); lo = f16(u - f32(hi))
     static __device__ __forceinline__ void split_unit(const f32x16 &e, int m, int q, float lim, h16x8 &hi, h16x8 &lo)
     {
-        const f32x2 u = {__builtin_fmaxf(e[8 * m + 2 * q], lim), __builtin_fmaxf(e[8 * m + 2 * q + 1], lim)};
+        const f32x2 u = {__builtin_elementwise_maximum(e[8 * m + 2 * q], lim), __builtin_elementwise_maximum(e[8 * m + 2 * q + 1], lim)};
         const h16x2 a = __builtin_convertvector(u, h16x2);
         const f32x2 back = __builtin_convertvector(a, f32x2);
         const h16x2 b = __builtin_convertvector(u - back, h16x2);

@@ -58,6 +58,7 @@ __global__ void __launch_bounds__(256, 1) rollout_f16_kernel(const RolloutArgs a
     bool alive0 = hh ? v_oth : v_own, alive1 = hh ? v_own : v_oth;
     int      t = 0;                                        // timestep of the OWN episode (the other half keeps the other tile's)
     uint32_t len_own = 0;
+    float    out_max = 0.0f;                               // split mode: largest |logit|, |value| of the own tile, NaN once one was NaN
     uint64_t rec_base = e_own * (uint64_t)a.out.t_pad;
     bool     more = PERSIST;                               // the episode queue may still hold work
 
@@ -97,6 +98,11 @@ __global__ void __launch_bounds__(256, 1) rollout_f16_kernel(const RolloutArgs a
 #pragma unroll
         for (int i = 0; i < 4; ++i) lg[i] = (hh ? out1[i] : out0[i]) * Eng::OUT_SCALE + bh[i];
         const float value = (hh ? out1[4] : out0[4]) * Eng::OUT_SCALE + bh[4];
+        if constexpr (Eng::SPLIT_RANGE) {                  // an operand outside the split's range ends here as inf or NaN (tw_engine16x2.hpp)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) out_max = __builtin_elementwise_maximum(out_max, __builtin_fabsf(lg[i]));
+            out_max = __builtin_elementwise_maximum(out_max, __builtin_fabsf(value));
+        }
         PuzzleLane mine;
         mine.board = hh ? st1.board : st0.board; mine.zx = hh ? st1.zx : st0.zx; mine.zy = hh ? st1.zy : st0.zy;
         mine.depth = hh ? st1.depth : st0.depth;
@@ -155,6 +161,9 @@ __global__ void __launch_bounds__(256, 1) rollout_f16_kernel(const RolloutArgs a
     TW_STAMP_FLUSH(eng.lane == 0, g_stamps16, eng.st[0], eng.st[1], eng.st[2], t_kernel1 - t_kernel0,   // (slot 3: whole wave lifetime)
                    eng.st[4], eng.st[5], eng.st[6], eng.st[7]);
     if constexpr (!PERSIST) { if (v_own) a.out.ep_len[e_own] = len_own; }
+    if constexpr (Eng::SPLIT_RANGE) {                            // (vector atomic, rare: the host re-runs the collect in f32)
+        if (!(out_max <= 3.0e38f)) atomicOr(a.range_flag, 1u);
+    }
     eng.end();
 }
 

@@ -102,16 +102,18 @@ __global__ void __launch_bounds__(256) policy_sync_kernel(const SyncArgs a)
                 }
             }
             const float sx = 16.0f * v;
-            const _Float16 hi = (_Float16)sx;
-            reinterpret_cast<_Float16 *>(a.stageS)[i] = want_lo ? (_Float16)(sx - (float)hi) : hi;
+            const _Float16 hi = (_Float16)sx, term = want_lo ? (_Float16)(sx - (float)hi) : hi;
+            reinterpret_cast<_Float16 *>(a.stageS)[i] = term;
+            if (!__builtin_isfinite((float)term)) atomicOr(a.split_range, 1u);     // |x| >= 4095 or NaN: no finite pair (tw_engine16x2.hpp)
         } else {          // t0S [2*nc16 KiB]: table tile 0, hi chunks then lo chunks
             const int piece = (int)(i >> 9), l = (int)((i >> 3) & 63), jx = (int)(i & 7), hh = l >> 5, row = l & 31;
             want_lo = piece >= a.nc16;
             const int c2 = want_lo ? piece - a.nc16 : piece, val = 8 * hh + jx;
             if (c2 < a.n16 && val < a.n16) v = T(c2 * a.n16 + val, row);
             const float sx = 16.0f * v;
-            const _Float16 hi = (_Float16)sx;
-            reinterpret_cast<_Float16 *>(a.t0S)[i] = want_lo ? (_Float16)(sx - (float)hi) : hi;
+            const _Float16 hi = (_Float16)sx, term = want_lo ? (_Float16)(sx - (float)hi) : hi;
+            reinterpret_cast<_Float16 *>(a.t0S)[i] = term;
+            if (!__builtin_isfinite((float)term)) atomicOr(a.split_range, 1u);
         }
     } break;
     }
