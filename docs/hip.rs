@@ -72,6 +72,11 @@ use crate::rl::env::Env;
     twists: Option<extern "C" fn(*mut c_void, *mut i32, *mut i32, u32) -> u32>,
 }
 
+/// tw_launch_info: what tw_debug_last_launch reports (test hook): family (TW_KERNEL_*: 1 mcts_f32, 2 solve_f32, 3 mcts_deep, 4 mcts_big,
+/// 5 solve_big, 6 rollout_big), the kernel's template arguments, its grid, and the engine kernel's grid of the split shape.
+#[repr(C)] #[derive(Default)] pub struct TwLaunchInfo { family: i32, nt: i32, nc: i32, nw: i32, nwk: i32, persist: u32, solve: u32, dec: u32, split: u32,
+                                                        blocks: u32, threads: u32, engine_blocks: u32, engine_threads: u32 }
+
 // fields of the result (TW_F_*)
 const F_OBS: c_int = 0; const F_LOGITS: c_int = 1; const F_PERMS: c_int = 2; const F_VALUES: c_int = 3; const F_REWARDS: c_int = 4;
 const F_ACTIONS: c_int = 5; const F_ADVS: c_int = 6; const F_RETS: c_int = 7; const F_REMAINING: c_int = 8;
@@ -91,6 +96,10 @@ extern "C" {
     fn tw_collected_obs_width(c: *const c_void) -> u32;
     fn tw_collected_copy_to_host(c: *const c_void, field: c_int, dst: *mut c_void, bytes: usize) -> c_int;
     fn tw_collected_free(c: *mut c_void);
+    // test hooks: the kernel the last self-play / evaluate / solve call launched; (success, total, steps) of every attempt of the last
+    // evaluate / solve (attempt a of episode e at e * num_searches + a; *n attempts, up to cap copied)
+    #[allow(dead_code)] fn tw_debug_last_launch(out: *mut TwLaunchInfo) -> c_int;
+    #[allow(dead_code)] fn tw_debug_last_attempts(success: *mut f32, total: *mut f32, n_steps: *mut u32, cap: u64, n: *mut u64) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {

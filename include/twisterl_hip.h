@@ -96,6 +96,30 @@ enum {
 int tw_set_launch_option(int option, int value);
 /* Diagnostic counters of the last self-play launch of this process (MctsArgs::eval_count[0..15]); test hook. */
 int tw_debug_counters(uint64_t *out, int n);
+/* Test hook: the kernel the last tw_az_collect / tw_evaluate / tw_solve / big-board tw_ppo_collect of this process launched, as its
+ * launcher reports it from its own template parameters (family 0: the call launched none of these kernels).  The arguments a family
+ * does not have are 0; the split shape of the walker kernel also reports the grid of its mcts_engine_kernel<nt, nc>. */
+enum {
+    TW_KERNEL_NONE = 0,
+    TW_KERNEL_MCTS_F32 = 1,     /* mcts_f32_kernel<nt, nc, nw, PERSIST>                          */
+    TW_KERNEL_SOLVE_F32 = 2,    /* solve_f32_kernel<nt, nc, nw>                                  */
+    TW_KERNEL_MCTS_DEEP = 3,    /* mcts_deep_kernel<nt, nc, nw, nwk, SOLVE, DEC, SPL>            */
+    TW_KERNEL_MCTS_BIG = 4,     /* mcts_big_kernel<nc>                                           */
+    TW_KERNEL_SOLVE_BIG = 5,    /* solve_big_kernel<nc>                                          */
+    TW_KERNEL_ROLLOUT_BIG = 6   /* rollout_big_kernel<nc>                                        */
+};
+typedef struct {
+    int32_t  family;            /* TW_KERNEL_*                                                   */
+    int32_t  nt, nc, nw, nwk;   /* template arguments                                            */
+    uint32_t persist, solve, dec, split;   /* the boolean template arguments (0 / 1)            */
+    uint32_t blocks, threads;   /* the kernel's grid                                             */
+    uint32_t engine_blocks, engine_threads;   /* split shape: the grid of mcts_engine_kernel    */
+} tw_launch_info;
+int tw_debug_last_launch(tw_launch_info *out);
+/* Test hook: (success, total reward, steps) of every attempt of the last tw_evaluate / tw_solve of this process that ran on the
+ * device, attempt a of episode e at index e * num_searches + a -- what the best-of-num_searches reduction and the two means are
+ * taken from.  *n: the number of attempts; up to cap of them are copied to each array that is not NULL. */
+int tw_debug_last_attempts(float *success, float *total, uint32_t *n_steps, uint64_t cap, uint64_t *n);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Env: host object with the PyBaseEnv / Puzzle surface.  Collectors only read its          */

@@ -473,6 +473,33 @@ def evaluate(env: Puzzle, policy: Policy, num_episodes, deterministic, num_searc
     return float(s.value), float(r.value)
 
 
+def evaluate_attempts(env: Puzzle, policy: Policy, num_episodes, deterministic, num_searches, num_mcts_searches=0, seed=0, Cc=1.41,
+                      max_expand_depth=1, arith=ARITH_REF, det_math=False, num_threads=1, from_state=False):
+    """Every attempt of evaluate() on its own -> (success, total, n_steps), attempt a of episode e at e * num_searches + a.
+    from_state: the attempts of solve(env, ..., episode=0) from the env's current state (num_episodes = 1)."""
+    prm = _SolveParams(int(deterministic), num_searches, num_mcts_searches, Cc, max_expand_depth, seed, arith, int(det_math))
+    n = num_episodes * num_searches
+    s, r, k = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+    lib().two_evaluate_attempts(C.byref(env.p), C.byref(policy.pol), C.byref(prm), C.c_uint64(num_episodes), C.c_int(int(from_state)), C.c_int(num_threads),
+                                _fp(s), _fp(r), k.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return s, r, k
+
+
+def reduce_attempts(success, total, num_episodes, num_searches):
+    """evaluate()'s reduction of per-attempt results: best of num_searches by (success, total) with a strict `>` (solve.rs:84-98), then
+    the two means accumulated serially in f32, episode order (evaluate.rs:36-52) -> (success_rate, mean_reward, best attempt of each episode)."""
+    f = np.float32
+    succ, rew, best = f(0.0), f(0.0), np.full(num_episodes, -1, np.int64)
+    for e in range(num_episodes):
+        bs, br = f(0.0), f(-np.inf)
+        for a in range(num_searches):
+            i = e * num_searches + a
+            if success[i] > bs or (success[i] == bs and total[i] > br):
+                bs, br, best[e] = success[i], total[i], i
+        succ, rew = f(succ + bs), f(rew + br)
+    return float(f(succ / f(num_episodes))), float(f(rew / f(num_episodes))), best
+
+
 def replay(env: Puzzle, actions):
     n = len(actions)
     nc = env.n_cells

@@ -991,6 +991,52 @@ void two_evaluate(const two_puzzle *env, const two_policy *pol, const two_solve_
     *mean_reward_out = rewards / (float)num_episodes;
 }
 
+/* Every attempt of two_evaluate on its own: (success, total, steps) of attempt a of episode e at e * num_searches + a, what two_solve
+ * reduces best-of-num_searches from (attempts are independent of each other: the RNG is keyed by the attempt).  from_state: the attempts
+ * of ONE two_solve(env, .., episode 0) from the env's current state instead (num_episodes = 1).  num_threads workers. */
+typedef struct {
+    const two_puzzle *env; const two_policy *pol; const two_solve_params *prm; uint64_t n_attempts;
+    float *success, *total; uint32_t *n_steps; atomic_ullong next; int from_state;
+} attempts_job;
+
+static void *attempts_worker(void *arg)
+{
+    attempts_job *job = (attempts_job *)arg;
+    g_det_exp = job->prm->det_math;
+    const int64_t reset_depth = job->env->depth_slope * job->env->difficulty;
+    int64_t *tmp = (int64_t *)malloc(sizeof(int64_t) * (size_t)((job->env->depth > reset_depth ? job->env->depth : reset_depth) + 2));
+    for (;;) {
+        unsigned long long i = atomic_fetch_add(&job->next, 1ULL);
+        if (i >= job->n_attempts) break;
+        two_puzzle p = *job->env;
+        if (!job->from_state) two_puzzle_reset(&p, job->prm->seed, i / job->prm->num_searches);        /* evaluate.rs:39 */
+        float s, r;
+        int n = single_solve(&p, job->pol, job->prm, i, &s, &r, tmp);
+        job->success[i] = s; job->total[i] = r; job->n_steps[i] = (uint32_t)n;
+    }
+    free(tmp);
+    return NULL;
+}
+
+void two_evaluate_attempts(const two_puzzle *env, const two_policy *pol, const two_solve_params *prm, uint64_t num_episodes,
+                           int from_state, int num_threads, float *success_out, float *total_out, uint32_t *n_steps_out)
+{
+    const int saved = g_det_exp;
+    attempts_job job; job.env = env; job.pol = pol; job.prm = prm; job.n_attempts = num_episodes * (uint64_t)prm->num_searches;
+    job.success = success_out; job.total = total_out; job.n_steps = n_steps_out; job.from_state = from_state;
+    atomic_init(&job.next, 0ULL);
+    int nt = num_threads < 1 ? 1 : num_threads;
+    if (nt == 1) {
+        attempts_worker(&job);
+    } else {
+        pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nt);
+        for (int i = 0; i < nt; ++i) pthread_create(&th[i], NULL, attempts_worker, &job);
+        for (int i = 0; i < nt; ++i) pthread_join(th[i], NULL);
+        free(th);
+    }
+    g_det_exp = saved;
+}
+
 /* ===================================================================================== */
 /* replay helper for replay-parity tests                                                 */
 /* ===================================================================================== */

@@ -205,6 +205,11 @@ int two_solve(const two_puzzle *env, const two_policy *pol, const two_solve_para
 void two_evaluate(const two_puzzle *env, const two_policy *pol, const two_solve_params *prm, uint64_t num_episodes,
                   float *success_rate_out, float *mean_reward_out);
 
+/* every attempt of two_evaluate (from_state: of one two_solve from the env's state, episode 0) on its own: attempt a of episode e at
+ * e * num_searches + a */
+void two_evaluate_attempts(const two_puzzle *env, const two_policy *pol, const two_solve_params *prm, uint64_t num_episodes,
+                           int from_state, int num_threads, float *success_out, float *total_out, uint32_t *n_steps_out);
+
 /* replay: apply `actions` from `start` (set_state semantics for depth unless depth0>=0),
  * recording for each of the n+1 visited states obs ids, masks, reward, is_final, board. */
 void two_replay(const two_puzzle *start, const int64_t *actions, size_t n,

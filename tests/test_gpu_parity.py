@@ -966,8 +966,16 @@ def test_mcts_guided_evaluate_on_the_walker_kernel(tw, oracle):
         genv, oenv = tw.env.Puzzle(3, 3, diff, 2, 256), oracle.Puzzle(3, 3, diff, 2, 256)
         kw = dict(num_episodes=n_ep, deterministic=det, num_searches=ns, num_mcts_searches=S, seed=3, C=1.41, max_expand_depth=med, num_cores=32)
         g = tw.collector.evaluate(genv, gp, **kw)
+        # (what ran, from the launcher itself: the walker kernel in its solve mode up to 8 attempts per CU at these few searches -- the last
+        #  case, 15 attempts per CU, is the lane-per-episode kernel's either way)
+        ran = _lib.debug_last_launch()
+        if n_ep * ns <= 8 * cus:
+            assert (ran["family"], ran["nw"], ran["solve"], ran["nwk"]) == (_lib.TW_KERNEL_MCTS_DEEP, -17, 1, 1 if n_ep * ns <= 2 * cus else 2 if 2 * n_ep * ns <= 9 * cus else 4), ran
+        else:
+            assert ran["family"] == _lib.TW_KERNEL_MCTS_F32, ran
         with _lib.launch_option(_lib.TW_OPT_AZ_VARIANT, 2):
             l = tw.collector.evaluate(genv, gp, **kw)
+        assert _lib.debug_last_launch()["family"] == _lib.TW_KERNEL_MCTS_F32
         assert f32_bits(g[0]) == f32_bits(l[0]) and f32_bits(g[1]) == f32_bits(l[1]), (diff, n_ep, g, l)
         if n_ep <= 2 * cus + 5:
             o = oracle.evaluate(oenv, op, n_ep, det, ns, num_mcts_searches=S, seed=3, Cc=1.41, max_expand_depth=med, arith=oracle.ARITH_CHAIN, det_math=True)

@@ -77,6 +77,16 @@ class CollectStats(C.Structure):
                 ("rollout_threads", C.c_uint32), ("forward_evals", C.c_uint64), ("speculative_evals", C.c_uint64), ("reused_evals", C.c_uint64)]
 
 
+class LaunchInfo(C.Structure):
+    _fields_ = [("family", C.c_int32), ("nt", C.c_int32), ("nc", C.c_int32), ("nw", C.c_int32), ("nwk", C.c_int32),
+                ("persist", C.c_uint32), ("solve", C.c_uint32), ("dec", C.c_uint32), ("split", C.c_uint32),
+                ("blocks", C.c_uint32), ("threads", C.c_uint32), ("engine_blocks", C.c_uint32), ("engine_threads", C.c_uint32)]
+
+
+(TW_KERNEL_NONE, TW_KERNEL_MCTS_F32, TW_KERNEL_SOLVE_F32, TW_KERNEL_MCTS_DEEP, TW_KERNEL_MCTS_BIG, TW_KERNEL_SOLVE_BIG,
+ TW_KERNEL_ROLLOUT_BIG) = range(7)
+
+
 class EnvVTable(C.Structure):
     _fields_ = [("prototype", C.c_void_p), ("num_actions", C.c_uint32), ("n_obs", C.c_uint32), ("obs_size", C.c_uint32),
                 ("clone", C.CFUNCTYPE(C.c_void_p, C.c_void_p)), ("destroy", C.CFUNCTYPE(None, C.c_void_p)),
@@ -107,6 +117,8 @@ SYMBOLS = {
     "tw_release_cached_memory": (C.c_int, []),
     "tw_set_launch_option": (C.c_int, [C.c_int, C.c_int]),
     "tw_debug_counters": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
+    "tw_debug_last_launch": (C.c_int, [C.POINTER(LaunchInfo)]),
+    "tw_debug_last_attempts": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]),
     "tw_debug_episode_order": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "tw_puzzle_create": (_VP, [C.c_uint32] * 5),
     "tw_puzzle_clone": (_VP, [_VP]),
@@ -252,6 +264,26 @@ def debug_counters(n: int = 16) -> list:
     buf = (C.c_uint64 * n)()
     check(lib().tw_debug_counters(buf, n))
     return [int(x) for x in buf]
+
+
+def debug_last_launch() -> dict:
+    """The kernel the last self-play / evaluate / solve / big-board PPO call of this process launched, as its launcher reported it
+    (tw_debug_last_launch; test hook): family (TW_KERNEL_*), template arguments, grid, and the engine kernel's grid of the split shape."""
+    info = LaunchInfo()
+    check(lib().tw_debug_last_launch(C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in LaunchInfo._fields_}
+
+
+def debug_last_attempts():
+    """(success, total, n_steps) of every attempt of the last evaluate / solve that ran on the device, attempt a of episode e at
+    e * num_searches + a (tw_debug_last_attempts; test hook)."""
+    import numpy as np
+    n = C.c_uint64()
+    check(lib().tw_debug_last_attempts(None, None, None, 0, C.byref(n)))
+    s, t, k = np.zeros(n.value, np.float32), np.zeros(n.value, np.float32), np.zeros(n.value, np.uint32)
+    check(lib().tw_debug_last_attempts(s.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_float)),
+                                       k.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)))
+    return s, t, k
 
 
 def debug_episode_order(desc, seed: int, episode_offset: int, n: int):

@@ -271,6 +271,45 @@ extern "C" int tw_debug_counters(uint64_t *out, int n)
     return TW_OK;
 }
 
+// tw_debug_last_launch / tw_debug_last_attempts (test hooks): what the last self-play / evaluate / solve call launched and returned per attempt
+static tw_launch_info g_last_launch;
+static std::vector<float> g_att_success, g_att_total;
+static std::vector<uint32_t> g_att_steps;
+namespace tw {
+void note_launch(int family, int nt, int nc, int nw, int nwk, bool persist, bool solve, bool dec, bool split, uint32_t blocks, uint32_t threads,
+                 uint32_t engine_blocks, uint32_t engine_threads)
+{
+    std::lock_guard<std::mutex> lock(g_dbg_mutex);
+    g_last_launch = tw_launch_info{family, nt, nc, nw, nwk, persist, solve, dec, split, blocks, threads, engine_blocks, engine_threads};
+}
+}  // namespace tw
+static void forget_last_launch()
+{
+    std::lock_guard<std::mutex> lock(g_dbg_mutex);
+    g_last_launch = tw_launch_info{};
+    g_att_success.clear(); g_att_total.clear(); g_att_steps.clear();
+}
+
+extern "C" int tw_debug_last_launch(tw_launch_info *out)
+{
+    if (!out) { set_error("tw_debug_last_launch: null argument"); return TW_ERR_INVALID; }
+    std::lock_guard<std::mutex> lock(g_dbg_mutex);
+    *out = g_last_launch;
+    return TW_OK;
+}
+
+extern "C" int tw_debug_last_attempts(float *success, float *total, uint32_t *n_steps, uint64_t cap, uint64_t *n)
+{
+    if (!n) { set_error("tw_debug_last_attempts: null argument"); return TW_ERR_INVALID; }
+    std::lock_guard<std::mutex> lock(g_dbg_mutex);
+    *n = g_att_success.size();
+    const size_t m = (size_t)(cap < *n ? cap : *n);
+    if (success && m) memcpy(success, g_att_success.data(), m * sizeof(float));
+    if (total && m) memcpy(total, g_att_total.data(), m * sizeof(float));
+    if (n_steps && m) memcpy(n_steps, g_att_steps.data(), m * sizeof(uint32_t));
+    return TW_OK;
+}
+
 extern "C" int tw_release_cached_memory(void)
 {
     {
@@ -1281,6 +1320,7 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
         }
     }
     TW_HIP(hipEventRecord(ev.ev[0], s));
+    if (big) forget_last_launch();         // (tw_debug_last_launch: launch_rollout_big reports itself)
     rc = big                               ? launch_rollout_big(ra, reinterpret_cast<uint16_t *>(ws + o_obs16), s, &st.rollout_blocks, &st.rollout_threads)
          : prm->precision == TW_PREC_F16   ? launch_rollout_f16(ra, s, &st.rollout_blocks, &st.rollout_threads)
          : prm->precision == TW_PREC_F16X2 ? launch_rollout_f16x2(ra, s, &st.rollout_blocks, &st.rollout_threads)
@@ -1354,6 +1394,7 @@ static int az_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, c
 extern "C" int tw_az_collect(const tw_puzzle_desc *env, const tw_policy *policy, const tw_az_params *prm, tw_collected **out)
 {
     bool split_watchdog = false;
+    forget_last_launch();
     int rc = az_collect_once(env, policy, prm, out, &split_watchdog);
     if (rc != TW_OK && split_watchdog) {
         fprintf(stderr, "[twisterl_hip] self-play: the split shape's kernels did not run side by side (a profiler that serialises kernels? a shared GPU?): "
@@ -1660,6 +1701,10 @@ int run_solve(const PuzzleConsts &envc, const tw_policy *policy, const tw_solve_
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
     if (rc != TW_OK || e != hipSuccess) { (void)hipFree(buf); return rc != TW_OK ? rc : hip_fail(e, "solve readback", __FILE__, __LINE__); }
+    {   // tw_debug_last_attempts
+        std::lock_guard<std::mutex> dl(g_dbg_mutex);
+        g_att_success = hs; g_att_total = hr; g_att_steps = hn;
+    }
     best_s.assign(n_episodes, 0.0f); best_r.assign(n_episodes, -__builtin_inff());
     std::vector<uint64_t> best_att(n_episodes, (uint64_t)-1);
     for (uint64_t ep = 0; ep < n_episodes; ++ep)
@@ -1683,6 +1728,7 @@ extern "C" int tw_evaluate(const tw_puzzle_desc *env, const tw_policy *policy, c
                            uint64_t num_episodes, uint64_t episode_offset, float *success_rate, float *mean_reward)
 {
     if (!env || !policy || !prm || !success_rate || !mean_reward) { set_error("tw_evaluate: null argument"); return TW_ERR_INVALID; }
+    forget_last_launch();
     int rc = require_device(); if (rc) return rc;
     // boards of 17 .. 64 cells: on the device (solve_big_kernel; MCTS-guided: mcts_big_kernel); whatever they do not take: the any-environment path (host env)
     const uint64_t cells = (uint64_t)env->width * env->height;
@@ -1714,6 +1760,7 @@ extern "C" int tw_solve(const tw_puzzle *env, const tw_policy *policy, const tw_
                         float *reward, uint8_t *actions_out, uint32_t actions_cap, uint32_t *n_actions)
 {
     if (!env || !policy || !prm || !success || !reward) { set_error("tw_solve: null argument"); return TW_ERR_INVALID; }
+    forget_last_launch();
     int rc = require_device(); if (rc) return rc;
     // boards of 17 .. 64 cells: on the device too (solve_big_kernel / mcts_big_kernel); whatever they do not take: the any-environment path (host env)
     bool big_dev = env->state.size() > 16 && env->state.size() <= 64 && policy->dev.generic && prm->precision == TW_PREC_F32_EXACT &&

@@ -119,6 +119,10 @@ LaunchOptions launch_options();
 int ensure_dynamic_lds(const void *kernel, size_t bytes);
 // Compute units of the current device (cached per device).
 int device_cus();
+// Test hook (tw_debug_last_launch): the launchers of the self-play / evaluate / solve / big-board kernels report what they launched,
+// from their own template parameters (one host-side store per launch).
+void note_launch(int family, int nt, int nc, int nw, int nwk, bool persist, bool solve, bool dec, bool split, uint32_t blocks, uint32_t threads,
+                 uint32_t engine_blocks = 0, uint32_t engine_threads = 0);
 
 // ---- RNG streams (see DESIGN.md "RNG spec") -------------------------------------------------
 enum : uint32_t {

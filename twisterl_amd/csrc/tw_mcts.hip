@@ -497,6 +497,7 @@ static int launch_mcts_geom(const MctsArgs &a, hipStream_t s, uint32_t *blocks, 
     });
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = 64 * G::WAVES;
+    note_launch(TW_KERNEL_MCTS_F32, NT, NC, NW, 0, PERSIST, false, false, false, (uint32_t)nb, 64 * G::WAVES);
     return TW_OK;
 }
 

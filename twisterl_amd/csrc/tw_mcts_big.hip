@@ -328,6 +328,7 @@ static int launch_mcts_big_nc(const MctsArgs &a, uint16_t *obs16, hipStream_t s,
     TW_HIP(hipGetLastError());
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = Eng::THREADS;
+    note_launch(TW_KERNEL_MCTS_BIG, 0, NC, 0, 0, false, false, false, false, (uint32_t)nb, Eng::THREADS);
     return TW_OK;
 }
 

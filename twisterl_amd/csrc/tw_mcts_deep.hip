@@ -1321,6 +1321,7 @@ static int launch_deep_split(const MctsArgs &a, const DeepShape &sh, hipStream_t
     });
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = 64 * NWK;
+    note_launch(TW_KERNEL_MCTS_DEEP, NT, NC, -16, NWK, false, false, true, true, (uint32_t)nb, 64 * NWK, (uint32_t)ne, 256);
     return TW_OK;
 }
 
@@ -1363,6 +1364,7 @@ static int launch_deep_nwk(const MctsArgs &a, hipStream_t s, uint32_t *blocks, u
     });
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = THREADS;
+    note_launch(TW_KERNEL_MCTS_DEEP, NT, NC, NW, NWK, false, SOLVE, DEC, false, (uint32_t)nb, THREADS);
     return TW_OK;
 }
 
@@ -1375,25 +1377,25 @@ static int launch_deep_geom(const MctsArgs &a, hipStream_t s, uint32_t *blocks, 
             case 2: return launch_deep_nwk<NT, NC, NW, 2, true>(a, s, blocks, threads);
             default: return launch_deep_nwk<NT, NC, NW, 4, true>(a, s, blocks, threads);
         }
-    }
-    const DeepShape sh = deep_shape(a.num_episodes, a.reserve_cus, a.num_searches);
-    if constexpr (NW == -16) {      // the decoupled shapes exist on the 16-column engine
-        if (sh.split) switch (sh.walkers) {
-            case 8:  return launch_deep_split<NT, NC, 8>(a, sh, s, blocks, threads);
-            case 12: return launch_deep_split<NT, NC, 12>(a, sh, s, blocks, threads);
-            default: return launch_deep_split<NT, NC, 16>(a, sh, s, blocks, threads);
+    } else {                         // (an `else`: the self-play shapes below are not instantiated for the solve-mode engine)
+        const DeepShape sh = deep_shape(a.num_episodes, a.reserve_cus, a.num_searches);
+        if constexpr (NW == -16) {      // the decoupled shapes exist on the 16-column engine
+            if (sh.split) switch (sh.walkers) {      // (split_walkers_per_group(): twelve or sixteen)
+                case 12: return launch_deep_split<NT, NC, 12>(a, sh, s, blocks, threads);
+                default: return launch_deep_split<NT, NC, 16>(a, sh, s, blocks, threads);
+            }
+            if (sh.dec) switch (sh.walkers) {
+                case 2: return launch_deep_nwk<NT, NC, NW, 2, false, true>(a, s, blocks, threads);
+                case 8: return launch_deep_nwk<NT, NC, NW, 8, false, true>(a, s, blocks, threads);
+                default: return launch_deep_nwk<NT, NC, NW, 4, false, true>(a, s, blocks, threads);
+            }
         }
-        if (sh.dec) switch (sh.walkers) {
-            case 2: return launch_deep_nwk<NT, NC, NW, 2, false, true>(a, s, blocks, threads);
-            case 8: return launch_deep_nwk<NT, NC, NW, 8, false, true>(a, s, blocks, threads);
-            default: return launch_deep_nwk<NT, NC, NW, 4, false, true>(a, s, blocks, threads);
+        switch (sh.walkers) {
+            case 1: return launch_deep_nwk<NT, NC, NW, 1>(a, s, blocks, threads);
+            case 2: return launch_deep_nwk<NT, NC, NW, 2>(a, s, blocks, threads);
+            case 8: return launch_deep_nwk<NT, NC, NW, 8>(a, s, blocks, threads);
+            default: return launch_deep_nwk<NT, NC, NW, 4>(a, s, blocks, threads);
         }
-    }
-    switch (sh.walkers) {
-        case 1: return launch_deep_nwk<NT, NC, NW, 1>(a, s, blocks, threads);
-        case 2: return launch_deep_nwk<NT, NC, NW, 2>(a, s, blocks, threads);
-        case 8: return launch_deep_nwk<NT, NC, NW, 8>(a, s, blocks, threads);
-        default: return launch_deep_nwk<NT, NC, NW, 4>(a, s, blocks, threads);
     }
 }
 

@@ -180,6 +180,7 @@ static int launch_solve_big_nc(const SolveArgs &a, hipStream_t s)
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&solve_big_kernel<NC>), lds_bytes)) return rc;
     hipLaunchKernelGGL((solve_big_kernel<NC>), dim3((unsigned)nb), dim3(Eng::THREADS), lds_bytes, s, a);
     TW_HIP(hipGetLastError());
+    note_launch(TW_KERNEL_SOLVE_BIG, 0, NC, 0, 0, false, false, false, false, (uint32_t)nb, Eng::THREADS);
     return TW_OK;
 }
 
@@ -222,6 +223,7 @@ static int launch_rollout_big_nc(const RolloutArgs &a, uint16_t *obs16, hipStrea
     TW_HIP(hipGetLastError());
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = Eng::THREADS;
+    note_launch(TW_KERNEL_ROLLOUT_BIG, 0, NC, 0, 0, false, false, false, false, (uint32_t)nb, Eng::THREADS);
     return TW_OK;
 }
 

@@ -91,6 +91,7 @@ static int launch_solve_geom(const SolveArgs &a, hipStream_t s)
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&solve_f32_kernel<NT, NC, NW>), lds_bytes)) return rc;
     hipLaunchKernelGGL((solve_f32_kernel<NT, NC, NW>), dim3((unsigned)nb), dim3(64 * G::WAVES), lds_bytes, s, a);
     TW_HIP(hipGetLastError());
+    note_launch(TW_KERNEL_SOLVE_F32, NT, NC, NW, 0, false, false, false, false, (uint32_t)nb, 64 * G::WAVES);
     return TW_OK;
 }
 
