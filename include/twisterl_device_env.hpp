@@ -33,6 +33,8 @@
 // memory, no globals, no virtual functions.  An id outside [0, obs_size()) fails the collect ("index out of bounds: obs id ..."), an
 // episode that has not ended within the collect's max_records_per_episode records fails it too -- as on the host-stepped path.  A
 // collect whose max_records_per_episode is above 1,820 (what the finalize step's LDS tile holds) runs on the host-stepped path.
+// A struct that holds instances of several sizes may add `int n_obs() const`, 1..N_OBS and CONSTANT for the object's lifetime (the
+// library reads it once, from the prototype): observe() then writes that many ids.
 #pragma once
 
 #include "twisterl_hip.h"
@@ -61,7 +63,7 @@ struct DeviceEnvModule {
     {
         int ids[NO];
         static_cast<const T *>(e)->observe(ids);
-        for (int i = 0; i < NO; ++i) out[i] = (int32_t)ids[i];
+        for (int i = 0, n = n_obs_of(e); i < n; ++i) out[i] = (int32_t)ids[i];
     }
     static void masks(void *e, uint8_t *out)
     {
@@ -81,6 +83,7 @@ struct DeviceEnvModule {
     static int get_difficulty(const void *e) { return static_cast<const T *>(e)->difficulty(); }
     static void set_difficulty(void *e, int d) { static_cast<T *>(e)->set_difficulty(d); }
     static int obs_size(const void *e) { return static_cast<const T *>(e)->obs_size(); }
+    static int n_obs_of(const void *e) { return env_n_obs(*static_cast<const T *>(e)); }
     static void fill_vtable(tw_env_vtable *v)
     {
         *v = tw_env_vtable{};
@@ -97,7 +100,7 @@ struct DeviceEnvModule {
             x.num_actions = (uint32_t)A; x.n_obs = (uint32_t)NO; x.state_bytes = (uint32_t)sizeof(T); x.engine_nc = (uint32_t)env_engine_nc(NO);
             x.type_name = type_name;
             x.launch_rollout = launch_rollout_env<T>; x.launch_solve = launch_solve_env<T>;
-            x.create = create; x.get_difficulty = get_difficulty; x.set_difficulty = set_difficulty; x.obs_size = obs_size;
+            x.create = create; x.get_difficulty = get_difficulty; x.set_difficulty = set_difficulty; x.obs_size = obs_size; x.n_obs_of = n_obs_of;
             x.fill_vtable = fill_vtable;
             return x;
         }();

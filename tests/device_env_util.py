@@ -1,11 +1,12 @@
-"""Helpers of the device-environment tests: the two test modules (examples/device_env/gridworld.hpp, tests/device_envs/ring.hpp) and
-a wrapper that gives a module's host functions the oracle's Python env protocol."""
+"""Helpers of the device-environment tests: the test modules (examples/device_env/gridworld.hpp, tests/device_envs/ring.hpp,
+tests/device_envs/big_puzzle.hpp) and a wrapper that gives a module's host functions the oracle's Python env protocol."""
 import ctypes as C
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRIDWORLD_HPP = os.path.join(ROOT, "examples", "device_env", "gridworld.hpp")
 RING_HPP = os.path.join(ROOT, "tests", "device_envs", "ring.hpp")
+BIG_PUZZLE_HPP = os.path.join(ROOT, "tests", "device_envs", "big_puzzle.hpp")
 GRIDWORLD_FIELDS = ("max_steps", "diff", "ax", "ay", "gx", "gy", "tx", "ty", "steps_left")     # struct GridWorld, int32 each
 
 
@@ -19,6 +20,11 @@ def build_ring():
     return build_device_env(RING_HPP, "RingWalk", "ring")
 
 
+def build_big_puzzle():
+    from twisterl_amd.build import build_device_env
+    return build_device_env(BIG_PUZZLE_HPP, "BigPuzzle25", "big_puzzle25")
+
+
 def gridworld(size=5, max_steps=64, difficulty=1, **kw):
     from twisterl_amd.env import DeviceEnv
     return DeviceEnv(build_gridworld(size), f"gridworld{size}x{size}", [size, size, max_steps, difficulty], **kw)
@@ -27,6 +33,12 @@ def gridworld(size=5, max_steps=64, difficulty=1, **kw):
 def ring(n=32, max_steps=40, difficulty=3, noise=0.2, bad_at=-1, **kw):
     from twisterl_amd.env import DeviceEnv
     return DeviceEnv(build_ring(), "ring", [n, max_steps, difficulty, noise, bad_at], **kw)
+
+
+def big_puzzle(width, height, difficulty, depth_slope, max_depth, **kw):
+    """tw::BigPuzzleEnv<25> (boards of up to 25 cells) with Puzzle::new's parameters."""
+    from twisterl_amd.env import DeviceEnv
+    return DeviceEnv(build_big_puzzle(), "big_puzzle25", [width, height, difficulty, depth_slope, max_depth], **kw)
 
 
 class HostEnv:

@@ -1,7 +1,7 @@
 """CPU: user-written device environments (include/twisterl_device_env.hpp) -- the modules build for gfx950 with the library's flags,
 their kernels are hazard-free and scratch-free, the contract's violations fail to compile with its messages, the descriptor and the
-host vtable are right, the C++ GridWorld's host side is the reference's GridWorld transition by transition, and without a GPU the
-collectors fail loudly."""
+host vtable are right, the C++ GridWorld's host side is the reference's GridWorld transition by transition, the big-board
+Puzzle as a device-environment struct (BigPuzzleEnv) collects what the oracle's Puzzle collects, and without a GPU the collectors fail loudly."""
 import ctypes as C
 import os
 import random
@@ -12,7 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.device_env_util import GRIDWORLD_FIELDS, build_gridworld, build_ring, gridworld, ring
+from tests.device_env_util import GRIDWORLD_FIELDS, HostEnv, big_puzzle, build_gridworld, build_ring, gridworld, ring
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -165,6 +165,30 @@ def test_gridworld_reset_places_as_the_reference():
         assert len(seen) == 25
     env.difficulty = 99
     assert env.difficulty == 10                                            # min(width + height, d) (lib.rs: set_difficulty)
+
+
+@pytest.mark.parametrize("w,h", [(5, 5), (6, 4)])
+def test_big_puzzle_struct_collects_what_the_oracle_puzzle_collects(oracle, w, h):
+    """BigPuzzleEnv<25> -- the functions rollout_big_kernel calls, as a device-environment struct -- built as a module: the oracle's any-environment
+    collector over its host vtable against the oracle's own Puzzle collect, every field bit for bit.  6 x 4 runs in the same class
+    of 25 with 24 ids per observation (the struct's n_obs())."""
+    from tests.util import f32_bits, make_deep_policy_arrays, oracle_policy, puzzle_transpose_twist
+    D, E, seed = 5, 40, 17
+    env = big_puzzle(w, h, D, 2, 256)
+    assert (env.n_obs, env.obs_size, env.num_actions(), env.difficulty) == (w * h, (w * h) ** 2, 4, D)
+    twists = puzzle_transpose_twist(w) if w == h else ((), ())
+    op = oracle_policy(oracle, make_deep_policy_arrays(w * h, seed=6, emb=32, common=(64, 32), scale=2.0), *twists)
+    want = oracle.ppo_collect(oracle.Puzzle(w, h, D, 2, 256), op, E, 0.995, 0.995, seed=seed, arith=oracle.ARITH_CHAIN, det_log=True)
+    got = oracle.ppo_collect_env(HostEnv(env), op, E, 0.995, 0.995, seed=seed, difficulty=D)
+    assert got.obs.shape == want.obs.shape == (len(want.values), w * h) and len(want.values) > E
+    for k in ("obs", "actions", "perms", "ep_len"):
+        assert np.array_equal(getattr(got, k), getattr(want, k)), k
+    for k in ("logits", "values", "rewards"):
+        assert np.array_equal(f32_bits(getattr(got, k)), f32_bits(getattr(want, k))), k
+    for k in ("advs", "rets"):
+        assert np.array_equal(f32_bits(got.additional_data[k]), f32_bits(want.additional_data[k])), k
+    if w == h:
+        assert set(np.unique(want.perms).tolist()) == {0, 1}
 
 
 def test_device_env_python_surface():

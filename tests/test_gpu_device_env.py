@@ -7,7 +7,7 @@ import signal
 import numpy as np
 import pytest
 
-from tests.device_env_util import HostEnv, gridworld, ring
+from tests.device_env_util import HostEnv, big_puzzle, gridworld, ring
 from tests.util import amd_policy, f32_bits, make_deep_policy_arrays, oracle_policy
 
 pytestmark = pytest.mark.gpu
@@ -151,6 +151,29 @@ def test_evaluate_equals_the_oracle(tw, oracle):
                 assert f32_bits(ge[0]) == f32_bits(oe[0]) and f32_bits(ge[1]) == f32_bits(oe[1]), (det, ns, ge, oe)
     finally:
         oracle.set_det_exp(False)
+
+
+def test_big_puzzle_module_gives_the_bytes_of_the_library_puzzle(tw):
+    """One Puzzle, two pairs of kernels: tw.env.Puzzle of a 5 x 5 board runs in rollout_big_kernel / solve_big_kernel, the same
+    step / masks / reward / is_final as the struct BigPuzzleEnv<25>, built as a module, in rollout_env_kernel / solve_env_kernel --
+    the same bytes from both.  40 episodes are two and a half workgroups."""
+    from tests.util import puzzle_transpose_twist
+    D = 5
+    gp = amd_policy(make_deep_policy_arrays(25, seed=7, emb=64, common=(64, 32), scale=2.0), *puzzle_transpose_twist(5))
+    lib_env, mod_env = tw.env.Puzzle(5, 5, D, 2, 256), big_puzzle(5, 5, D, 2, 256, max_records=2 * D + 1)
+    for merge_order in (True, False):
+        a = tw.collector.PPOCollector(40, 0.995, 0.995, 4, merge_order=merge_order).collect(lib_env, gp, seed=23)
+        b = tw.collector.PPOCollector(40, 0.995, 0.995, 4, merge_order=merge_order).collect(mod_env, gp, seed=23)
+        assert a.stats["rollout_blocks"] == b.stats["rollout_blocks"] == 3 and a.stats["rollout_threads"] == b.stats["rollout_threads"] == 256
+        _same_bytes(a, b)
+        x = a.to_numpy()
+        assert sorted(x) == sorted(FIELDS) and x["obs"].dtype == np.uint16 and x["obs"].shape[1] == 25 and set(np.unique(x["perms"]).tolist()) == {0, 1}
+    for det, ns in ((True, 1), (False, 2)):
+        ea = tw.collector.evaluate(lib_env, gp, num_episodes=200, deterministic=det, num_searches=ns, num_mcts_searches=0, seed=5, C=1.41,
+                                   max_expand_depth=1, num_cores=4)
+        eb = tw.collector.evaluate(mod_env, gp, num_episodes=200, deterministic=det, num_searches=ns, num_mcts_searches=0, seed=5, C=1.41,
+                                   max_expand_depth=1, num_cores=4)
+        assert f32_bits(ea[0]) == f32_bits(eb[0]) and f32_bits(ea[1]) == f32_bits(eb[1]), (det, ns, ea, eb)
 
 
 def test_shapes_the_kernel_does_not_take_run_on_the_host(tw, oracle):

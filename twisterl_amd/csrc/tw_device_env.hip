@@ -58,7 +58,7 @@ int check_descriptor(const tw_device_env *d, const void *proto, size_t proto_byt
                   mine[0], mine[1], mine[2], mine[3], mine[4], mine[5], mine[6], mine[7]);
         return TW_ERR_INVALID;
     }
-    if (!d->launch_rollout || !d->launch_solve || !d->create || !d->get_difficulty || !d->set_difficulty || !d->obs_size || !d->fill_vtable) {
+    if (!d->launch_rollout || !d->launch_solve || !d->create || !d->get_difficulty || !d->set_difficulty || !d->obs_size || !d->n_obs_of || !d->fill_vtable) {
         set_error("%s: the device environment descriptor lacks a function", who); return TW_ERR_INVALID;
     }
     if (d->num_actions < 1 || d->num_actions > 4 || d->n_obs < 1 || d->n_obs > 64 || d->engine_nc != (uint32_t)env_engine_nc((int)d->n_obs)) {
@@ -67,8 +67,9 @@ int check_descriptor(const tw_device_env *d, const void *proto, size_t proto_byt
     if (proto_bytes != d->state_bytes) {
         set_error("%s: the prototype has %zu bytes, the module's environment %u", who, proto_bytes, d->state_bytes); return TW_ERR_INVALID;
     }
-    const int os = d->obs_size(proto);
+    const int os = d->obs_size(proto), no = d->n_obs_of(proto);
     if (os < 1 || os > 65535) { set_error("%s: obs_size() is %d (1..65535)", who, os); return TW_ERR_INVALID; }
+    if (no < 1 || no > (int)d->n_obs) { set_error("%s: n_obs() is %d (1..N_OBS = %u)", who, no, d->n_obs); return TW_ERR_INVALID; }
     return TW_OK;
 }
 
@@ -78,6 +79,7 @@ tw_env_vtable host_table(const tw_device_env *d, const void *proto)
     d->fill_vtable(&vt);
     vt.prototype = const_cast<void *>(proto);          // the collectors clone it and never write to it
     vt.obs_size = (uint32_t)d->obs_size(proto);
+    vt.n_obs = (uint32_t)d->n_obs_of(proto);
     return vt;
 }
 
@@ -130,7 +132,7 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     rc = require_device(); if (rc) return rc;
 
     const uint64_t E = prm->num_episodes;
-    const uint32_t A = env->num_actions, NO = env->n_obs, OW = pd->obs_size > 256 ? 2u : 1u;
+    const uint32_t A = env->num_actions, NO = vt.n_obs, OW = pd->obs_size > 256 ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
     const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;
     if (blocks > 0x7fffffffull || t_pad > 0x7fffffffull) { set_error("tw_ppo_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }

@@ -7,9 +7,9 @@
 // a "generic" policy (tw_policy_create) -- runs on EngineV (tw_engine_generic.hpp: every Linear on the matrix cores, the
 // EmbeddingBag gathered from global memory).  Same path otherwise: PPOCollector::single_collect (collector/ppo.rs:54-80),
 // Policy::forward_with_perm (nn/policy.rs:56-100), sample_from_logits (policy.rs:169-172), Env::step / masks / reward / is_final
-// (puzzle.rs:135-181), same RNG streams, same arithmetic: bit-equal to the oracle.  evaluate() without MCTS runs here too
-// (solve_big_kernel).  Boards above 64 cells, self-play, solve() from a given state and MCTS-guided evaluate of boards above 16
-// cells stay on the host-stepped path (tw_env_generic.hip).
+// (puzzle.rs:135-181: the big_* functions of tw_big_board.hpp, shared with tw_mcts_big.hip and BigPuzzleEnv), same RNG streams,
+// same arithmetic: bit-equal to the oracle.  evaluate() and solve() without MCTS run here too (solve_big_kernel).  Self-play and
+// MCTS-guided evaluate: tw_mcts_big.hip; boards above 64 cells stay on the host-stepped path (tw_env_generic.hip).
 #include "tw_engine_generic.hpp"
 #include "tw_big_board.hpp"
 
@@ -64,11 +64,10 @@ __global__ void __launch_bounds__(256, 1) rollout_big_kernel(const RolloutArgs a
         float lg[4]; float value;
         eng.forward(rowoff, lg, value);
         eng.act_perm(perm, lg);
-        const uint32_t mb = (st.zx > 0 ? 1u : 0u) | (st.zy > 0 ? 2u : 0u) | (st.zx < env.width - 1 ? 4u : 0u) | (st.zy < env.height - 1 ? 8u : 0u);   // puzzle.rs:162-165
+        const uint32_t mb = big_maskbits(st, env);                                   // puzzle.rs:162-165
 #pragma unroll
         for (int i = 0; i < 4; ++i) lg[i] = ((mb >> i) & 1u) ? lg[i] : -1e10f;       // policy.rs:62
-        const bool solved = st.board == ident;
-        const float rew = solved ? 1.0f : (st.depth == 0 ? -0.5f : env.r_step);      // puzzle.rs:171-177
+        const float rew = big_reward(st, ident, env);                                // puzzle.rs:171-177
         const u32x4 gw = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_GUMBEL);
         const int action = gumbel_argmax4(lg, gw);
         // ---- push the record (ppo.rs:71-76), then is_final / step (ppo.rs:78-79) --------------
@@ -81,7 +80,7 @@ __global__ void __launch_bounds__(256, 1) rollout_big_kernel(const RolloutArgs a
 #pragma unroll
                 for (int i = 0; i < NC; ++i) if (i < nc) o[i] = (uint16_t)(i * nc + (int)st.board.cell(i));
             }
-            if (st.depth == 0 || solved) alive = false;                      // puzzle.rs:167-169
+            if (big_final(st, ident)) alive = false;                         // puzzle.rs:167-169
             else { big_step(st, env, action); ++t; }
         }
     }
@@ -117,7 +116,8 @@ __global__ void __launch_bounds__(256, 1) solve_big_kernel(const SolveArgs a)
         }
         st.depth = env.depth0;
     }
-    bool  alive = valid && !(st.depth == 0 || st.board == ident);
+    bool  alive = valid && !(st.depth == 0 || st.board == ident);                     // big_final, spelled out here and after the step: the call compiles
+                                                                                      // to other code for these three kernels (profiles/r06_generic_body_ab.txt)
     float total = 0.0f;
     int   t = 0;
     eng.begin2();
@@ -140,11 +140,11 @@ __global__ void __launch_bounds__(256, 1) solve_big_kernel(const SolveArgs a)
         float lg[4], value;
         eng.forward(rowoff, lg, value);
         eng.act_perm(perm, lg);
-        const uint32_t mb = (st.zx > 0 ? 1u : 0u) | (st.zy > 0 ? 2u : 0u) | (st.zx < env.width - 1 ? 4u : 0u) | (st.zy < env.height - 1 ? 8u : 0u);
+        const uint32_t mb = big_maskbits(st, env);
         float probs[4];
         masked_softmax4(lg, mb, probs);                                               // policy.rs:43-47
         if (alive) {
-            total = total + (st.board == ident ? 1.0f : (st.depth == 0 ? -0.5f : env.r_step));      // solve.rs:31,34
+            total = total + big_reward(st, ident, env);                               // solve.rs:31,34
             int action = 0;
             if (a.deterministic) {
                 float bv = probs[0];
@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(256, 1) solve_big_kernel(const SolveArgs a)
         }
     }
     if (valid && writer) {
-        total = total + (st.board == ident ? 1.0f : (st.depth == 0 ? -0.5f : env.r_step));          // solve.rs:65-66
+        total = total + big_reward(st, ident, env);                                   // solve.rs:65-66
         a.success[att] = st.board == ident ? 1.0f : 0.0f;                             // solve.rs:68
         a.total[att]   = total;
         a.n_steps[att] = (uint32_t)t;

@@ -11,6 +11,7 @@
 #include "tw_engine_generic.hpp"
 
 #include <type_traits>
+#include <utility>
 
 namespace tw {
 
@@ -56,6 +57,7 @@ struct tw_device_env {
     int   (*get_difficulty)(const void *env);
     void  (*set_difficulty)(void *env, int d);
     int   (*obs_size)(const void *env);
+    int   (*n_obs_of)(const void *env);                    // ids per observation of THIS object: n_obs, or the struct's own n_obs() (<= n_obs)
     void  (*fill_vtable)(tw_env_vtable *out);
 };
 
@@ -67,6 +69,15 @@ inline void tw_device_env_layout(uint32_t (&out)[TW_DEVICE_ENV_LAYOUT_WORDS])
 }
 
 namespace tw {
+
+// ids per observation: the struct's own n_obs() where it has one (BigPuzzleEnv<25>, tw_big_board.hpp, holds boards of 1 .. 25 cells),
+// else the constant Env::N_OBS -- which is what every use below folds to for a struct without the method
+template <class Env, class = void>
+struct EnvNObs { __host__ __device__ static constexpr int of(const Env &) { return Env::N_OBS; } };
+template <class Env>
+struct EnvNObs<Env, decltype((void)std::declval<const Env &>().n_obs())> { __host__ __device__ static int of(const Env &e) { return e.n_obs(); } };
+template <class Env>
+__host__ __device__ inline int env_n_obs(const Env &e) { return EnvNObs<Env>::of(e); }
 
 // sample_from_logits (policy.rs:169-172) over the environment's A <= 4 actions: the words of ONE draw (t, STREAM_GUMBEL) as the
 // host path takes them (tw_env_generic.hip), first maximum wins, NaN never; A = 4 is gumbel_argmax4
@@ -104,10 +115,11 @@ template <class Env, int NC>
 __device__ __forceinline__ void env_rows(const Env &st, const PolicyDev &pol, int perm, int (&ids)[Env::N_OBS], int (&rowoff)[NC], bool &bad, int &bad_id)
 {
     st.observe(ids);
+    const int n = env_n_obs(st);
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
         int row = -1;
-        if (i < Env::N_OBS) {
+        if (i < Env::N_OBS && i < n) {
             const int id = ids[i];
             if ((unsigned)id >= (unsigned)pol.obs_size) { if (!bad) bad_id = id; bad = true; }
             else row = perm < 0 ? id : (pol.obs_size > 256 ? (int)pol.obs_perms16[(size_t)perm * pol.obs_size + id]
@@ -172,9 +184,10 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
                     const uint64_t rec = e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
                     const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
                     store_rec(a.out.rec + rec, zero4, lg, value, rew, action, perm);
-                    uint16_t *o = a.obs16 + rec * (uint64_t)NO;
+                    const int n = env_n_obs(st);
+                    uint16_t *o = a.obs16 + rec * (uint64_t)n;
 #pragma unroll
-                    for (int i = 0; i < NO; ++i) o[i] = (uint16_t)ids[i];
+                    for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
                 }
                 if (st.is_final()) alive = false;                                     // ppo.rs:78
                 else if (t + 1 >= a.out.t_pad) {                                      // the host path's max_records_per_episode

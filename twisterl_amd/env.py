@@ -224,7 +224,7 @@ class DeviceEnvDesc(C.Structure):
                 ("engine_nc", C.c_uint32), ("type_name", C.c_char_p), ("launch_rollout", C.c_void_p), ("launch_solve", C.c_void_p),
                 ("create", C.CFUNCTYPE(C.c_void_p, C.POINTER(C.c_double), C.c_int)),
                 ("get_difficulty", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("set_difficulty", C.CFUNCTYPE(None, C.c_void_p, C.c_int)),
-                ("obs_size", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("fill_vtable", C.c_void_p)]
+                ("obs_size", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("n_obs_of", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("fill_vtable", C.c_void_p)]
 
 
 class DeviceEnv:
@@ -294,7 +294,7 @@ class DeviceEnv:
 
     @property
     def n_obs(self) -> int:
-        return int(self._desc.n_obs)
+        return int(self._vt.n_obs)                # (this object's: a struct with its own n_obs() may write fewer than N_OBS)
 
     @property
     def obs_size(self) -> int:
