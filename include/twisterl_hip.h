@@ -96,7 +96,8 @@ enum {
 int tw_set_launch_option(int option, int value);
 /* Diagnostic counters of the last self-play launch of this process (MctsArgs::eval_count[0..15]); test hook. */
 int tw_debug_counters(uint64_t *out, int n);
-/* Test hook: the kernel the last tw_az_collect / tw_evaluate / tw_solve / big-board tw_ppo_collect of this process launched, as its
+/* Test hook: the kernel the last tw_az_collect / tw_evaluate / tw_solve / big-board tw_ppo_collect / one-hot hand-off
+ * (tw_collected_pack_trainer) of this process launched, as its
  * launcher reports it from its own template parameters (family 0: the call launched none of these kernels).  The arguments a family
  * does not have are 0; the split shape of the walker kernel also reports the grid of its mcts_engine_kernel<nt, nc>. */
 enum {
@@ -106,7 +107,9 @@ enum {
     TW_KERNEL_MCTS_DEEP = 3,    /* mcts_deep_kernel<nt, nc, nw, nwk, SOLVE, DEC, SPL>            */
     TW_KERNEL_MCTS_BIG = 4,     /* mcts_big_kernel<nc>                                           */
     TW_KERNEL_SOLVE_BIG = 5,    /* solve_big_kernel<nc>                                          */
-    TW_KERNEL_ROLLOUT_BIG = 6   /* rollout_big_kernel<nc>                                        */
+    TW_KERNEL_ROLLOUT_BIG = 6,  /* rollout_big_kernel<nc>                                        */
+    TW_KERNEL_ONEHOT = 7        /* nt 4: onehot4_kernel<8>, 1: onehot_kernel, 0: memset + onehot_scatter_kernel; nc: the rows a
+                                 * workgroup writes per trip of its loop (32, 4; 0: one id per thread, no loop)                */
 };
 typedef struct {
     int32_t  family;            /* TW_KERNEL_*                                                   */
@@ -403,6 +406,8 @@ void tw_collected_free(tw_collected *c);
  *      reference src/twisterl/rl/ppo.py:25-61, rl/az.py:28-46).  Every output is a DEVICE pointer supplied by the
  *      caller (e.g. torch tensors) and may be NULL; rows [row_begin, row_begin+row_count) of the collected data.
  *  obs_onehot  float [row_count][obs_size]   np_obs[i, obs_i] = 1.0                        (ppo.py:37-39)
+ *                                            obs_size must be the one the data was collected with (Puzzle: cells^2; an
+ *                                            environment: the policy's), else TW_ERR_INVALID before anything is launched
  *  log_probs   float [row_count]             Categorical(logits).log_prob(actions)          (ppo.py:57-59)  PPO only
  *  actions     int64 [row_count]             (ppo.py:47)                                                    PPO only
  *  perms       int64 [row_count]             -1 = None (ppo.py:50-52)
@@ -452,7 +457,7 @@ int  tw_comm_broadcast_policy(tw_comm *c, tw_policy *p, int root);
 typedef struct tw_gather tw_gather;
 /* Placement of one step's chunks in the root's result -- pure host arithmetic (no device, no RCCL; tw_gather_submit calls
  * it with the counts it has exchanged).  counts[world][TW_GATHER_COUNTS]: records, records of the chunk's last episode,
- * episodes, first global episode, bytes per obs id, actions, status, 0.  *st: steps / max_records / max_episode_records
+ * episodes, first global episode, bytes per obs id, actions, status, obs_size | cell-major << 32 (the placement reads neither).  *st: steps / max_records / max_episode_records
  * set by the caller, step 0 at the start; front, cap, pos, tail are maintained by the function (front / cap decided in step
  * 0: one step = exact size with the records of episode E-1 first, several = max_records + max_episode_records with that
  * much slack in front).  Out: n_pieces[r] in {0, 1, 2} and pieces[r][2] = records [src_lo, src_hi) of rank r's chunk ->

@@ -1,4 +1,4 @@
-"""A float64 reference of the PPO policy forward and GAE, in plain numpy.
+"""A float64 reference of the PPO policy forward, GAE and the trainer hand-off, in plain numpy.
 
 Written from the reference's definitions, not from the oracle's C code, so that a test can hold both the GPU and the oracle's own
 f32 orders against an arithmetic neither of them uses:
@@ -113,6 +113,64 @@ def gae_f64_episodes(rews, vals, ep_len, gamma, lam):
         advs[idx] = rets[idx] - v[idx]
         nxt_v[live], nxt_a[live] = v[idx], advs[idx]
     return advs, rets
+
+
+# ---------------------------------------------------------------------------------------------- trainer hand-off
+# PPO.data_to_torch / AZ.data_to_torch of the reference trainer (src/twisterl/rl/ppo.py:25-61, rl/az.py:28-46), from their definitions.
+def onehot_ref(obs, obs_size):
+    """np_obs[i, obs_i] = 1.0 (ppo.py:37-39): row i has a one in every column that appears among the ids of record i -- in any order,
+    any number of times -- and zeros elsewhere.  float32 [n, obs_size]."""
+    obs = np.asarray(obs, np.int64)
+    obs = obs.reshape(obs.shape[0], -1) if obs.size else obs.reshape(obs.shape[0], 0)
+    if obs.size and (obs.min() < 0 or obs.max() >= obs_size):
+        raise ValueError(f"an obs id outside [0, {obs_size})")
+    out = np.zeros((obs.shape[0], int(obs_size)), np.float32)
+    for i in range(obs.shape[0]):
+        out[i, obs[i]] = 1.0
+    return out
+
+
+def log_prob_f64(logits, actions):
+    """Categorical(logits=l).log_prob(a) = l[a] - logsumexp(l) per row, in float64 (ppo.py:57-59).  A masked logit (-1e10) is an
+    ordinary number: its term exp(-1e10 - max) is 0.0 in float64 whenever another action is legal."""
+    l = np.asarray(logits, np.float64)
+    a = np.asarray(actions, np.int64).reshape(-1)
+    m = l.max(axis=1)
+    lse = m + np.log(np.exp(l - m[:, None]).sum(axis=1))
+    return l[np.arange(l.shape[0]), a] - lse
+
+
+def normalized_adv_f64(advs):
+    """(a - mean) / (std + 1e-8), std unbiased as torch.std (ppo.py:55-56), in float64.  One record: nan, as torch."""
+    a = np.asarray(advs, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sd = a.std(ddof=1) if a.size > 1 else np.float64("nan")
+        return (a - a.mean()) / (sd + 1e-8)
+
+
+def log_prob_bound(n_actions, want, lse=0.0):
+    """|f32 log-prob - log_prob_f64| per record for a kernel that computes (l[a] - max) - log(sum exp(l - max)) in f32:
+    (A + 8) 2^-24 + 2^-23 |want|.  A rounded additions of terms <= 1 into a sum in [1, A] (relative to the sum, which the logarithm
+    divides by), a few ulp for exp, log and the two subtractions, and the rounding of the result relative to its size.
+    `lse`: |logsumexp(l)| per record for an implementation that forms l[a] - (max + log(sum)) instead, as torch's Categorical does
+    (logits - logits.logsumexp()): max + log(sum) and the difference are rounded at the size of the logits, not of the result --
+    2^-23 |lse| more.  With logits of size 50 that is 6e-6 on a log-prob that may be 1e-5: the form the hand-off kernel does not use."""
+    return (int(n_actions) + 8) * 2.0 ** -24 + 2.0 ** -23 * (np.abs(np.asarray(want, np.float64)) + np.abs(np.asarray(lse, np.float64)))
+
+
+def logsumexp_f64(logits):
+    l = np.asarray(logits, np.float64)
+    m = l.max(axis=1)
+    return m + np.log(np.exp(l - m[:, None]).sum(axis=1))
+
+
+def normalized_adv_bound(advs, want):
+    """|f32 (a - mean) / (std + 1e-8) - normalized_adv_f64| per record, mean and std rounded to f32 from exact values:
+    2^-23 (|a| + |mean|) / (std + 1e-8) for the subtraction and the rounded mean, 2^-23 |want| for the rounded denominator and the
+    division."""
+    a = np.asarray(advs, np.float64)
+    sd = a.std(ddof=1)
+    return 2.0 ** -23 * (np.abs(a) + abs(a.mean())) / (sd + 1e-8) + 2.0 ** -23 * np.abs(np.asarray(want, np.float64))
 
 
 # ---------------------------------------------------------------------------------------------- a-priori error bounds

@@ -35,6 +35,23 @@ def test_library_exports_every_declared_symbol():
     assert lib.tw_abi_version() == _lib.ABI_VERSION == 6
 
 
+def test_kernel_families_of_the_launch_hook_agree_with_the_header():
+    """TW_KERNEL_* (tw_debug_last_launch): include/twisterl_hip.h, twisterl_amd/_lib.py and docs/hip.rs name the same families, the
+    one-hot hand-off (TW_KERNEL_ONEHOT) among them, and tw_launch_info has the fields of _lib.LaunchInfo in order."""
+    from twisterl_amd import _lib
+    text = open(os.path.join(ROOT, "include", "twisterl_hip.h")).read()
+    enum = dict((k, int(v)) for k, v in re.findall(r"\b(TW_KERNEL_[A-Z0-9_]+) = (\d+)", text))
+    assert enum == {k: getattr(_lib, k) for k in dir(_lib) if k.startswith("TW_KERNEL_")} and enum["TW_KERNEL_ONEHOT"] == 7 == max(enum.values())
+    struct = re.search(r"typedef struct \{([^}]*)\} tw_launch_info;", text).group(1)
+    struct = re.sub(r"/\*.*?\*/", "", struct, flags=re.S)
+    fields = [n for decl in struct.split(";") for n in re.findall(r"\b([a-z_]+)\b(?=\s*(?:,|$))", decl.strip())]
+    assert fields == [n for n, _ in _lib.LaunchInfo._fields_]
+    rs = open(os.path.join(ROOT, "docs", "hip.rs")).read()
+    doc = rs[rs.index("/// tw_launch_info"):rs.index("pub struct TwLaunchInfo")]
+    assert all(f"{v} " in doc for v in enum.values() if v) and "one-hot" in doc
+    assert re.findall(r"(\w+): [iu]32", rs[rs.index("pub struct TwLaunchInfo"):rs.index("// fields of the result")]) == fields
+
+
 def test_launch_options_are_validated():
     """tw_set_launch_option (diagnostic launch overrides, include/twisterl_hip.h): values outside an option's set are refused with a
     message, accepted ones can be set back to automatic.  Needs no device."""

@@ -5,6 +5,8 @@
 * The float64 forward stays within 1e-5 of the oracle's reference order and of its fma chain, and the float64 GAE within
   1e-5 of the oracle's f32 GAE at the benchmark's horizon and beyond.
 * Both float64 pieces reproduce the reference's own known answers (tests/golden/reference_known_answers.json).
+* The trainer hand-off's references (one-hot, log-prob, normalised advantages) agree with torch in float64 and with cases worked by hand,
+  and torch's own f32 Categorical stays inside the bound the GPU log-probs are held to.
 """
 import json
 import os
@@ -285,3 +287,79 @@ def test_gae_bound_holds_for_perturbed_values(oracle):
         a32, r32 = oracle.gae(rews[s:s + n], moved[s:s + n], 0.995, 0.995)
         assert np.all(np.abs(a32 - a64[s:s + n]) <= ea[s:s + n]) and np.all(np.abs(r32 - r64[s:s + n]) <= er[s:s + n])
         s += n
+
+
+# ---------------------------------------------------------------------------------------------- trainer hand-off references
+def test_onehot_ref_is_a_set_per_row():
+    from tests.ref64 import onehot_ref
+    got = onehot_ref([[4, 0, 4], [2, 1, 0], [3, 3, 3]], 5)
+    assert got.dtype == np.float32 and got.tolist() == [[1, 0, 0, 0, 1], [1, 1, 1, 0, 0], [0, 0, 0, 1, 0]]
+    assert np.array_equal(onehot_ref([[1, 0]], 2), onehot_ref([[0, 1]], 2))             # order does not matter
+    assert onehot_ref(np.zeros((0, 3), np.uint8), 7).shape == (0, 7)
+    rng = np.random.default_rng(0)
+    obs = rng.integers(0, 50, (300, 3))
+    want = np.zeros((300, 50), np.float32)
+    for i, o in enumerate(obs):
+        want[i, o] = 1.0                                                                # ppo.py:37-39, literally
+    assert np.array_equal(onehot_ref(obs.astype(np.uint8), 50), want)
+    for bad in ([[5]], [[-1]]):
+        with pytest.raises(ValueError):
+            onehot_ref(bad, 5)
+
+
+def _random_logits(A, n, seed, scale):
+    rng = np.random.default_rng(seed)
+    l = (rng.standard_normal((n, A)) * scale).astype(np.float32)
+    masks = rng.random((n, A)) < 0.6
+    masks[np.arange(n), rng.integers(0, A, n)] = True
+    l[~masks] = np.float32(MASKED)
+    acts = np.array([rng.choice(np.flatnonzero(m)) for m in masks])
+    return l, acts
+
+
+@pytest.mark.parametrize("A", [3, 4, 5, 17, 31])
+def test_log_prob_f64_against_torch_and_by_hand(A):
+    import torch
+    from tests.ref64 import log_prob_bound, log_prob_f64, logsumexp_f64
+    for scale in (1.0, 30.0):
+        l, acts = _random_logits(A, 4000, A, scale)
+        want = torch.distributions.Categorical(logits=torch.tensor(l, dtype=torch.float64)).log_prob(torch.tensor(acts)).numpy()
+        got = log_prob_f64(l, acts)
+        assert np.max(np.abs(got - want) / (1.0 + np.abs(want))) < 1e-13
+        # torch's own f32 arithmetic: inside the bound the hand-off kernel is held to while the logits are of the size of the log-probs;
+        # with large logits only inside the bound of ITS form, logits - logsumexp(logits), which rounds at the size of the logits
+        t32 = torch.distributions.Categorical(logits=torch.tensor(l)).log_prob(torch.tensor(acts)).numpy().astype(np.float64)
+        dev = np.abs(t32 - got)
+        assert np.all(dev <= log_prob_bound(A, got, lse=logsumexp_f64(l))), (A, scale, float(np.max(dev / log_prob_bound(A, got, lse=logsumexp_f64(l)))))
+        assert np.all(dev <= log_prob_bound(A, got)) == (scale == 1.0), (A, scale, float(np.max(dev / log_prob_bound(A, got))))
+    # one legal action: its probability is one; equal logits: 1 / A each; two logits ln 3 apart: 1/4 and 3/4
+    one = np.full((1, A), MASKED)
+    one[0, A - 2] = -3.25
+    assert log_prob_f64(one, [A - 2])[0] == 0.0
+    np.testing.assert_allclose(log_prob_f64(np.full((2, A), 7.5), [0, A - 1]), [-np.log(A)] * 2, rtol=0, atol=1e-14)
+    two = np.full((2, A), MASKED)
+    two[:, 0], two[:, 2] = 1.0, 1.0 + np.log(3.0)
+    np.testing.assert_allclose(log_prob_f64(two, [0, 2]), [np.log(0.25), np.log(0.75)], rtol=0, atol=1e-15)
+    assert np.isclose(log_prob_f64(two, [1])[0], MASKED - 1.0 - np.log(4.0), rtol=1e-15)     # a masked action: an ordinary number
+
+
+def test_normalized_adv_f64_against_torch_and_by_hand():
+    import torch
+    from tests.ref64 import normalized_adv_bound, normalized_adv_f64
+    rng = np.random.default_rng(1)
+    a = (rng.standard_normal(5000) * 0.3 - 0.2).astype(np.float32)
+    t = torch.tensor(a, dtype=torch.float64)
+    want = ((t - t.mean()) / (t.std() + 1e-8)).numpy()
+    got = normalized_adv_f64(a)
+    assert np.max(np.abs(got - want)) < 1e-12
+    assert np.array_equal(normalized_adv_f64([1.0, 2.0, 3.0]), np.array([-1.0, 0.0, 1.0]) / (1.0 + 1e-8))
+    assert np.all(normalized_adv_f64([2.0, 2.0, 2.0]) == 0.0)                            # std 0: the 1e-8 keeps it finite
+    assert np.isnan(normalized_adv_f64([0.7])).all()                                     # one record: torch.std is nan
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                                              # (torch says so too: degrees of freedom <= 0)
+        assert np.isnan(((torch.tensor([0.7]) - 0.7) / (torch.tensor([0.7]).std() + 1e-8)).numpy()).all()
+    # torch's f32 normalisation inside the bound the hand-off kernel is held to
+    t32 = torch.tensor(a)
+    n32 = ((t32 - t32.mean()) / (t32.std() + 1e-8)).numpy().astype(np.float64)
+    assert np.all(np.abs(n32 - got) <= normalized_adv_bound(a, got) + 2.0 ** -22 * np.abs(got).max())   # (+ torch's own f32 mean and std)

@@ -51,7 +51,7 @@ OTHER = {
     "policy_sync_kernel": ("tw_sync", "test_gpu_parity.py", "test_policy_update_from_torch_equals_rebuilding"),
     "policy_sync_generic_kernel": ("tw_sync", "test_gpu_parity.py", "test_policy_update_from_torch_for_any_depth"),
     "onehot_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),
-    "onehot_scatter_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),
+    "onehot_scatter_kernel": ("tw_trainer", "test_gpu_trainer_handoff.py", "test_one_hot_of_ids_that_follow_no_layout"),
     "onehot4_kernel<8>": ("tw_trainer", "test_gpu_parity.py", "test_trainer_one_hot_of_boards_whose_cells_own_multiples_of_four_ids"),
     "ppo_pack_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),
     "sum_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),

@@ -78,9 +78,24 @@ def scenario_exchange(rank, world, checks):
             pol = gp
 
     # --- PPO: uneven shards, one step / three chunks / steps sized in episodes with CUs reserved
-    def check(coll, env_, pol_, keys, tag, dst=0, **kw):
-        want = coll.collect(env_, pol_, seed=3).to_numpy() if rank == dst else None
-        merged, parts = collect_sharded(coll, env_, pol_, seed=3, dst=dst, comm=comm, **kw)
+    def check(coll, env_, pol_, keys, tag, dst=0, handoff=0, **kw):
+        whole = coll.collect(env_, pol_, seed=3) if rank == dst else None
+        want = whole.to_numpy() if rank == dst else None
+        merged, parts = collect_sharded(coll, env_, pol_, seed=3, dst=dst, comm=comm, as_data=bool(handoff), **kw)
+        if rank == dst and handoff:
+            # the merged result carries the chunks' obs_size and layout through the count exchange: the trainer hand-off takes it like
+            # the un-sharded collect -- same kernel form, same tensors -- and refuses another obs_size
+            import torch
+            from twisterl_amd import _lib, trainer
+            got = trainer.ppo_data_to_torch(merged, handoff, normalize_advantage=True)
+            form = _lib.debug_last_launch()
+            ref = trainer.ppo_data_to_torch(whole, handoff, normalize_advantage=True)
+            assert form == _lib.debug_last_launch() and form["family"] == _lib.TW_KERNEL_ONEHOT and form["nt"] == 4, f"{tag}: {form}"
+            assert all(torch.equal(x, y) for x, y in zip(got, ref)), f"{tag}: the hand-off of the merged result differs"
+            assert float(got[0].sum()) == got[0].shape[0] * merged._dev.n_cells
+            msg = _raises(lambda: trainer.ppo_data_to_torch(merged, handoff - 1))
+            assert msg is not None and f"obs_size {handoff - 1}" in msg and f"obs_size {handoff}" in msg, f"{tag}: {msg}"
+            merged = merged.to_torch()
         if rank == dst:
             bad = _same(merged, want, keys)
             assert bad is None, f"{tag}: field {bad} of the merged result differs from the un-sharded collect"
@@ -115,7 +130,7 @@ def scenario_exchange(rank, world, checks):
     op4, ap4 = puzzle_transpose_twist(4)
     pol4 = amd_policy(make_policy_arrays(16, seed=1, emb=64, hidden=32), op4, ap4)
     check(tw.collector.PPOCollector(203, 0.995, 0.995, 1), tw.env.Puzzle(4, 4, 7, 2, 256), pol4, PPO_KEYS, "ppo_puzzle15_twists_steps",
-          step_episodes=32, max_episode_records=15, reserve_cus=8)
+          step_episodes=32, max_episode_records=15, reserve_cus=8, handoff=256)
     comm.close()
 
 

@@ -84,7 +84,7 @@ class LaunchInfo(C.Structure):
 
 
 (TW_KERNEL_NONE, TW_KERNEL_MCTS_F32, TW_KERNEL_SOLVE_F32, TW_KERNEL_MCTS_DEEP, TW_KERNEL_MCTS_BIG, TW_KERNEL_SOLVE_BIG,
- TW_KERNEL_ROLLOUT_BIG) = range(7)
+ TW_KERNEL_ROLLOUT_BIG, TW_KERNEL_ONEHOT) = range(8)
 
 
 class EnvVTable(C.Structure):
@@ -267,8 +267,10 @@ def debug_counters(n: int = 16) -> list:
 
 
 def debug_last_launch() -> dict:
-    """The kernel the last self-play / evaluate / solve / big-board PPO call of this process launched, as its launcher reported it
-    (tw_debug_last_launch; test hook): family (TW_KERNEL_*), template arguments, grid, and the engine kernel's grid of the split shape."""
+    """The kernel the last self-play / evaluate / solve / big-board PPO / one-hot hand-off call of this process launched, as its launcher
+    reported it (tw_debug_last_launch; test hook): family (TW_KERNEL_*), template arguments, grid, and the engine kernel's grid of the
+    split shape.  TW_KERNEL_ONEHOT: nt = 4 / 1 / 0 for onehot4_kernel / onehot_kernel / memset + onehot_scatter_kernel, nc = the rows a
+    workgroup writes per trip of its loop."""
     info = LaunchInfo()
     check(lib().tw_debug_last_launch(C.byref(info)))
     return {name: int(getattr(info, name)) for name, _ in LaunchInfo._fields_}

@@ -966,6 +966,9 @@ struct tw_collected {
     size_t arena_cap = 0; int device = -1;
     hipStream_t stream = nullptr;           // the library stream of the thread that produced it (tw_set_stream is thread-local)
     uint32_t obs_width = 1;                 // bytes per obs id (2: an environment with more than 256 ids, tw_ppo_collect_env)
+    uint32_t obs_size = 0;                  // the ids lie in [0, obs_size): Puzzle n_cells^2, an environment the policy's (0: not recorded)
+    bool cell_major = false;                // position k of an observation holds an id of [k * n2, (k + 1) * n2), n2 = obs_size / n_cells:
+                                            // what the Puzzle collectors write, and nobody else claims (trainer hand-off, tw_trainer.hip)
     void *field_ptr[TW_F_COUNT] = {};
     size_t field_bytes[TW_F_COUNT] = {};
     uint64_t n_records = 0, n_episodes = 0;
@@ -1042,12 +1045,17 @@ extern "C" int tw_collected_pack_trainer(const tw_collected *c, uint32_t obs_siz
         return TW_ERR_INVALID;
     }
     if (obs_onehot && c->obs_width != 1) { set_error("tw_collected_pack_trainer: one-hot packing exists for one-byte obs ids (obs_size <= 256)"); return TW_ERR_UNSUPPORTED; }
-    if (obs_onehot && (obs_size == 0 || obs_size > 256 || obs_size < c->n_cells)) { set_error("tw_collected_pack_trainer: obs_size %u", obs_size); return TW_ERR_INVALID; }
+    // the ids were checked against the obs_size the data was collected with: any other row length would drop ids or write outside the rows
+    if (obs_onehot && (obs_size == 0 || obs_size > 256 || obs_size != c->obs_size)) {
+        set_error("tw_collected_pack_trainer: obs_size %u, the data was collected with obs_size %u", obs_size, c->obs_size);
+        return TW_ERR_INVALID;
+    }
     if ((log_probs || actions || advs) && !c->is_ppo) { set_error("tw_collected_pack_trainer: log_probs / actions / advs exist for PPO data only"); return TW_ERR_INVALID; }
     hipStream_t s = current_stream();
     int rc = TW_OK;
     if (obs_onehot)
-        rc = launch_onehot(reinterpret_cast<const uint8_t *>(c->field_ptr[TW_F_OBS]), row_begin, row_count, (int)c->n_cells, (int)obs_size, obs_onehot, s);
+        rc = launch_onehot(reinterpret_cast<const uint8_t *>(c->field_ptr[TW_F_OBS]), row_begin, row_count, (int)c->n_cells, (int)obs_size, c->cell_major,
+                           obs_onehot, s);
     if (rc) return rc;
     float mean = 0.0f, denom = 1.0f;
     if (advs && normalize_advantage) {
@@ -1066,6 +1074,8 @@ extern "C" int tw_collected_pack_trainer(const tw_collected *c, uint32_t obs_siz
 namespace tw {
 const PolicyDev *policy_dev(const tw_policy *p) { return &p->dev; }
 void collected_adopt_obs_width(tw_collected *c, uint32_t obs_width) { c->obs_width = obs_width; }
+void collected_adopt_obs_layout(tw_collected *c, uint32_t obs_size, bool cell_major) { c->obs_size = obs_size; c->cell_major = cell_major; }
+void collected_obs_layout(const tw_collected *c, uint32_t *obs_size, bool *cell_major) { *obs_size = c->obs_size; *cell_major = c->cell_major; }
 int policy_device_image(tw_policy *p, void **image, size_t *bytes)
 {
     if (!p || !p->arena) { set_error("policy: no device image"); return TW_ERR_INVALID; }
@@ -1348,6 +1358,7 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
     size_t ccur = 0;
     auto cseg = [&](int f, size_t bytes) { c->field_bytes[f] = bytes; size_t o = ccur; ccur = align_up(ccur + bytes, 256); return o; };
     if (big) c->obs_width = 2;
+    c->obs_size = c->n_cells * c->n_cells; c->cell_major = !big;         // (boards up to 16 cells: cell k holds k * n_cells + tile)
     const size_t c_obs = cseg(TW_F_OBS, total * c->n_cells * c->obs_width), c_lg = cseg(TW_F_LOGITS, total * 16), c_prm = cseg(TW_F_PERMS, total),
                  c_val = cseg(TW_F_VALUES, total * 4), c_rew = cseg(TW_F_REWARDS, total * 4), c_act = cseg(TW_F_ACTIONS, total),
                  c_adv = cseg(TW_F_ADVS, total * 4), c_ret = cseg(TW_F_RETS, total * 4), c_len = cseg(TW_F_EP_LEN, E * 4),
@@ -1548,6 +1559,7 @@ static int az_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, c
     size_t ccur = 0;
     auto cseg = [&](int f, size_t bytes) { c->field_bytes[f] = bytes; size_t o = ccur; ccur = align_up(ccur + bytes, 256); return o; };
     if (big) c->obs_width = 2;
+    c->obs_size = c->n_cells * c->n_cells; c->cell_major = !big;         // (boards up to 16 cells: cell k holds k * n_cells + tile)
     const size_t c_obs = cseg(TW_F_OBS, total * c->n_cells * c->obs_width), c_lg = cseg(TW_F_LOGITS, total * 16), c_prm = cseg(TW_F_PERMS, total),
                  c_rem = cseg(TW_F_REMAINING, total * 4), c_len = cseg(TW_F_EP_LEN, E * 4), c_start = cseg(TW_F_EP_START, E * 8);
     rc = hipGetDevice(&c->device) == hipSuccess ? arena_acquire(ccur, &c->arena, &c->arena_cap) : TW_ERR_HIP;

@@ -262,6 +262,7 @@ struct tw_gather {
     tw_comm *c = nullptr;
     int root = 0, is_ppo = 1;
     uint32_t n_cells = 0, n_actions = 0, obs_width = 0;       // n_actions / obs_width: taken from the first non-empty chunk any rank submits
+    uint64_t obs_layout = 0;                                  // ... and its obs_size | cell_major << 32 (the trainer hand-off's, tw_collected)
     uint64_t total_episodes = 0;
     tw_gather_state st{};                  // steps, step, pos, front, cap, tail: advanced by tw_gather_plan
     size_t width[TW_F_COUNT] = {};
@@ -356,15 +357,17 @@ extern "C" int tw_gather_submit(tw_gather *g, const tw_collected *local, uint64_
     // A chunk that does not fit the gather is reported THROUGH the count exchange (status word), so that every rank sees it and
     // all of them return the error together: a rank that left before the collective would leave the others waiting in it.
     uint64_t status = 0;
-    int is_ppo = g->is_ppo; uint32_t nc = g->n_cells, na = 0, ow = 0; uint64_t n_local = 0, e_local = 0;
+    int is_ppo = g->is_ppo; uint32_t nc = g->n_cells, na = 0, ow = 0; uint64_t n_local = 0, e_local = 0, layout = 0;
     if (local) {
         int rc = collected_describe(local, &is_ppo, &nc, &na, &n_local, &e_local);
         if (rc || is_ppo != g->is_ppo || nc != g->n_cells) status = 1;          // layout differs from tw_gather_begin's
         ow = tw_collected_obs_width(local);
-        if (!status && n_local == 0) { na = 0; ow = 0; }                        // an empty chunk has no say in the layout
+        if (!rc) { uint32_t os = 0; bool cm = false; collected_obs_layout(local, &os, &cm); layout = (uint64_t)os | ((uint64_t)cm << 32); }
+        if (!status && n_local == 0) { na = 0; ow = 0; layout = 0; }            // an empty chunk has no say in the layout
     }
-    // (records, records of the chunk's last episode, episodes, first global episode, bytes per obs id, actions, status) of every rank
-    uint64_t mine[TW_GATHER_COUNTS] = {status ? 0 : n_local, 0, status ? 0 : e_local, episode_offset, ow, na, status, 0};
+    // (records, records of the chunk's last episode, episodes, first global episode, bytes per obs id, actions, status, obs_size | cell_major << 32)
+    // of every rank
+    uint64_t mine[TW_GATHER_COUNTS] = {status ? 0 : n_local, 0, status ? 0 : e_local, episode_offset, ow, na, status, layout};
     hipStream_t s = c->stream;
     if (local && e_local && !status) {
         // (behind the previous step's transfer on the exchange stream: the wait is the bounded one)
@@ -385,7 +388,12 @@ extern "C" int tw_gather_submit(tw_gather *g, const tw_collected *local, uint64_
     }
     // layout of the records: from the first non-empty chunk any rank has submitted; every later one has to agree
     for (int r = 0; r < world; ++r) if (cnt(r, 0)) {
-        if (!g->obs_width) { g->obs_width = (uint32_t)cnt(r, 4); g->n_actions = (uint32_t)cnt(r, 5); }
+        if (!g->obs_width) { g->obs_width = (uint32_t)cnt(r, 4); g->n_actions = (uint32_t)cnt(r, 5); g->obs_layout = cnt(r, 7); }
+        if (cnt(r, 7) != g->obs_layout) {
+            set_error("tw_gather_submit: rank %d holds obs ids of obs_size %u (cell-major %u), the gather of %u (%u)", r, (uint32_t)cnt(r, 7), (uint32_t)(cnt(r, 7) >> 32),
+                      (uint32_t)g->obs_layout, (uint32_t)(g->obs_layout >> 32));
+            return TW_ERR_INVALID;
+        }
         if (cnt(r, 4) != g->obs_width || cnt(r, 5) != g->n_actions || (g->obs_width != 1 && g->obs_width != 2) || g->n_actions == 0) {
             set_error("tw_gather_submit: rank %d holds %llu-byte obs ids and %llu actions, the gather %u and %u", r, (unsigned long long)cnt(r, 4),
                       (unsigned long long)cnt(r, 5), g->obs_width, g->n_actions);
@@ -477,7 +485,10 @@ extern "C" int tw_gather_finish(tw_gather *g, tw_collected **merged)
             for (int f = 0; f < TW_F_COUNT; ++f) if (g->width[f]) { fp[f] = g->base[f] + a0 * g->width[f]; fb[f] = (size_t)total * g->width[f]; }
             fp[TW_F_EP_LEN] = g->ep_len; fb[TW_F_EP_LEN] = E * 4; fp[TW_F_EP_START] = g->ep_start; fb[TW_F_EP_START] = E * 8;
             rc = collected_adopt(g->arena, g->arena_bytes, c->device, g->is_ppo, g->n_cells, g->n_actions, total, E, fp, fb, merged);
-            if (rc == TW_OK) { g->arena = nullptr; collected_adopt_obs_width(*merged, g->obs_width); }    // owned by the result now
+            if (rc == TW_OK) {                                                                             // owned by the result now
+                g->arena = nullptr; collected_adopt_obs_width(*merged, g->obs_width);
+                collected_adopt_obs_layout(*merged, (uint32_t)g->obs_layout, (g->obs_layout >> 32) != 0);
+            }
         }
     }
     if (g->arena) (void)hipFree(g->arena);

@@ -119,7 +119,7 @@ LaunchOptions launch_options();
 int ensure_dynamic_lds(const void *kernel, size_t bytes);
 // Compute units of the current device (cached per device).
 int device_cus();
-// Test hook (tw_debug_last_launch): the launchers of the self-play / evaluate / solve / big-board kernels report what they launched,
+// Test hook (tw_debug_last_launch): the launchers of the self-play / evaluate / solve / big-board / one-hot kernels report what they launched,
 // from their own template parameters (one host-side store per launch).
 void note_launch(int family, int nt, int nc, int nw, int nwk, bool persist, bool solve, bool dec, bool split, uint32_t blocks, uint32_t threads,
                  uint32_t engine_blocks = 0, uint32_t engine_threads = 0);
@@ -641,7 +641,7 @@ size_t mcts_big_node_bytes();
 int launch_mcts_big(const MctsArgs &a, uint16_t *obs16, hipStream_t s, uint32_t *blocks, uint32_t *threads);
 int launch_finalize_az(const PaddedTraj &in, const uint64_t *ep_start, uint64_t n_episodes, int n_cells,
                        uint8_t *obs_out, float *probs_out, int8_t *perms_out, float *remaining_out, hipStream_t s);
-int launch_onehot(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, float *out, hipStream_t s);
+int launch_onehot(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, bool cell_major, float *out, hipStream_t s);
 int launch_ppo_pack(const float *logits, const uint8_t *actions, const int8_t *perms, const float *advs, uint64_t row0, uint64_t rows,
                     int n_actions, float mean, float denom, int normalize, float *logp_out, int64_t *acts_out, int64_t *perms_out,
                     float *advs_out, hipStream_t s);
@@ -682,6 +682,9 @@ int launch_policy_sync_generic(const GenSyncArgs &a, hipStream_t s);
 int require_device();
 const PolicyDev *policy_dev(const tw_policy *p);
 void collected_adopt_obs_width(tw_collected *c, uint32_t obs_width);
+// what the trainer hand-off needs to know of the obs ids: their range, and whether position k holds an id of cell k's own block
+void collected_adopt_obs_layout(tw_collected *c, uint32_t obs_size, bool cell_major);
+void collected_obs_layout(const tw_collected *c, uint32_t *obs_size, bool *cell_major);
 int policy_device_image(tw_policy *p, void **image, size_t *bytes);       // the one allocation holding every weight image
 int policy_restore_local_tables(tw_policy *p, hipStream_t s);             // ... and what in it is process-local (pointers)
 int collected_describe(const tw_collected *c, int *is_ppo, uint32_t *n_cells, uint32_t *n_actions, uint64_t *n_records, uint64_t *n_episodes);

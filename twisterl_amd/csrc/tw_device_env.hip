@@ -208,6 +208,7 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     rc = collected_adopt(arena, cap, dev_id, 1, NO, A, total, E, fp, bytes, &c);
     if (rc) { (void)hipFree(arena); return rc; }
     collected_adopt_obs_width(c, OW);
+    collected_adopt_obs_layout(c, (uint32_t)pd->obs_size, false);         // an environment's ids: any of [0, obs_size), in any order
 #define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
     CompactTraj ct{};
     ct.obs = nullptr;                                                          // (0 cells: the ids have their own array)

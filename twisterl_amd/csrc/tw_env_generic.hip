@@ -167,6 +167,7 @@ extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *pol
     rc = collected_adopt(arena, cur ? cur : 256, dev_id, 1, NO, A, total, E, fp, bytes, out);
     if (rc) { (void)hipFree(arena); return rc; }
     collected_adopt_obs_width(*out, OW);
+    collected_adopt_obs_layout(*out, (uint32_t)pd->obs_size, false);      // an environment's ids: any of [0, obs_size), in any order
     return TW_OK;
 }
 
@@ -469,6 +470,7 @@ extern "C" int tw_az_collect_env(const tw_env_vtable *env, const tw_policy *poli
     rc = collected_adopt(arena, cur ? cur : 256, dev_id, 0, NO, A, total, E, fp, bytes, out);
     if (rc) { (void)hipFree(arena); return rc; }
     collected_adopt_obs_width(*out, OW);
+    collected_adopt_obs_layout(*out, (uint32_t)pd->obs_size, false);      // an environment's ids: any of [0, obs_size), in any order
     return TW_OK;
 }
 

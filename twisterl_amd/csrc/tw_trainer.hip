@@ -59,7 +59,8 @@ __global__ void __launch_bounds__(256) onehot4_kernel(const uint8_t *obs, uint64
     }
 }
 
-// generic fallback when obs ids are not "cell k owns [k*n2,(k+1)*n2)" (never the case for Puzzle): zero, then scatter
+// the general form, for ids that may be anything in [0, obs_size) in any order, with repeats (an environment's: PyEnv / DeviceEnv, which
+// promise no more than tw_ppo_collect_env checks): zero, then scatter.  The two kernels above run on Puzzle data only (cell_major).
 __global__ void __launch_bounds__(256) onehot_scatter_kernel(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, float *out)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -116,22 +117,29 @@ __global__ void __launch_bounds__(64) sum_partials_kernel(const double *partials
     if (threadIdx.x == 0) *out = acc;
 }
 
-int launch_onehot(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, float *out, hipStream_t s)
+// cell_major: position k of every observation holds an id of [k * n2, (k + 1) * n2) -- known of Puzzle data only (tw_collected); every id
+// is below obs_size (the collectors checked it, tw_collected_pack_trainer checked obs_size), so no form writes outside rows x obs_size
+int launch_onehot(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, bool cell_major, float *out, hipStream_t s)
 {
     if (rows == 0) return TW_OK;
-    if (obs_size % n_cells == 0 && (obs_size / n_cells) % 4 == 0) {
+    const bool blocks_of_ids = cell_major && obs_size % n_cells == 0;
+    if (blocks_of_ids && (obs_size / n_cells) % 4 == 0) {
         constexpr int ROWS = 8;
         uint64_t blocks = (rows + 4 * ROWS - 1) / (4 * ROWS);
         if (blocks > 256ull * 32) blocks = 256ull * 32;
         hipLaunchKernelGGL(onehot4_kernel<ROWS>, dim3((unsigned)blocks), dim3(256), 0, s, obs, row0, rows, n_cells, obs_size, out);
-    } else if (obs_size % n_cells == 0) {
+        note_launch(TW_KERNEL_ONEHOT, 4, 4 * ROWS, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
+    } else if (blocks_of_ids) {
         uint64_t blocks = (rows + 3) / 4;
         if (blocks > 256ull * 32) blocks = 256ull * 32;
         hipLaunchKernelGGL(onehot_kernel, dim3((unsigned)blocks), dim3(256), 0, s, obs, row0, rows, n_cells, obs_size, out);
+        note_launch(TW_KERNEL_ONEHOT, 1, 4, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
     } else {
         TW_HIP(hipMemsetAsync(out, 0, rows * (uint64_t)obs_size * sizeof(float), s));
-        const uint64_t n = rows * (uint64_t)n_cells;
-        hipLaunchKernelGGL(onehot_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, obs, row0, rows, n_cells, obs_size, out);
+        const uint64_t n = rows * (uint64_t)n_cells, blocks = (n + 255) / 256;
+        if (blocks > 0x7fffffffull) { set_error("one-hot hand-off: %llu rows at once", (unsigned long long)rows); return TW_ERR_UNSUPPORTED; }
+        hipLaunchKernelGGL(onehot_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, obs, row0, rows, n_cells, obs_size, out);
+        note_launch(TW_KERNEL_ONEHOT, 0, 0, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
     }
     TW_HIP(hipGetLastError());
     return TW_OK;

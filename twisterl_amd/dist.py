@@ -296,7 +296,8 @@ def _empty_like_fields(template: Dict[str, torch.Tensor]):
 
 def collect_sharded(collector, env, policy, seed: int, dst: int = 0, group=None, gather: bool = True, chunks: int = 1,
                     max_episode_records: Optional[int] = None, gatherer: Optional[TrajectoryGather] = None,
-                    reserve_cus: Optional[int] = None, step_episodes: Optional[int] = None, comm: Optional[Comm] = None):
+                    reserve_cus: Optional[int] = None, step_episodes: Optional[int] = None, comm: Optional[Comm] = None,
+                    as_data: bool = False):
     """Run `collector` (a PPOCollector/AZCollector configured with the GLOBAL num_episodes) over all ranks and gather to
     `dst`.  Returns (merged dict of device tensors on `dst` else None, list of this rank's CollectedData, one per non-empty
     chunk).  chunks > 1 collects in that many pipeline steps so that each step's transfer overlaps with the next step's
@@ -305,7 +306,11 @@ def collect_sharded(collector, env, policy, seed: int, dst: int = 0, group=None,
     can be in flight (default DEFAULT_RESERVE_CUS when pipelining on more than one rank, else 0).  `step_episodes` sets the
     episodes per rank and step instead of `chunks` -- with episodes of equal length a step should be a whole number of
     rounds of the GPU's resident lanes ((CUs - reserve_cus) x 256).  With `comm` (a Comm) the exchange runs inside the library
-    (tw_gather_*: RCCL issued from C++, the path a non-Python host has) instead of torch.distributed's point-to-point ops."""
+    (tw_gather_*: RCCL issued from C++, the path a non-Python host has) instead of torch.distributed's point-to-point ops; with
+    `as_data` the merged result is then returned as the CollectedData itself (what trainer.ppo_data_to_torch takes: it knows the
+    obs_size and the layout of the ranks' chunks), not as its tensors."""
+    if as_data and (comm is None or not gather):
+        raise ValueError("collect_sharded: as_data needs the library's exchange (comm=...)")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     E = int(collector.num_episodes)
@@ -337,7 +342,7 @@ def collect_sharded(collector, env, policy, seed: int, dst: int = 0, group=None,
                 datas.append(d)
             rg.submit(d, a)
         merged = rg.finish()
-        return (merged.to_torch() if merged is not None else None), datas
+        return (merged if as_data or merged is None else merged.to_torch()), datas
     tg = None
     if gather:
         if K > 1 and max_episode_records is None:
