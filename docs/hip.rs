@@ -70,10 +70,14 @@ use crate::rl::env::Env;
     solution: Option<extern "C" fn(*mut c_void, *mut u32, u32) -> u32>,
     set_state: Option<extern "C" fn(*mut c_void, *const i64, u32)>,
     twists: Option<extern "C" fn(*mut c_void, *mut i32, *mut i32, u32) -> u32>,
+    // observations of variable length (optional, trailing; None = observe() and its fixed length): at most `cap` = n_obs ids are
+    // written, their number is returned; n_obs is then the maximum
+    observe_n: Option<extern "C" fn(*mut c_void, *mut i32, u32) -> u32>,
 }
 
 /// tw_launch_info: what tw_debug_last_launch reports (test hook): family (TW_KERNEL_*: 1 mcts_f32, 2 solve_f32, 3 mcts_deep, 4 mcts_big,
-/// 5 solve_big, 6 rollout_big, 7 the one-hot hand-off: nt 4 / 1 / 0 = onehot4 / onehot / scatter, nc = rows per workgroup and trip), the
+/// 5 solve_big, 6 rollout_big, 7 the one-hot hand-off: nt 4 / 1 / 0 / 2 = onehot4 / onehot / scatter / two-byte scatter, nc = rows per workgroup and trip; 5 and 6 with nt 1: the
+/// kernels of a device-environment module), the
 /// kernel's template arguments, its grid, and the engine kernel's grid of the split shape.
 #[repr(C)] #[derive(Default)] pub struct TwLaunchInfo { family: i32, nt: i32, nc: i32, nw: i32, nwk: i32, persist: u32, solve: u32, dec: u32, split: u32,
                                                         blocks: u32, threads: u32, engine_blocks: u32, engine_threads: u32 }
@@ -95,6 +99,7 @@ extern "C" {
     fn tw_collected_num_cells(c: *const c_void) -> u32;
     fn tw_collected_num_actions(c: *const c_void) -> u32;
     fn tw_collected_obs_width(c: *const c_void) -> u32;
+    fn tw_collected_obs_ragged(c: *const c_void) -> c_int;
     fn tw_collected_copy_to_host(c: *const c_void, field: c_int, dst: *mut c_void, bytes: usize) -> c_int;
     fn tw_collected_free(c: *mut c_void);
     // test hooks: the kernel the last self-play / evaluate / solve call launched; (success, total, steps) of every attempt of the last
@@ -155,9 +160,16 @@ extern "C" fn env_destroy(e: *mut c_void) { drop(unsafe { Box::from_raw(e as *mu
 extern "C" fn env_reset(e: *mut c_void, _seed: u64, _episode: u64) { unsafe { (*(e as *mut Box<dyn Env>)).reset() } }
 extern "C" fn env_step(e: *mut c_void, a: u32) { unsafe { (*(e as *mut Box<dyn Env>)).step(a as usize) } }
 extern "C" fn env_observe(e: *mut c_void, out: *mut i32) {
-    // tw_env_vtable.n_obs ids per state, always (include/twisterl_hip.h): an env whose observe() changes length cannot use this path
+    // tw_env_vtable.n_obs ids per state, always (include/twisterl_hip.h): an env whose observe() changes length goes through observe_n
     let obs = unsafe { (*(e as *mut Box<dyn Env>)).observe() };
     for (i, &v) in obs.iter().enumerate() { unsafe { *out.add(i) = v as i32 } }
+}
+// Env::observe as it is -- a Vec of ANY length (tw_env_vtable.observe_n): the ids this state has, at most `cap`; the count goes back
+// as it is, so that a longer observation fails the call instead of being cut
+extern "C" fn env_observe_n(e: *mut c_void, out: *mut i32, cap: u32) -> u32 {
+    let obs = unsafe { (*(e as *mut Box<dyn Env>)).observe() };
+    for (i, &v) in obs.iter().take(cap as usize).enumerate() { unsafe { *out.add(i) = v as i32 } }
+    obs.len() as u32
 }
 extern "C" fn env_masks(e: *mut c_void, out: *mut u8) { let m = unsafe { (*(e as *mut Box<dyn Env>)).masks() }; for (i, &v) in m.iter().enumerate() { unsafe { *out.add(i) = v as u8 } } }
 extern "C" fn env_reward(e: *mut c_void) -> f32 { unsafe { (*(e as *mut Box<dyn Env>)).reward() } }
@@ -186,13 +198,16 @@ extern "C" fn env_twists(e: *mut c_void, obs_perms: *mut i32, act_perms: *mut i3
     op.len() as u32
 }
 
-fn vtable_of(env: &Box<dyn Env>) -> TwEnvVtable {
+/// `max_obs`: None = every state returns as many ids as the prototype does now; Some(m) = observations of 0 .. m ids (m <= 64), e.g. the
+/// indices of the set bits of a bit matrix: the table then carries observe_n and n_obs is the maximum
+fn vtable_of(env: &Box<dyn Env>, max_obs: Option<u32>) -> TwEnvVtable {
     TwEnvVtable {
         prototype: env as *const Box<dyn Env> as *mut c_void,
-        num_actions: env.num_actions() as u32, n_obs: env.observe().len() as u32, obs_size: env.obs_shape().iter().product::<usize>() as u32,
+        num_actions: env.num_actions() as u32, n_obs: max_obs.unwrap_or(env.observe().len() as u32), obs_size: env.obs_shape().iter().product::<usize>() as u32,
         clone: env_clone, destroy: env_destroy, reset: env_reset, step: env_step, observe: env_observe, masks: env_masks,
         reward: env_reward, is_final: env_is_final, success: Some(env_success),
         track_solution: Some(env_track_solution), solution: Some(env_solution), set_state: Some(env_set_state), twists: Some(env_twists),
+        observe_n: max_obs.map(|_| env_observe_n as extern "C" fn(*mut c_void, *mut i32, u32) -> u32),
     }
 }
 
@@ -216,8 +231,9 @@ fn obs_and_logits(h: &Handle) -> Result<(Vec<Vec<usize>>, Vec<Vec<f32>>, Vec<Opt
     let n = unsafe { tw_collected_num_records(h.0) } as usize;
     let nc = unsafe { tw_collected_num_cells(h.0) } as usize;
     let na = unsafe { tw_collected_num_actions(h.0) } as usize;
+    let ragged = unsafe { tw_collected_obs_ragged(h.0) } != 0;                            // variable length: a record's ids, then 0xFFFF = no id
     let obs: Vec<Vec<usize>> = if unsafe { tw_collected_obs_width(h.0) } == 2 {          // ids beyond 255: two bytes each
-        fetch::<u16>(h, F_OBS, n * nc)?.chunks(nc).map(|r| r.iter().map(|&x| x as usize).collect()).collect()
+        fetch::<u16>(h, F_OBS, n * nc)?.chunks(nc).map(|r| r.iter().take_while(|&&x| !(ragged && x == 0xFFFF)).map(|&x| x as usize).collect()).collect()
     } else {
         fetch::<u8>(h, F_OBS, n * nc)?.chunks(nc).map(|r| r.iter().map(|&x| x as usize).collect()).collect()
     };
@@ -228,7 +244,8 @@ fn obs_and_logits(h: &Handle) -> Result<(Vec<Vec<usize>>, Vec<Vec<f32>>, Vec<Opt
 
 // ---------------------------------------------------------------------------------------------- the collectors
 #[derive(Clone)]
-pub struct HipPPOCollector { pub num_episodes: usize, pub gamma: f32, pub lambda: f32, pub num_cores: usize, pub seed: u64, pub max_records: u32 }
+pub struct HipPPOCollector { pub num_episodes: usize, pub gamma: f32, pub lambda: f32, pub num_cores: usize, pub seed: u64, pub max_records: u32,
+                             pub max_obs: Option<u32> /* Some(m): the environment's observations hold 0 .. m ids (vtable_of) */ }
 
 impl Collector for HipPPOCollector {
     fn collect(&self, env: &Box<dyn Env>, policy: &Policy) -> Result<CollectedData> {
@@ -239,7 +256,7 @@ impl Collector for HipPPOCollector {
         let mut out: *mut c_void = std::ptr::null_mut();
         let rc = match puzzle_desc(env) {
             Some(desc) => unsafe { tw_ppo_collect(&desc, pol.0, &prm, &mut out) },
-            None => { let vt = vtable_of(env); unsafe { tw_ppo_collect_env(&vt, pol.0, &prm, self.max_records, &mut out) } }
+            None => { let vt = vtable_of(env, self.max_obs); unsafe { tw_ppo_collect_env(&vt, pol.0, &prm, self.max_records, &mut out) } }
         };
         if rc != 0 { return Err(last_error()); }
         let h = Handle(out);
@@ -257,7 +274,7 @@ impl Collector for HipPPOCollector {
 #[derive(Clone)]
 #[allow(non_snake_case)]
 pub struct HipAZCollector { pub num_episodes: usize, pub num_mcts_searches: usize, pub C: f32, pub max_expand_depth: usize, pub num_cores: usize,
-                            pub seed: u64, pub max_records: u32 }
+                            pub seed: u64, pub max_records: u32, pub max_obs: Option<u32> }
 
 impl Collector for HipAZCollector {
     fn collect(&self, env: &Box<dyn Env>, policy: &Policy) -> Result<CollectedData> {
@@ -268,7 +285,7 @@ impl Collector for HipAZCollector {
         let mut out: *mut c_void = std::ptr::null_mut();
         let rc = match puzzle_desc(env) {
             Some(desc) => unsafe { tw_az_collect(&desc, pol.0, &prm, &mut out) },
-            None => { let vt = vtable_of(env); unsafe { tw_az_collect_env(&vt, pol.0, &prm, self.max_records, &mut out) } }
+            None => { let vt = vtable_of(env, self.max_obs); unsafe { tw_az_collect_env(&vt, pol.0, &prm, self.max_records, &mut out) } }
         };
         if rc != 0 { return Err(last_error()); }
         let h = Handle(out);

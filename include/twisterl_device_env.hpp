@@ -13,13 +13,14 @@
 //   struct MyEnv {                                      // trivially copyable, default-constructible, at most 1 KiB: the prototype AND
 //                                                       // the per-episode state
 //       static constexpr int NUM_ACTIONS = 4;           // 1..4 (EngineV's head has four action columns)
-//       static constexpr int N_OBS       = 25;          // observe() writes EXACTLY this many ids, 1..64
+//       static constexpr int N_OBS       = 25;          // observe() writes EXACTLY this many ids, 1..64 (observe_n(): at most)
 //       __host__ __device__ int      obs_size() const;  // every id < obs_size() <= 65535 (the policy's obs_size)
 //       __host__ __device__ int      difficulty() const;
 //       __host__            void     set_difficulty(int d);
 //       __host__ __device__ void     reset(uint64_t seed, uint64_t episode);   // Env::reset; episode = the GLOBAL episode index
 //       __host__ __device__ void     step(int action);
-//       __host__ __device__ void     observe(int *ids) const;                  // N_OBS ids
+//       __host__ __device__ void     observe(int *ids) const;                  // N_OBS ids            } one of the two
+//       __host__ __device__ int      observe_n(int *ids) const;                // 0..N_OBS ids, returns how many } (see below)
 //       __host__ __device__ uint32_t masks() const;                            // bit i = action i allowed
 //       __host__ __device__ float    reward() const;
 //       __host__ __device__ bool     is_final() const;
@@ -35,6 +36,14 @@
 // collect whose max_records_per_episode is above 1,820 (what the finalize step's LDS tile holds) runs on the host-stepped path.
 // A struct that holds instances of several sizes may add `int n_obs() const`, 1..N_OBS and CONSTANT for the object's lifetime (the
 // library reads it once, from the prototype): observe() then writes that many ids.
+// Observations of VARIABLE length (the reference's Env::observe returns a Vec of any length and its EmbeddingBag adds however many
+// vectors it is given): define observe_n() instead of observe().  It writes the ids of the current state -- at most N_OBS (n_obs()) of
+// them, WHATEVER it returns, in the order the embedding adds them -- and returns their number; 0 is legal (the embedding is then its
+// bias).  Write ids[i] with indices the compiler can resolve after unrolling (slot i = the i-th id, not ids[k++]), or the array goes to
+// scratch memory.  A count outside 0..N_OBS fails the collect ("observation of %u ids, at most %u") without anything being indexed
+// by it.  The collected obs field is then two-byte ids [records][N_OBS], a record's ids first and 0xFFFF in the slots it leaves free
+// (2 x N_OBS bytes per record however short the observation); the module's host vtable carries observe_n, and observe (the ids,
+// then -1) for hosts that only know the fixed-length member.
 #pragma once
 
 #include "twisterl_hip.h"
@@ -52,6 +61,8 @@ struct DeviceEnvModule {
     static_assert(sizeof(T) <= 1024, "twisterl device environment: the struct must be at most 1 KiB (it lives in registers on the device)");
     static_assert(T::NUM_ACTIONS >= 1 && T::NUM_ACTIONS <= 4, "twisterl device environment: NUM_ACTIONS must be 1..4 (EngineV's head has four action columns)");
     static_assert(T::N_OBS >= 1 && T::N_OBS <= 64, "twisterl device environment: N_OBS must be 1..64");
+    static constexpr bool VAR_OBS = EnvHasObserveN<T>::value;
+    static_assert(VAR_OBS || EnvHasObserve<T>::value, "twisterl device environment: the struct needs `void observe(int *ids) const`, or `int observe_n(int *ids) const` for observations of variable length");
     static constexpr int A = T::NUM_ACTIONS, NO = T::N_OBS;
 
     // tw_env_vtable over T (the host-stepped collectors and solve run the same code on the CPU)
@@ -61,9 +72,23 @@ struct DeviceEnvModule {
     static void step(void *e, uint32_t action) { static_cast<T *>(e)->step((int)action); }
     static void observe(void *e, int32_t *out)
     {
-        int ids[NO];
-        static_cast<const T *>(e)->observe(ids);
-        for (int i = 0, n = n_obs_of(e); i < n; ++i) out[i] = (int32_t)ids[i];
+        if constexpr (VAR_OBS) {                                      // for a host that only knows observe(): the ids, then -1 = no id
+            const uint32_t k = observe_n(e, out, (uint32_t)n_obs_of(e));
+            for (int i = (int)k < 0 ? 0 : (int)k, n = n_obs_of(e); i < n; ++i) out[i] = -1;
+        } else if constexpr (EnvHasObserve<T>::value) {
+            int ids[NO];
+            static_cast<const T *>(e)->observe(ids);
+            for (int i = 0, n = n_obs_of(e); i < n; ++i) out[i] = (int32_t)ids[i];
+        }
+    }
+    // tw_env_vtable::observe_n: at most `cap` ids are written; the count is returned as the struct gave it (the caller holds it against cap)
+    static uint32_t observe_n(void *e, int32_t *out, uint32_t cap)
+    {
+        int ids[NO] = {};
+        int k = 0;
+        if constexpr (VAR_OBS) k = static_cast<const T *>(e)->observe_n(ids);
+        for (int i = 0; i < k && i < NO && (uint32_t)i < cap; ++i) out[i] = (int32_t)ids[i];
+        return (uint32_t)k;
     }
     static void masks(void *e, uint8_t *out)
     {
@@ -90,6 +115,7 @@ struct DeviceEnvModule {
         v->num_actions = (uint32_t)A; v->n_obs = (uint32_t)NO;
         v->clone = clone; v->destroy = destroy; v->reset = reset; v->step = step; v->observe = observe; v->masks = masks;
         v->reward = reward; v->is_final = is_final; v->success = success;
+        if (VAR_OBS) v->observe_n = observe_n;
     }
 
     static const tw_device_env *descriptor(const char *type_name)

@@ -35,7 +35,10 @@
 extern "C" {
 #endif
 
-#define TW_ABI_VERSION 6   /* 6: tw_env_vtable grew track_solution / solution / set_state / twists (the rest of `trait Env`), tw_solve_env32 */
+#define TW_ABI_VERSION 6   /* 6: tw_env_vtable grew track_solution / solution / set_state / twists (the rest of `trait Env`), tw_solve_env32.
+                            * Still 6 with tw_env_vtable::observe_n (observations of variable length): a trailing member that may be
+                            * NULL, so a table filled as before means what it meant; a device-environment module built before it is
+                            * refused all the same, through the layout word that holds sizeof(tw_env_vtable) (tw_rollout_env.hpp) */
 
 /* status codes */
 enum {
@@ -97,7 +100,7 @@ int tw_set_launch_option(int option, int value);
 /* Diagnostic counters of the last self-play launch of this process (MctsArgs::eval_count[0..15]); test hook. */
 int tw_debug_counters(uint64_t *out, int n);
 /* Test hook: the kernel the last tw_az_collect / tw_evaluate / tw_solve / big-board tw_ppo_collect / one-hot hand-off
- * (tw_collected_pack_trainer) of this process launched, as its
+ * (tw_collected_pack_trainer) / tw_ppo_collect_device_env / tw_evaluate_device_env of this process launched, as its
  * launcher reports it from its own template parameters (family 0: the call launched none of these kernels).  The arguments a family
  * does not have are 0; the split shape of the walker kernel also reports the grid of its mcts_engine_kernel<nt, nc>. */
 enum {
@@ -106,10 +109,11 @@ enum {
     TW_KERNEL_SOLVE_F32 = 2,    /* solve_f32_kernel<nt, nc, nw>                                  */
     TW_KERNEL_MCTS_DEEP = 3,    /* mcts_deep_kernel<nt, nc, nw, nwk, SOLVE, DEC, SPL>            */
     TW_KERNEL_MCTS_BIG = 4,     /* mcts_big_kernel<nc>                                           */
-    TW_KERNEL_SOLVE_BIG = 5,    /* solve_big_kernel<nc>                                          */
-    TW_KERNEL_ROLLOUT_BIG = 6,  /* rollout_big_kernel<nc>                                        */
-    TW_KERNEL_ONEHOT = 7        /* nt 4: onehot4_kernel<8>, 1: onehot_kernel, 0: memset + onehot_scatter_kernel; nc: the rows a
-                                 * workgroup writes per trip of its loop (32, 4; 0: one id per thread, no loop)                */
+    TW_KERNEL_SOLVE_BIG = 5,    /* solve_big_kernel<nc>; nt 1: solve_env_kernel<Env, nc> of a device-environment module     */
+    TW_KERNEL_ROLLOUT_BIG = 6,  /* rollout_big_kernel<nc>; nt 1: rollout_env_kernel<Env, nc> of a device-environment module */
+    TW_KERNEL_ONEHOT = 7        /* nt 4: onehot4_kernel<8>, 1: onehot_kernel, 0: memset + onehot_scatter_kernel, 2: the same on
+                                 * two-byte ids (0xFFFF = no id, skipped); nc: the rows a workgroup writes per trip of its loop
+                                 * (32, 4; 0: one id per thread, no loop)                                                      */
 };
 typedef struct {
     int32_t  family;            /* TW_KERNEL_*                                                   */
@@ -217,7 +221,9 @@ enum {
 };
 /* Batched Policy.{forward,predict,full_predict} on the device.  Host pointers.
  * obs [n][n_obs] ids, masks [n][n_actions] (0/1), perms [n] (-1 = None; NULL = all None;
- * ignored by FULL_PREDICT).  out_actions [n][n_actions], out_values [n]. */
+ * ignored by FULL_PREDICT).  out_actions [n][n_actions], out_values [n].  An id of -1 means "no id": the slot adds
+ * nothing to the EmbeddingBag's sum (an observation shorter than n_obs; the reference sums the ids it is given,
+ * layers.rs:56-62). */
 int tw_policy_evaluate(const tw_policy *p, int mode, uint32_t precision,
                        const int32_t *obs, uint32_t n, uint32_t n_obs,
                        const uint8_t *masks, const int32_t *perms,
@@ -259,14 +265,15 @@ typedef struct {
 typedef struct {
     void    *prototype;
     uint32_t num_actions;                 /* Env::num_actions (<= 31)                                   */
-    uint32_t n_obs, obs_size;             /* observe() returns EXACTLY n_obs ids for every state, each  */
-                                          /* < obs_size (<= 65535): fixed-length observations only; an  */
-                                          /* id >= obs_size fails the collect (the reference panics)    */
+    uint32_t n_obs, obs_size;             /* observe() returns EXACTLY n_obs (1..64) ids for every      */
+                                          /* state, each < obs_size (<= 65535); with observe_n (below)  */
+                                          /* n_obs is the MAXIMUM number of ids.  An id >= obs_size     */
+                                          /* fails the collect (the reference panics)                   */
     void  *(*clone)(void *env);
     void   (*destroy)(void *env);
     void   (*reset)(void *env, uint64_t seed, uint64_t episode);
     void   (*step)(void *env, uint32_t action);
-    void   (*observe)(void *env, int32_t *out /* n_obs */);
+    void   (*observe)(void *env, int32_t *out /* n_obs */);   /* not called, and may be NULL, when observe_n is set */
     void   (*masks)(void *env, uint8_t *out /* num_actions, 0/1 */);
     float  (*reward)(void *env);
     int    (*is_final)(void *env);
@@ -285,6 +292,12 @@ typedef struct {
                                                                     /* returns how many there are; NULL: none.  Host-side member: */
                                                                     /* the HOST builds the policy with them (tw_policy_create),   */
                                                                     /* as src/twisterl/rl/algorithm.py does from env.twists()     */
+    /* Observations of variable length (Env::observe returns a Vec of any length, rust/src/rl/env.rs; EmbeddingBag adds however   */
+    /* many vectors it is given, layers.rs:56-62).  Optional, trailing: NULL = observe() and its fixed length, as before.  When    */
+    /* set the library calls it INSTEAD of observe, with cap = n_obs: it writes at most `cap` ids, in the order the embedding adds */
+    /* them, and returns how many (0 .. cap; an empty observation is legal).  A return above cap fails the call: "observation of   */
+    /* %u ids, at most %u".  The collected TW_F_OBS is then uint16 [n][n_obs]: the ids of a record first, 0xFFFF in the rest.      */
+    uint32_t (*observe_n)(void *env, int32_t *out, uint32_t cap);
 } tw_env_vtable;
 
 /* solve / evaluate (rust/src/rl/solve.rs:73-101, rust/src/rl/evaluate.rs:22-89; PyO3 functions
@@ -353,7 +366,10 @@ int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t p
 
 /* Fields of the result (device-resident, compact, in the order params.merge_order asked for) */
 enum {
-    TW_F_OBS       = 0,  /* uint8  [n][n_cells]    obs ids (< 256)                             */
+    TW_F_OBS       = 0,  /* uint8  [n][n_cells]    obs ids (< 256); uint16 when                */
+                         /*                        tw_collected_obs_width() is 2; variable-    */
+                         /*                        length observations (tw_collected_obs_      */
+                         /*                        ragged): uint16, 0xFFFF = no id             */
     TW_F_LOGITS    = 1,  /* float  [n][n_actions]  PPO: masked logits; AZ: MCTS probs          */
     TW_F_PERMS     = 2,  /* int8   [n]             -1 = None                                   */
     TW_F_VALUES    = 3,  /* float  [n]             (PPO only)                                  */
@@ -373,6 +389,10 @@ uint32_t tw_collected_num_cells(const tw_collected *c);
 uint32_t tw_collected_num_actions(const tw_collected *c);
 int      tw_collected_is_ppo(const tw_collected *c);
 uint32_t tw_collected_obs_width(const tw_collected *c);   /* bytes per obs id in TW_F_OBS: 1, or 2 for environments with > 256 ids */
+/* 1: the observations vary in length (an environment with observe_n).  TW_F_OBS is then uint16 [n][n_cells] whatever the obs_size,
+ * n_cells = the environment's n_obs (the longest observation): the first k slots of a record hold its ids, the others 0xFFFF (never
+ * an id: obs_size <= 65535).  Dense rows: 2 x n_obs bytes per record however short the observation. */
+int      tw_collected_obs_ragged(const tw_collected *c);
 /* device pointer + byte size of a field (NULL/0 when the collector does not produce it) */
 void    *tw_collected_device_ptr(const tw_collected *c, int field, size_t *bytes);
 int      tw_collected_copy_to_host(const tw_collected *c, int field, void *dst, size_t bytes);
@@ -407,7 +427,9 @@ void tw_collected_free(tw_collected *c);
  *      caller (e.g. torch tensors) and may be NULL; rows [row_begin, row_begin+row_count) of the collected data.
  *  obs_onehot  float [row_count][obs_size]   np_obs[i, obs_i] = 1.0                        (ppo.py:37-39)
  *                                            obs_size must be the one the data was collected with (Puzzle: cells^2; an
- *                                            environment: the policy's), else TW_ERR_INVALID before anything is launched
+ *                                            environment: the policy's), else TW_ERR_INVALID before anything is launched.
+ *                                            One-byte ids: obs_size <= 256; two-byte ids (obs_size up to 65535, and every
+ *                                            result of variable-length observations): zero + scatter, 0xFFFF slots skipped
  *  log_probs   float [row_count]             Categorical(logits).log_prob(actions)          (ppo.py:57-59)  PPO only
  *  actions     int64 [row_count]             (ppo.py:47)                                                    PPO only
  *  perms       int64 [row_count]             -1 = None (ppo.py:50-52)
@@ -470,6 +492,8 @@ int tw_gather_plan(tw_gather_state *st, int world, const uint64_t *counts, int32
                    tw_gather_piece *pieces);
 int tw_gather_begin(tw_comm *c, int root, uint32_t steps, uint64_t max_records, uint32_t max_episode_records,
                     uint64_t total_episodes, int is_ppo, uint32_t n_cells, tw_gather **out);
+/* A chunk of variable-length observations (tw_collected_obs_ragged) is refused with TW_ERR_UNSUPPORTED before anything is exchanged:
+ * the mark does not travel with the counts yet (every rank collects the same environment, so every rank is refused alike). */
 int tw_gather_submit(tw_gather *g, const tw_collected *local, uint64_t episode_offset);
 int tw_gather_finish(tw_gather *g, tw_collected **merged);
 

@@ -5,6 +5,9 @@ with the policy shape of the reference's ppo_grid_world_5x5_v1.json (embedding 5
 device collect is checked byte-equal to the host one first.
 
     python scripts/bench_device_env.py [--reps 5] [--out profiles/r05_device_env.jsonl]
+
+--env lamps40: the same comparison for an environment whose observations vary in length (tests/device_envs/lamps.hpp with 40 lamps:
+0 .. 40 ids per state, obs_size 1,600, at most 24 records per episode; policy 1600-64-64-32 + heads): profiles/r07_var_obs.jsonl.
 """
 import argparse
 import ctypes as C
@@ -23,6 +26,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--episodes", default="1024,65536")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--env", default="gridworld", choices=["gridworld", "lamps40"])
     args = ap.parse_args()
     import numpy as np
     import twisterl_amd
@@ -32,8 +36,14 @@ def main():
     from tests.util import amd_policy, make_deep_policy_arrays
     if twisterl_amd.device_count() < 1:
         raise SystemExit("no GPU")
-    env = gridworld(max_steps=64, difficulty=1, max_records=65)
-    pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
+    if args.env == "lamps40":
+        from tests.var_obs_util import lamps, lamps_policy_arrays
+        env, pol = lamps(40), amd_policy(lamps_policy_arrays(40))
+        env_name, pol_name = "Lamps40 (0..40 ids per state)", "1600-64-64-32+heads (generic)"
+    else:
+        env = gridworld(max_steps=64, difficulty=1, max_records=65)
+        pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
+        env_name, pol_name = "GridWorld5x5", "625-512-128+heads (generic)"
     vt = _lib.EnvVTable()
     _lib.check(_lib.lib().tw_device_env_host_vtable(*env._args(), C.byref(vt)))
 
@@ -64,7 +74,7 @@ def main():
                 recs.append(n)
                 roll.append(c.stats.get("ms_rollout", 0.0))
             k = int(np.argsort(ts)[len(ts) // 2])
-            row = {"env": "GridWorld5x5", "policy": "625-512-128+heads (generic)", "path": path, "episodes": E,
+            row = {"env": env_name, "policy": pol_name, "path": path, "episodes": E,
                    "records": recs[k], "wall_ms": round(ts[k] * 1e3, 3), "records_per_s": round(recs[k] / ts[k], 1),
                    "ms_rollout": round(roll[k], 3) if path == "device" else None, "reps": args.reps, "device": info["name"]}
             rows.append(row)

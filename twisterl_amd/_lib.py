@@ -98,7 +98,10 @@ class EnvVTable(C.Structure):
                 ("track_solution", C.CFUNCTYPE(C.c_int, C.c_void_p)),
                 ("solution", C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32)),
                 ("set_state", C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_int64), C.c_uint32)),
-                ("twists", C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32))]
+                ("twists", C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32)),
+                # observations of variable length (optional, trailing; NULL = observe() and its fixed length): writes at most `cap`
+                # ids, returns how many; n_obs is then the maximum
+                ("observe_n", C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32))]
 
 
 class CommId(C.Structure):
@@ -173,6 +176,7 @@ SYMBOLS = {
     "tw_collected_num_actions": (C.c_uint32, [_VP]),
     "tw_collected_is_ppo": (C.c_int, [_VP]),
     "tw_collected_obs_width": (C.c_uint32, [_VP]),
+    "tw_collected_obs_ragged": (C.c_int, [_VP]),
     "tw_collected_device_ptr": (_VP, [_VP, C.c_int, C.POINTER(C.c_size_t)]),
     "tw_collected_copy_to_host": (C.c_int, [_VP, C.c_int, _VP, C.c_size_t]),
     "tw_collected_stats": (C.c_int, [_VP, C.POINTER(CollectStats)]),
@@ -269,8 +273,8 @@ def debug_counters(n: int = 16) -> list:
 def debug_last_launch() -> dict:
     """The kernel the last self-play / evaluate / solve / big-board PPO / one-hot hand-off call of this process launched, as its launcher
     reported it (tw_debug_last_launch; test hook): family (TW_KERNEL_*), template arguments, grid, and the engine kernel's grid of the
-    split shape.  TW_KERNEL_ONEHOT: nt = 4 / 1 / 0 for onehot4_kernel / onehot_kernel / memset + onehot_scatter_kernel, nc = the rows a
-    workgroup writes per trip of its loop."""
+    split shape.  TW_KERNEL_ONEHOT: nt = 4 / 1 / 0 / 2 for onehot4_kernel / onehot_kernel / memset + onehot_scatter_kernel / the same on
+    two-byte ids, nc = the rows a workgroup writes per trip of its loop."""
     info = LaunchInfo()
     check(lib().tw_debug_last_launch(C.byref(info)))
     return {name: int(getattr(info, name)) for name, _ in LaunchInfo._fields_}

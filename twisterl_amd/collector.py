@@ -32,6 +32,9 @@ _FIELD_NAMES = {
 }
 
 
+NO_ID = 0xFFFF      # "no id" in the two-byte obs field of a result whose observations vary in length (never an id: obs_size <= 65535)
+
+
 class _DeviceResult:
     """Owner of a tw_collected handle."""
 
@@ -44,6 +47,7 @@ class _DeviceResult:
         self.n_actions = int(L.tw_collected_num_actions(handle))
         self.is_ppo = bool(L.tw_collected_is_ppo(handle))
         self.obs_width = int(L.tw_collected_obs_width(handle))      # 2: an environment with more than 256 obs ids
+        self.ragged = bool(L.tw_collected_obs_ragged(handle))       # observations of variable length: uint16 rows, 0xFFFF = no id
         st = _lib.CollectStats()
         _lib.check(L.tw_collected_stats(handle, C.byref(st)))
         self.stats = {k: getattr(st, k) for k, _ in st._fields_}
@@ -101,7 +105,11 @@ class DeviceArray:
 class CollectedData:
     """CollectedData(obs, logits, values, rewards, actions, perms=None) with get/set attributes
     obs, logits, perms, values, rewards, actions, additional_data and the methods merge,
-    get_additional_data_item, set_additional_data_item (python_interface/collector.rs:24-137)."""
+    get_additional_data_item, set_additional_data_item (python_interface/collector.rs:24-137).
+
+    Observations of variable length (an environment with observe_n / max_obs()): `.obs` is a list of lists of differing length,
+    as the reference's; the zero-copy views (`.device_arrays()`, `.to_torch()`, `.to_numpy()`) stay the dense device buffer,
+    uint16 [records, max ids]: a record's ids first, NO_ID (0xFFFF) in the slots it leaves free (`.ragged` says so)."""
 
     def __init__(self, obs, logits, values, rewards, actions, perms=None):
         self._dev = None
@@ -129,7 +137,11 @@ class CollectedData:
         if self._dev is None or self._obs is not None:
             return
         d = self._dev
-        self._obs = d.host(_lib.TW_F_OBS).astype(np.int64).tolist()
+        obs = d.host(_lib.TW_F_OBS)
+        if d.ragged:     # a record's ids first, NO_ID in the slots it leaves free: the reference's lists are just the ids
+            self._obs = [row[:k].tolist() for row, k in zip(obs.astype(np.int64), (obs != NO_ID).sum(axis=1))]
+        else:
+            self._obs = obs.astype(np.int64).tolist()
         self._logits = d.host(_lib.TW_F_LOGITS).tolist()
         self._perms = d.host(_lib.TW_F_PERMS).astype(np.int64).tolist()
         if d.is_ppo:
@@ -193,6 +205,11 @@ class CollectedData:
     @property
     def on_device(self) -> bool:
         return self._dev is not None
+
+    @property
+    def ragged(self) -> bool:
+        """The device buffers hold observations of variable length: dense uint16 rows, NO_ID (0xFFFF) in the free slots."""
+        return self._dev is not None and self._dev.ragged
 
     @property
     def stats(self) -> dict:
@@ -370,20 +387,36 @@ class _PyEnvBridge:
         def f_step(h, a):
             envs[h].next(int(a))
 
-        # The C side hands out buffers of exactly n_obs ids / num_actions flags per state (tw_env_vtable): an environment whose
-        # observe() changes length (legal for the reference's EmbeddingBag, layers.rs:56-62) is refused here instead of writing
-        # past the buffer or leaving stale ids in it -- see PyEnv's docstring.
+        # The C side hands out buffers of n_obs ids / num_actions flags per state (tw_env_vtable).  An environment WITHOUT max_obs()
+        # whose observe() changes length (legal for the reference's EmbeddingBag, layers.rs:56-62) is refused here instead of
+        # writing past the buffer or leaving stale ids in it; one WITH max_obs() goes through f_observe_n -- see PyEnv's docstring.
         @guard()
         def f_observe(h, out_p):
             obs = envs[h].observe()
-            if len(obs) != n_obs:
+            if variable:
+                if len(obs) > n_obs:
+                    raise ValueError(f"PyEnv: observe() returned {len(obs)} ids, max_obs() is {n_obs}")
+                obs = list(obs) + [-1] * (n_obs - len(obs))
+            elif len(obs) != n_obs:
                 raise ValueError(f"PyEnv: observe() returned {len(obs)} ids, the prototype returned {n_obs}; this collector needs a "
                                  "fixed number of obs ids per state")
             for i, v in enumerate(obs):
                 v = int(v)
-                if not 0 <= v < obs_size:
+                if not (0 <= v < obs_size or (variable and v == -1)):
                     raise IndexError(f"PyEnv: obs id {v} outside the obs_shape's {obs_size} ids")      # (the reference panics: layers.rs:61)
                 out_p[i] = v
+
+        @guard(0)
+        def f_observe_n(h, out_p, cap):
+            obs = envs[h].observe()
+            if len(obs) > int(cap):
+                raise ValueError(f"PyEnv: observe() returned {len(obs)} ids, max_obs() is {int(cap)}")
+            for i, v in enumerate(obs):
+                v = int(v)
+                if not 0 <= v < obs_size:
+                    raise IndexError(f"PyEnv: obs id {v} outside the obs_shape's {obs_size} ids")
+                out_p[i] = v
+            return len(obs)
 
         @guard()
         def f_masks(h, out_p):
@@ -423,7 +456,8 @@ class _PyEnvBridge:
         def f_set_state(h, st_p, n):
             envs[h].set_state([int(st_p[i]) for i in range(int(n))])
 
-        n_obs, n_actions = len(proto.observe()), int(proto.num_actions())
+        variable = callable(getattr(proto, "max_obs", None))         # build extension: observations of up to max_obs() ids
+        n_obs, n_actions = (int(proto.max_obs()) if variable else len(proto.observe())), int(proto.num_actions())
         obs_size = 1
         for x in proto.obs_shape():
             obs_size *= int(x)
@@ -440,11 +474,13 @@ class _PyEnvBridge:
 
         fields = dict(V._fields_)
         opt = lambda name, fn: fields[name](fn) if callable(getattr(proto, name, None)) else fields[name]()
-        self._keep = (f_clone, f_destroy, f_reset, f_step, f_observe, f_masks, f_reward, f_final, f_success, f_track, f_solution, f_set_state, f_twists)
+        self._keep = (f_clone, f_destroy, f_reset, f_step, f_observe, f_masks, f_reward, f_final, f_success, f_track, f_solution, f_set_state, f_twists,
+                      f_observe_n)
         self.vt = V(1, n_actions, n_obs, obs_size, fields["clone"](f_clone), fields["destroy"](f_destroy), fields["reset"](f_reset),
                     fields["step"](f_step), fields["observe"](f_observe), fields["masks"](f_masks), fields["reward"](f_reward),
                     fields["is_final"](f_final), fields["success"](f_success),
-                    opt("track_solution", f_track), opt("solution", f_solution), opt("set_state", f_set_state), opt("twists", f_twists))
+                    opt("track_solution", f_track), opt("solution", f_solution), opt("set_state", f_set_state), opt("twists", f_twists),
+                    fields["observe_n"](f_observe_n) if variable else fields["observe_n"]())
         self.max_records = int(getattr(proto, "max_records", 1 << 16))
 
     def finish(self, rc):

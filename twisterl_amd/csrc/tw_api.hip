@@ -931,8 +931,8 @@ extern "C" int tw_policy_evaluate(const tw_policy *p, int mode, uint32_t precisi
     if (n == 0) return TW_OK;
     if (n_obs == 0 || n_obs > 64) { set_error("tw_policy_evaluate: n_obs %u out of range", n_obs); return TW_ERR_INVALID; }
     const int A = p->dev.n_actions;
-    for (size_t i = 0; i < (size_t)n * n_obs; ++i)
-        if (obs[i] < 0 || obs[i] >= p->dev.obs_size) { set_error("index out of bounds: obs id %d, obs_size %d", obs[i], p->dev.obs_size); return TW_ERR_INVALID; }
+    for (size_t i = 0; i < (size_t)n * n_obs; ++i)                                       // (-1: no id in this slot)
+        if (obs[i] < -1 || obs[i] >= p->dev.obs_size) { set_error("index out of bounds: obs id %d, obs_size %d", obs[i], p->dev.obs_size); return TW_ERR_INVALID; }
     if (perms)
         for (uint32_t i = 0; i < n; ++i)
             if (perms[i] >= p->dev.n_perms) { set_error("perm index %d out of range (%d twists)", perms[i], p->dev.n_perms); return TW_ERR_INVALID; }
@@ -967,6 +967,8 @@ struct tw_collected {
     hipStream_t stream = nullptr;           // the library stream of the thread that produced it (tw_set_stream is thread-local)
     uint32_t obs_width = 1;                 // bytes per obs id (2: an environment with more than 256 ids, tw_ppo_collect_env)
     uint32_t obs_size = 0;                  // the ids lie in [0, obs_size): Puzzle n_cells^2, an environment the policy's (0: not recorded)
+    bool ragged = false;                    // observations of variable length (an environment with observe_n): two-byte ids, a record's
+                                            // ids first, 0xFFFF in the slots it leaves free
     bool cell_major = false;                // position k of an observation holds an id of [k * n2, (k + 1) * n2), n2 = obs_size / n_cells:
                                             // what the Puzzle collectors write, and nobody else claims (trainer hand-off, tw_trainer.hip)
     void *field_ptr[TW_F_COUNT] = {};
@@ -983,6 +985,7 @@ extern "C" uint32_t tw_collected_num_cells(const tw_collected *c) { return c ? c
 extern "C" uint32_t tw_collected_num_actions(const tw_collected *c) { return c ? c->n_actions : 0; }
 extern "C" int tw_collected_is_ppo(const tw_collected *c) { return c ? c->is_ppo : 0; }
 extern "C" uint32_t tw_collected_obs_width(const tw_collected *c) { return c ? c->obs_width : 0; }
+extern "C" int tw_collected_obs_ragged(const tw_collected *c) { return c && c->ragged ? 1 : 0; }
 
 extern "C" void *tw_collected_device_ptr(const tw_collected *c, int field, size_t *bytes)
 {
@@ -1044,16 +1047,19 @@ extern "C" int tw_collected_pack_trainer(const tw_collected *c, uint32_t obs_siz
                   (unsigned long long)row_count, (unsigned long long)c->n_records);
         return TW_ERR_INVALID;
     }
-    if (obs_onehot && c->obs_width != 1) { set_error("tw_collected_pack_trainer: one-hot packing exists for one-byte obs ids (obs_size <= 256)"); return TW_ERR_UNSUPPORTED; }
+    if (obs_onehot && c->obs_width != 1 && c->obs_width != 2) { set_error("tw_collected_pack_trainer: obs ids of %u bytes", c->obs_width); return TW_ERR_UNSUPPORTED; }
     // the ids were checked against the obs_size the data was collected with: any other row length would drop ids or write outside the rows
-    if (obs_onehot && (obs_size == 0 || obs_size > 256 || obs_size != c->obs_size)) {
+    // (one-byte ids: at most 256; two-byte ids: at most 65535, so that 0xFFFF is never an id)
+    if (obs_onehot && (obs_size == 0 || obs_size > (c->obs_width == 2 ? 65535u : 256u) || obs_size != c->obs_size)) {
         set_error("tw_collected_pack_trainer: obs_size %u, the data was collected with obs_size %u", obs_size, c->obs_size);
         return TW_ERR_INVALID;
     }
     if ((log_probs || actions || advs) && !c->is_ppo) { set_error("tw_collected_pack_trainer: log_probs / actions / advs exist for PPO data only"); return TW_ERR_INVALID; }
     hipStream_t s = current_stream();
     int rc = TW_OK;
-    if (obs_onehot)
+    if (obs_onehot && c->obs_width == 2)
+        rc = launch_onehot16(reinterpret_cast<const uint16_t *>(c->field_ptr[TW_F_OBS]), row_begin, row_count, (int)c->n_cells, (int)obs_size, obs_onehot, s);
+    else if (obs_onehot)
         rc = launch_onehot(reinterpret_cast<const uint8_t *>(c->field_ptr[TW_F_OBS]), row_begin, row_count, (int)c->n_cells, (int)obs_size, c->cell_major,
                            obs_onehot, s);
     if (rc) return rc;
@@ -1076,6 +1082,7 @@ const PolicyDev *policy_dev(const tw_policy *p) { return &p->dev; }
 void collected_adopt_obs_width(tw_collected *c, uint32_t obs_width) { c->obs_width = obs_width; }
 void collected_adopt_obs_layout(tw_collected *c, uint32_t obs_size, bool cell_major) { c->obs_size = obs_size; c->cell_major = cell_major; }
 void collected_obs_layout(const tw_collected *c, uint32_t *obs_size, bool *cell_major) { *obs_size = c->obs_size; *cell_major = c->cell_major; }
+void collected_adopt_obs_ragged(tw_collected *c) { c->ragged = true; c->obs_width = 2; }
 int policy_device_image(tw_policy *p, void **image, size_t *bytes)
 {
     if (!p || !p->arena) { set_error("policy: no device image"); return TW_ERR_INVALID; }

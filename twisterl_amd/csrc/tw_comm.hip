@@ -353,6 +353,12 @@ extern "C" int tw_gather_submit(tw_gather *g, const tw_collected *local, uint64_
     if (g->st.step >= g->st.steps) { set_error("tw_gather_submit: more submits than steps"); return TW_ERR_INVALID; }
     tw_comm *c = g->c;
     if (c->dead) { set_error("tw_gather_submit: the communicator was aborted"); return TW_ERR_HIP; }
+    // Variable-length observations are not gathered yet: the mark does not travel with the counts, so a ragged chunk is refused here,
+    // before anything is exchanged (every rank collects the same environment and is refused alike).
+    if (local && tw_collected_obs_ragged(local)) {
+        set_error("tw_gather_submit: a chunk of variable-length observations (a ragged result, tw_collected_obs_ragged) cannot be gathered yet");
+        return TW_ERR_UNSUPPORTED;
+    }
     const int world = c->world, rank = c->rank;
     // A chunk that does not fit the gather is reported THROUGH the count exchange (status word), so that every rank sees it and
     // all of them return the error together: a rank that left before the collective would leave the others waiting in it.

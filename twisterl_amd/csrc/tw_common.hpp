@@ -642,6 +642,7 @@ int launch_mcts_big(const MctsArgs &a, uint16_t *obs16, hipStream_t s, uint32_t 
 int launch_finalize_az(const PaddedTraj &in, const uint64_t *ep_start, uint64_t n_episodes, int n_cells,
                        uint8_t *obs_out, float *probs_out, int8_t *perms_out, float *remaining_out, hipStream_t s);
 int launch_onehot(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, bool cell_major, float *out, hipStream_t s);
+int launch_onehot16(const uint16_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, float *out, hipStream_t s);   // two-byte ids, 0xFFFF = none
 int launch_ppo_pack(const float *logits, const uint8_t *actions, const int8_t *perms, const float *advs, uint64_t row0, uint64_t rows,
                     int n_actions, float mean, float denom, int normalize, float *logp_out, int64_t *acts_out, int64_t *perms_out,
                     float *advs_out, hipStream_t s);
@@ -685,6 +686,7 @@ void collected_adopt_obs_width(tw_collected *c, uint32_t obs_width);
 // what the trainer hand-off needs to know of the obs ids: their range, and whether position k holds an id of cell k's own block
 void collected_adopt_obs_layout(tw_collected *c, uint32_t obs_size, bool cell_major);
 void collected_obs_layout(const tw_collected *c, uint32_t *obs_size, bool *cell_major);
+void collected_adopt_obs_ragged(tw_collected *c);     // observations of variable length: two-byte ids, 0xFFFF in the free slots (sets obs_width 2)
 int policy_device_image(tw_policy *p, void **image, size_t *bytes);       // the one allocation holding every weight image
 int policy_restore_local_tables(tw_policy *p, hipStream_t s);             // ... and what in it is process-local (pointers)
 int collected_describe(const tw_collected *c, int *is_ppo, uint32_t *n_cells, uint32_t *n_actions, uint64_t *n_records, uint64_t *n_episodes);

@@ -119,6 +119,7 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     if (!policy || !prm || !out) { set_error("tw_ppo_collect_device_env: null argument"); return TW_ERR_INVALID; }
     *out = nullptr;
     int rc = check_descriptor(env, proto, proto_bytes, "tw_ppo_collect_device_env"); if (rc) return rc;
+    note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);      // (tw_debug_last_launch: nothing yet; the host-stepped path reports nothing)
     const tw_env_vtable vt = host_table(env, proto);
     const PolicyDev *pd = policy_dev(policy);
     // what the kernel does not take: the host-stepped path over the module's own vtable (same bytes; its messages).  Episodes
@@ -132,7 +133,8 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     rc = require_device(); if (rc) return rc;
 
     const uint64_t E = prm->num_episodes;
-    const uint32_t A = env->num_actions, NO = vt.n_obs, OW = pd->obs_size > 256 ? 2u : 1u;
+    const bool ragged = vt.observe_n != nullptr;                          // observations of variable length: two-byte ids, 0xFFFF = no id
+    const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
     const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;
     if (blocks > 0x7fffffffull || t_pad > 0x7fffffffull) { set_error("tw_ppo_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
@@ -162,6 +164,7 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     TW_HIP(hipEventRecord(ev.ev[0], s));
     const int lr = env->launch_rollout(&ra, proto, (unsigned)blocks, lds_bytes, s);
     if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment rollout launch", __FILE__, __LINE__);
+    note_launch(TW_KERNEL_ROLLOUT_BIG, 1, (int)env->engine_nc, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
     TW_HIP(hipEventRecord(ev.ev[1], s));
     rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;
@@ -171,21 +174,23 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     TW_HIP(hipStreamSynchronize(s));
     const uint64_t total = hv[0];
     const uint32_t err = (uint32_t)hv[1];
-    if (err & 1u) {
-        // the id the host path reports: the first it meets -- the smallest record index, then the smallest episode (the kernel
-        // flagged each such episode in ep_len and left the id in that record's value field)
+    if (err & 9u) {
+        // the id (or the count of observe_n) the host path reports: the first it meets -- the smallest record index, then the smallest
+        // episode (the kernel flagged each such episode in ep_len and left the id / the count in that record's value field, which of
+        // the two in its reward field)
         std::vector<uint32_t> len(E);
         TW_HIP(hipMemcpy(len.data(), ra.out.ep_len, E * 4, hipMemcpyDeviceToHost));
         uint64_t first = E;
         for (uint64_t e = 0; e < E; ++e)
             if ((len[e] & 0x80000000u) && (first == E || (len[e] & 0x7fffffffu) < (len[first] & 0x7fffffffu))) first = e;
-        int32_t id = 0;
+        int32_t id = 0; bool count = false;
         if (first < E) {
             PaddedRec r;
             TW_HIP(hipMemcpy(&r, ra.out.rec + first * t_pad + ((len[first] & 0x7fffffffu) - 1u), sizeof(r), hipMemcpyDeviceToHost));
-            id = __builtin_bit_cast(int32_t, r.value);
+            id = __builtin_bit_cast(int32_t, r.value); count = r.reward != 0.0f;
         }
-        set_error("index out of bounds: obs id %d, obs_size %d", (int)id, pd->obs_size);
+        if (count) set_error("observation of %u ids, at most %u", (uint32_t)id, NO);
+        else set_error("index out of bounds: obs id %d, obs_size %d", (int)id, pd->obs_size);
         return TW_ERR_INVALID;
     }
     if (err & 2u) { set_error("tw_ppo_collect_env: an episode did not end within %u records", max_records_per_episode); return TW_ERR_INVALID; }
@@ -209,6 +214,7 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     if (rc) { (void)hipFree(arena); return rc; }
     collected_adopt_obs_width(c, OW);
     collected_adopt_obs_layout(c, (uint32_t)pd->obs_size, false);         // an environment's ids: any of [0, obs_size), in any order
+    if (ragged) collected_adopt_obs_ragged(c);
 #define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
     CompactTraj ct{};
     ct.obs = nullptr;                                                          // (0 cells: the ids have their own array)
@@ -254,6 +260,7 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
 {
     if (!policy || !prm || !success_rate || !mean_reward) { set_error("tw_evaluate_device_env: null argument"); return TW_ERR_INVALID; }
     int rc = check_descriptor(env, proto, proto_bytes, "tw_evaluate_device_env"); if (rc) return rc;
+    note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);
     const tw_env_vtable vt = host_table(env, proto);
     const PolicyDev *pd = policy_dev(policy);
     if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_mcts_searches != 0 || prm->num_searches == 0 || num_episodes == 0 ||
@@ -288,6 +295,7 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
         TW_HIP(hipMemsetAsync(ws + o_err, 0, 16, s));
         const int lr = env->launch_solve(&sa, proto, (unsigned)blocks, lds_bytes, s);
         if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment evaluate launch", __FILE__, __LINE__);
+        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
         TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
         TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
         TW_HIP(hipMemcpyAsync(steps.data(), ws + o_n, NA * 4, hipMemcpyDeviceToHost, s));
@@ -295,12 +303,14 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
         TW_HIP(hipStreamSynchronize(s));
     }
     const uint32_t err = (uint32_t)hv[0];
-    if (err & 1u) {       // the first bad id the host path meets: the smallest move, then the smallest attempt (its total holds the id)
+    if (err & 9u) {       // the first bad id (or count of observe_n) the host path meets: the smallest move, then the smallest attempt
+                          // (its total holds the id / the count; a count: its success is 2.0f)
         uint64_t first = NA;
         for (uint64_t i = 0; i < NA; ++i)
             if ((steps[i] & 0x80000000u) && (first == NA || (steps[i] & 0x7fffffffu) < (steps[first] & 0x7fffffffu))) first = i;
         const int32_t id = first < NA ? __builtin_bit_cast(int32_t, tot[first]) : 0;
-        set_error("index out of bounds: obs id %d, obs_size %d", (int)id, pd->obs_size);
+        if (first < NA && succ[first] == 2.0f) set_error("observation of %u ids, at most %u", (uint32_t)id, vt.n_obs);
+        else set_error("index out of bounds: obs id %d, obs_size %d", (int)id, pd->obs_size);
         return TW_ERR_INVALID;
     }
     if (err & 4u) { set_error("solve: an attempt did not end within %u steps", max_steps ? max_steps : 1u); return TW_ERR_INVALID; }

@@ -16,12 +16,37 @@
 
 using namespace tw;
 
+namespace {
+
+// The observation of one state as a row of NO slots (tw_env_vtable::n_obs): observe() fills all of them; observe_n() the first k, and the
+// others become -1 = no id (the policy kernels skip it, the collected two-byte field shows it as 0xFFFF).  Returns k, which the caller
+// holds against NO ("observation of %u ids, at most %u") before it looks at the ids.
+uint32_t observe_row(const tw_env_vtable *env, void *st, int32_t *row, uint32_t NO)
+{
+    if (!env->observe_n) { env->observe(st, row); return NO; }
+    const uint32_t k = env->observe_n(st, row, NO);
+    for (uint32_t c = k; c < NO; ++c) row[c] = -1;
+    return k;
+}
+
+// ... with the checks of a staging site: the count, then the first k ids
+int observe_checked(const tw_env_vtable *env, void *st, int32_t *row, uint32_t NO, int obs_size)
+{
+    const uint32_t k = observe_row(env, st, row, NO);
+    if (k > NO) { set_error("observation of %u ids, at most %u", k, NO); return TW_ERR_INVALID; }
+    for (uint32_t c = 0; c < k; ++c)
+        if (row[c] < 0 || row[c] >= obs_size) { set_error("index out of bounds: obs id %d, obs_size %d", row[c], obs_size); return TW_ERR_INVALID; }
+    return TW_OK;
+}
+
+}  // namespace
+
 extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *policy, const tw_ppo_params *prm,
                                   uint32_t max_records_per_episode, tw_collected **out)
 {
     if (!env || !policy || !prm || !out) { set_error("tw_ppo_collect_env: null argument"); return TW_ERR_INVALID; }
     *out = nullptr;
-    if (!env->prototype || !env->clone || !env->destroy || !env->reset || !env->step || !env->observe || !env->masks || !env->reward || !env->is_final) {
+    if (!env->prototype || !env->clone || !env->destroy || !env->reset || !env->step || (!env->observe && !env->observe_n) || !env->masks || !env->reward || !env->is_final) {
         set_error("tw_ppo_collect_env: the environment table lacks a method"); return TW_ERR_INVALID;
     }
     if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
@@ -35,7 +60,8 @@ extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *pol
     int rc = require_device(); if (rc) return rc;
 
     const uint64_t E = prm->num_episodes;
-    const uint32_t OW = pd->obs_size > 256 ? 2u : 1u;                      // bytes per obs id in the result
+    const bool ragged = env->observe_n != nullptr;                         // observations of variable length: two-byte ids, 0xFFFF = no id
+    const uint32_t OW = (ragged || pd->obs_size > 256) ? 2u : 1u;          // bytes per obs id in the result
     hipStream_t s = current_stream();
     struct Ep {
         void *env = nullptr; bool alive = true;
@@ -66,11 +92,8 @@ extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *pol
         const uint32_t n = (uint32_t)live.size();
         for (uint32_t r = 0; r < n; ++r) {                                  // get_step_data (ppo.rs:46-48)
             Ep &e = eps[live[r]];
-            env->observe(e.env, &h_obs[(size_t)r * NO]);
-            for (uint32_t c = 0; c < NO; ++c) {
-                const int32_t id = h_obs[(size_t)r * NO + c];
-                if (id < 0 || id >= pd->obs_size) { cleanup(); (void)hipFree(dev); set_error("index out of bounds: obs id %d, obs_size %d", id, pd->obs_size); return TW_ERR_INVALID; }
-            }
+            rc = observe_checked(env, e.env, &h_obs[(size_t)r * NO], NO, pd->obs_size);
+            if (rc) { cleanup(); (void)hipFree(dev); return rc; }
             env->masks(e.env, &h_m[(size_t)r * A]);
             e.rewards.push_back(env->reward(e.env));
             int32_t perm = -1;                                               // get_perm_id (policy.rs:67-77)
@@ -138,7 +161,7 @@ extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *pol
             for (uint32_t c = 0; c < NO; ++c) {
                 const int32_t id = e.obs[tt * NO + c];
                 if (OW == 1) f_obs[(pos + tt) * NO + c] = (uint8_t)id;
-                else { const uint16_t v = (uint16_t)id; memcpy(&f_obs[((pos + tt) * NO + c) * 2], &v, 2); }
+                else { const uint16_t v = (uint16_t)id; memcpy(&f_obs[((pos + tt) * NO + c) * 2], &v, 2); }    // (-1, no id: 0xFFFF)
             }
             memcpy(&f_lg[(pos + tt) * A], &e.logits[tt * A], A * 4);
             f_perm[pos + tt] = (int8_t)e.perms[tt]; f_val[pos + tt] = e.values[tt]; f_rew[pos + tt] = e.rewards[tt];
@@ -168,6 +191,7 @@ extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *pol
     if (rc) { (void)hipFree(arena); return rc; }
     collected_adopt_obs_width(*out, OW);
     collected_adopt_obs_layout(*out, (uint32_t)pd->obs_size, false);      // an environment's ids: any of [0, obs_size), in any order
+    if (ragged) collected_adopt_obs_ragged(*out);
     return TW_OK;
 }
 
@@ -315,11 +339,8 @@ struct HostEvalBatch {
     ~HostEvalBatch() { if (dev) (void)hipFree(dev); }
     int stage(uint32_t r, void *st, int32_t perm)
     {
-        env->observe(st, &h_obs[(size_t)r * NO]);
-        for (uint32_t c = 0; c < NO; ++c) {
-            const int32_t id = h_obs[(size_t)r * NO + c];
-            if (id < 0 || id >= pd->obs_size) { set_error("index out of bounds: obs id %d, obs_size %d", id, pd->obs_size); return TW_ERR_INVALID; }
-        }
+        const int rc = observe_checked(env, st, &h_obs[(size_t)r * NO], NO, pd->obs_size);
+        if (rc) return rc;
         env->masks(st, &h_m[(size_t)r * A]);
         h_perm[r] = perm;
         return TW_OK;
@@ -342,7 +363,7 @@ struct HostEvalBatch {
 
 int check_env_table(const tw_env_vtable *env, const PolicyDev *pd, const char *who)
 {
-    if (!env->prototype || !env->clone || !env->destroy || !env->reset || !env->step || !env->observe || !env->masks || !env->reward || !env->is_final) {
+    if (!env->prototype || !env->clone || !env->destroy || !env->reset || !env->step || (!env->observe && !env->observe_n) || !env->masks || !env->reward || !env->is_final) {
         set_error("%s: the environment table lacks a method", who); return TW_ERR_INVALID;
     }
     const uint32_t A = env->num_actions, NO = env->n_obs;
@@ -367,7 +388,8 @@ extern "C" int tw_az_collect_env(const tw_env_vtable *env, const tw_policy *poli
     rc = require_device(); if (rc) return rc;
     const uint32_t A = env->num_actions, NO = env->n_obs;
     const uint64_t E = prm->num_episodes;
-    const uint32_t OW = pd->obs_size > 256 ? 2u : 1u;
+    const bool ragged = env->observe_n != nullptr;
+    const uint32_t OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     struct Ep {
         void *env = nullptr; bool done = false; uint32_t t = 0; HostMcts mc;
         std::vector<int32_t> obs; std::vector<float> probs, vals;
@@ -398,7 +420,7 @@ extern "C" int tw_az_collect_env(const tw_env_vtable *env, const tw_policy *poli
             const u32x4 w = rng_draw(prm->seed, prm->episode_offset + i, e.t, STREAM_AZ_ACT);
             const int action = sample_weighted_host(mp.data(), (int)A, u32_to_unit(w.x));
             std::vector<int32_t> ob(NO);
-            env->observe(e.env, ob.data());
+            (void)observe_row(env, e.env, ob.data(), NO);                // (the state the move's search was rooted in: staged, and checked, above)
             e.obs.insert(e.obs.end(), ob.begin(), ob.end());
             e.probs.insert(e.probs.end(), mp.begin(), mp.end());
             e.vals.push_back(env->reward(e.env));
@@ -441,7 +463,7 @@ extern "C" int tw_az_collect_env(const tw_env_vtable *env, const tw_policy *poli
             for (uint32_t c = 0; c < NO; ++c) {
                 const int32_t id = e.obs[tt * NO + c];
                 if (OW == 1) f_obs[(pos + tt) * NO + c] = (uint8_t)id;
-                else { const uint16_t v = (uint16_t)id; memcpy(&f_obs[((pos + tt) * NO + c) * 2], &v, 2); }
+                else { const uint16_t v = (uint16_t)id; memcpy(&f_obs[((pos + tt) * NO + c) * 2], &v, 2); }    // (-1, no id: 0xFFFF)
             }
             memcpy(&f_lg[(pos + tt) * A], &e.probs[tt * A], A * 4);
             f_rem[pos + tt] = total_val - before[tt];
@@ -471,6 +493,7 @@ extern "C" int tw_az_collect_env(const tw_env_vtable *env, const tw_policy *poli
     if (rc) { (void)hipFree(arena); return rc; }
     collected_adopt_obs_width(*out, OW);
     collected_adopt_obs_layout(*out, (uint32_t)pd->obs_size, false);      // an environment's ids: any of [0, obs_size), in any order
+    if (ragged) collected_adopt_obs_ragged(*out);
     return TW_OK;
 }
 

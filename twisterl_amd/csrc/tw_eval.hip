@@ -46,6 +46,7 @@ __global__ void __launch_bounds__(EVAL_THREADS) policy_eval_kernel(const PolicyD
             float v = pol.emb_rows[(size_t)bias_row * pol.emb + k];
             for (uint32_t i = 0; i < n_obs; ++i) {
                 int id = obs[(size_t)sample * n_obs + i];
+                if (id < 0) continue;                                    // no id in this slot (a shorter observation): nothing is added
                 if (perm >= 0) id = pol.obs_perms[perm * pol.obs_size + id];
                 v = v + pol.emb_rows[(size_t)id * pol.emb + k];
             }
@@ -146,6 +147,7 @@ __global__ void __launch_bounds__(EVAL_THREADS) policy_eval_generic_kernel(const
             float v = pol.emb_rows[(size_t)pol.obs_size * pol.emb + k];
             for (uint32_t i = 0; i < n_obs; ++i) {
                 int id = obs[(size_t)sample * n_obs + i];
+                if (id < 0) continue;                                    // no id in this slot (a shorter observation): nothing is added
                 if (perm >= 0) id = pol.obs_perms16 ? (int)pol.obs_perms16[(size_t)perm * pol.obs_size + id] : (int)pol.obs_perms[perm * pol.obs_size + id];
                 v = v + pol.emb_rows[(size_t)id * pol.emb + k];
             }

@@ -19,10 +19,12 @@ namespace tw {
 struct EnvRolloutArgs {
     PolicyDev  pol;
     PaddedTraj out;                  // records [E][t_pad]: obs bytes zero (the ids have their own array), logits, value, reward, action | twist
-    uint16_t  *obs16;                // [E][t_pad][n_obs] obs ids as the environment wrote them (before the twist)
+    uint16_t  *obs16;                // [E][t_pad][n_obs] obs ids as the environment wrote them (before the twist); a struct with
+                                     // observe_n: the ids of the record, then 0xFFFF up to the row stride n_obs
     uint32_t  *err;                  // |= 1: an obs id outside [0, obs_size); |= 2: an episode did not end within t_pad records;
-                                     // zeroed by the library before the launch.  An episode that met a bad id at record t ends
-                                     // there: its ep_len is (t + 1) | 1 << 31 and record t's value field holds the id (bits)
+                                     // |= 8: observe_n returned a count outside 0 .. n_obs; zeroed by the library before the launch.
+                                     // An episode that met a bad id (count) at record t ends there: its ep_len is (t + 1) | 1 << 31,
+                                     // record t's value field holds the id (the count) as bits and its reward field is 0.0f (1.0f)
     uint64_t   num_episodes, episode_offset, seed;
 };
 
@@ -32,8 +34,9 @@ struct EnvSolveArgs {
     uint64_t  num_attempts, episode_offset, seed;
     uint32_t  num_searches, deterministic, max_steps, pad;
     float    *success, *total;       // [num_attempts]
-    uint32_t *n_steps;               // [num_attempts]; an attempt that met a bad id at move t: t | 1 << 31, its total = the id (bits)
-    uint32_t *err;                   // as EnvRolloutArgs::err (bit 2: an attempt did not end within max_steps steps)
+    uint32_t *n_steps;               // [num_attempts]; an attempt that met a bad id (a bad count of observe_n) at move t: t | 1 << 31,
+                                     // its total = the id (the count) as bits; a bad count: its success = 2.0f
+    uint32_t *err;                   // as EnvRolloutArgs::err (|= 4: an attempt did not end within max_steps steps)
 };
 
 // EngineV column count for an environment of n_obs ids: the smallest instantiation the Puzzle kernels already use
@@ -78,6 +81,18 @@ template <class Env>
 struct EnvNObs<Env, decltype((void)std::declval<const Env &>().n_obs())> { __host__ __device__ static int of(const Env &e) { return e.n_obs(); } };
 template <class Env>
 __host__ __device__ inline int env_n_obs(const Env &e) { return EnvNObs<Env>::of(e); }
+
+// Observations of variable length: a struct that defines `int observe_n(int *ids) const` (the ids of THIS state, at most env_n_obs
+// of them, and their count) is asked through it, and need not have observe().  Detected as n_obs() is above; a struct without the
+// method compiles to what it compiled to before (every use below is an `if constexpr`).
+template <class Env, class = void>
+struct EnvHasObserveN : std::false_type {};
+template <class Env>
+struct EnvHasObserveN<Env, decltype((void)std::declval<const Env &>().observe_n(std::declval<int *>()))> : std::true_type {};
+template <class Env, class = void>
+struct EnvHasObserve : std::false_type {};
+template <class Env>
+struct EnvHasObserve<Env, decltype((void)std::declval<const Env &>().observe(std::declval<int *>()))> : std::true_type {};
 
 // sample_from_logits (policy.rs:169-172) over the environment's A <= 4 actions: the words of ONE draw (t, STREAM_GUMBEL) as the
 // host path takes them (tw_env_generic.hip), first maximum wins, NaN never; A = 4 is gumbel_argmax4
@@ -129,6 +144,37 @@ __device__ __forceinline__ void env_rows(const Env &st, const PolicyDev &pol, in
     }
 }
 
+// The same for a struct with observe_n: the rows of the ids the state has, -1 beyond them; returns their number.  A count outside
+// 0 .. env_n_obs is never used as an index: no id is read (the count becomes 0), `bad` and `bad_count` are set and `bad_id` is the
+// count (the host path reports it before it looks at an id).  `obs_row` (the rollout's writer lanes; else null): where the record's
+// raw ids go, followed by 0xFFFF = no id up to the row stride env_n_obs -- stored HERE, before the twist: with up to 64 ids and 64 rows
+// alive together the 64-column kernel went to scratch memory.  (Of an observation that turns out to hold a bad id the row is written
+// all the same; the collect fails and nobody reads it.)
+template <class Env, int NC>
+__device__ __forceinline__ int env_rows_n(const Env &st, const PolicyDev &pol, int perm, int (&ids)[Env::N_OBS], int (&rowoff)[NC], bool &bad, int &bad_id,
+                                          bool &bad_count, uint16_t *obs_row)
+{
+    const int stride = env_n_obs(st);
+    int n = st.observe_n(ids);
+    if ((unsigned)n > (unsigned)stride) { bad = true; bad_count = true; bad_id = n; n = 0; }
+    else if (obs_row) {
+#pragma unroll
+        for (int i = 0; i < Env::N_OBS; ++i) if (i < stride) obs_row[i] = i < n ? (uint16_t)ids[i] : (uint16_t)0xFFFFu;
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        int row = -1;
+        if (i < Env::N_OBS && i < n) {
+            const int id = ids[i];
+            if ((unsigned)id >= (unsigned)pol.obs_size) { if (!bad) bad_id = id; bad = true; }
+            else row = perm < 0 ? id : (pol.obs_size > 256 ? (int)pol.obs_perms16[(size_t)perm * pol.obs_size + id]
+                                                            : (int)pol.obs_perms[(size_t)perm * pol.obs_size + id]);
+        }
+        rowoff[i] = row;
+    }
+    return n;
+}
+
 template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArgs a, const Env proto)
 {
@@ -156,8 +202,13 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
         }
         int ids[NO], rowoff[NC];
         bool bad = false; int bad_id = 0;
-        if (alive) env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
-        else {
+        [[maybe_unused]] bool bad_count = false;                                      // (a struct with observe_n: a count outside 0 .. n_obs)
+        if (alive) {
+            if constexpr (EnvHasObserveN<Env>::value)
+                (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count,
+                                          writer ? a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)env_n_obs(st) : nullptr);
+            else env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+        } else {
 #pragma unroll
             for (int i = 0; i < NC; ++i) rowoff[i] = -1;
         }
@@ -174,8 +225,8 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
             if (bad) {                                                                // (the host path fails the collect here)
                 if (writer) {                                                         // the library names the first one (t, episode)
                     const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
-                    store_rec(a.out.rec + e_local * (uint64_t)a.out.t_pad + (uint64_t)t, zero4, lg, __builtin_bit_cast(float, bad_id), 0.0f, 0, -1);
-                    atomicOr(a.err, 1u);
+                    store_rec(a.out.rec + e_local * (uint64_t)a.out.t_pad + (uint64_t)t, zero4, lg, __builtin_bit_cast(float, bad_id), bad_count ? 1.0f : 0.0f, 0, -1);
+                    atomicOr(a.err, bad_count ? 8u : 1u);
                 }
                 failed = true;
                 alive = false;
@@ -184,10 +235,12 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
                     const uint64_t rec = e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
                     const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
                     store_rec(a.out.rec + rec, zero4, lg, value, rew, action, perm);
-                    const int n = env_n_obs(st);
-                    uint16_t *o = a.obs16 + rec * (uint64_t)n;
+                    if constexpr (!EnvHasObserveN<Env>::value) {                      // (observe_n: env_rows_n has stored them)
+                        const int n = env_n_obs(st);
+                        uint16_t *o = a.obs16 + rec * (uint64_t)n;
 #pragma unroll
-                    for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
+                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
+                    }
                 }
                 if (st.is_final()) alive = false;                                     // ppo.rs:78
                 else if (t + 1 >= a.out.t_pad) {                                      // the host path's max_records_per_episode
@@ -221,6 +274,7 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
     bool  alive = valid && !st.is_final(), failed = false;                            // solve.rs:29
     float total = 0.0f;
     int   bad_first = 0;
+    [[maybe_unused]] bool bad_first_count = false;
     int   t = 0;
     eng.begin2();
     while (__syncthreads_or(alive ? 1 : 0)) {
@@ -231,8 +285,11 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
         }
         int ids[NO], rowoff[NC];
         bool bad = false; int bad_id = 0;
-        if (alive) env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
-        else {
+        [[maybe_unused]] bool bad_count = false;
+        if (alive) {
+            if constexpr (EnvHasObserveN<Env>::value) (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count, nullptr);
+            else env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+        } else {
 #pragma unroll
             for (int i = 0; i < NC; ++i) rowoff[i] = -1;
         }
@@ -244,7 +301,12 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
         masked_softmax4(lg, mb, probs);                                               // policy.rs:43-47 (masked entries add +0.0)
         if (alive) {
             if (bad) {
-                if (writer) atomicOr(a.err, 1u);
+                if constexpr (EnvHasObserveN<Env>::value) {
+                    if (writer) atomicOr(a.err, bad_count ? 8u : 1u);
+                    bad_first_count = bad_count;
+                } else {
+                    if (writer) atomicOr(a.err, 1u);
+                }
                 failed = true; bad_first = bad_id;
                 alive = false;
             } else {
@@ -271,6 +333,7 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
     if (valid && writer) {
         total = total + st.reward();                                                  // solve.rs:65-66
         a.success[att] = st.success() ? 1.0f : 0.0f;                                  // solve.rs:68
+        if constexpr (EnvHasObserveN<Env>::value) { if (bad_first_count) a.success[att] = 2.0f; }
         a.total[att]   = failed ? __builtin_bit_cast(float, bad_first) : total;
         a.n_steps[att] = (uint32_t)t | (failed ? 0x80000000u : 0u);
     }

@@ -60,13 +60,22 @@ __global__ void __launch_bounds__(256) onehot4_kernel(const uint8_t *obs, uint64
 }
 
 // the general form, for ids that may be anything in [0, obs_size) in any order, with repeats (an environment's: PyEnv / DeviceEnv, which
-// promise no more than tw_ppo_collect_env checks): zero, then scatter.  The two kernels above run on Puzzle data only (cell_major).
-__global__ void __launch_bounds__(256) onehot_scatter_kernel(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, float *out)
+// promise no more than tw_ppo_collect_env checks): zero, then scatter, one thread per slot.  The two kernels above run on Puzzle data
+// only (cell_major).  id_bytes 2: two-byte ids (environments with more than 256 ids; every result of variable-length observations,
+// whose free slots hold 0xFFFF) -- an id is below obs_size <= 65535 (the collectors checked it), so the one comparison both skips the
+// free slots and keeps every store inside its row.
+__global__ void __launch_bounds__(256) onehot_scatter_kernel(const uint8_t *obs, int id_bytes, uint64_t row0, uint64_t rows, int n_cells, int obs_size,
+                                                             float *out)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= rows * (uint64_t)n_cells) return;
-    const uint64_t r = i / n_cells;
-    out[r * (uint64_t)obs_size + obs[row0 * (uint64_t)n_cells + i]] = 1.0f;
+    const uint64_t r = i / n_cells, slot = row0 * (uint64_t)n_cells + i;
+    int id;
+    if (id_bytes == 2) {
+        id = (int)reinterpret_cast<const uint16_t *>(obs)[slot];
+        if (id >= obs_size) return;                                      // 0xFFFF: no id in this slot
+    } else id = (int)obs[slot];
+    out[r * (uint64_t)obs_size + id] = 1.0f;
 }
 
 // thread per row: log-prob of the taken action, int64 widening, optional advantage normalisation
@@ -138,9 +147,22 @@ int launch_onehot(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells,
         TW_HIP(hipMemsetAsync(out, 0, rows * (uint64_t)obs_size * sizeof(float), s));
         const uint64_t n = rows * (uint64_t)n_cells, blocks = (n + 255) / 256;
         if (blocks > 0x7fffffffull) { set_error("one-hot hand-off: %llu rows at once", (unsigned long long)rows); return TW_ERR_UNSUPPORTED; }
-        hipLaunchKernelGGL(onehot_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, obs, row0, rows, n_cells, obs_size, out);
+        hipLaunchKernelGGL(onehot_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, obs, 1, row0, rows, n_cells, obs_size, out);
         note_launch(TW_KERNEL_ONEHOT, 0, 0, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
     }
+    TW_HIP(hipGetLastError());
+    return TW_OK;
+}
+
+// two-byte ids, 0xFFFF = no id (tw_collected::obs_width == 2): any obs_size up to 65535; the scatter kernel's two-byte form
+int launch_onehot16(const uint16_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, float *out, hipStream_t s)
+{
+    if (rows == 0) return TW_OK;
+    TW_HIP(hipMemsetAsync(out, 0, rows * (uint64_t)obs_size * sizeof(float), s));
+    const uint64_t n = rows * (uint64_t)n_cells, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffull) { set_error("one-hot hand-off: %llu rows at once", (unsigned long long)rows); return TW_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(onehot_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const uint8_t *>(obs), 2, row0, rows, n_cells, obs_size, out);
+    note_launch(TW_KERNEL_ONEHOT, 2, 0, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
     TW_HIP(hipGetLastError());
     return TW_OK;
 }

@@ -327,7 +327,11 @@ def collect_sharded(collector, env, policy, seed: int, dst: int = 0, group=None,
         if hasattr(local, "reserve_cus"):
             # nothing is collected after the last step, so it has no later transfer to make room for: it runs on every CU
             local.reserve_cus = 0 if last_step else int(reserve_cus)
-        return local.collect(env, policy, seed=seed)
+        d = local.collect(env, policy, seed=seed)
+        if gather and getattr(d, "ragged", False):
+            raise RuntimeError("collect_sharded: variable-length observations (a ragged result) cannot be gathered yet "
+                               "(tw_gather_submit refuses them); collect per rank with gather=False")
+        return d
 
     if gather and comm is not None:
         from .env import get_env_desc

@@ -142,10 +142,13 @@ class PyEnv:
     Its code runs on the host -- as in the reference -- while the policy forward of all live episodes of a time step is one
     batched launch on the GPU (tw_ppo_collect_env).  Build extension: if `pyenv` has seed_episode(seed, episode) it is
     called before every reset(), so that a collect is reproducible (the reference's envs draw from OS entropy).
-    Restriction: observe() must return the SAME NUMBER of ids for every state (the prototype's) and masks() one flag per
-    action -- the C side's per-state buffers have that size (tw_env_vtable.n_obs); the reference's EmbeddingBag would also
-    take observations of varying length (layers.rs:56-62).  A different length, or an id outside obs_shape, raises from
-    collect() / evaluate() / solve()."""
+    Observation length: by default observe() must return the SAME NUMBER of ids for every state (the prototype's) and masks()
+    one flag per action -- the C side's per-state buffers have that size (tw_env_vtable.n_obs).  An environment whose
+    observations vary in length, which the reference's EmbeddingBag takes as they come (layers.rs:56-62), says so by defining
+    max_obs() -> the largest number of ids any state returns, 1..64 (build extension, like seed_episode): observe() may then
+    return 0 .. max_obs() ids, the policy sums the vectors of exactly those, and the collected `.obs` is a list of lists of
+    differing length (the device buffer: dense uint16 rows, 0xFFFF in the free slots -- CollectedData).  A length above
+    max_obs(), a changing length without max_obs(), or an id outside obs_shape raises from collect() / evaluate() / solve()."""
 
     def __init__(self, pyenv):
         for m in ("copy", "num_actions", "obs_shape", "reset", "next", "masks", "is_final", "value", "observe"):
@@ -239,7 +242,8 @@ class DeviceEnv:
 
     `max_records`: the longest episode a collect accepts (a longer one fails it, as on the host-stepped path).  Set it to the
     environment's own bound (GridWorld: max_steps + 1): the device collect's padded workspace holds num_episodes x max_records x
-    (48 + 2 x n_obs) bytes -- 65,536 GridWorld 5 x 5 episodes at the default 256: 1.6 GB.  Above 1,820 records the collect runs on
+    (48 + 2 x n_obs) bytes (n_obs: the longest observation, for a struct with observe_n) -- 65,536 GridWorld 5 x 5 episodes at the
+    default 256: 1.6 GB.  Above 1,820 records the collect runs on
     the host-stepped path (the finalize step's LDS tile)."""
 
     def __init__(self, module_path: str, name: str, params=(), *, max_records: int = 256):
@@ -300,10 +304,16 @@ class DeviceEnv:
     def obs_size(self) -> int:
         return int(self._desc.obs_size(self._obj))
 
+    @property
+    def variable_obs(self) -> bool:
+        """The struct defines observe_n(): its observations hold 0 .. n_obs ids."""
+        return bool(self._vt.observe_n)
+
     def obs_shape(self) -> list:
-        """[n_obs, obs_size / n_obs] when that divides (GridWorld: [w*h, w*h], lib.rs obs_shape), else [obs_size]."""
+        """[n_obs, obs_size / n_obs] when that divides (GridWorld: [w*h, w*h], lib.rs obs_shape), else [obs_size]; [obs_size] for
+        an environment whose observations vary in length (n_obs is then only their maximum)."""
         n, s = self.n_obs, self.obs_size
-        return [n, s // n] if s % n == 0 else [s]
+        return [n, s // n] if s % n == 0 and not self.variable_obs else [s]
 
     @property
     def difficulty(self) -> int:
@@ -334,6 +344,11 @@ class DeviceEnv:
 
     def observe(self) -> list:
         out = (C.c_int32 * self.n_obs)()
+        if self.variable_obs:                     # the ids this state has
+            k = int(self._vt.observe_n(self._obj, out, self.n_obs))
+            if k > self.n_obs:
+                raise ValueError(f"observation of {k} ids, at most {self.n_obs}")
+            return [int(x) for x in out[:k]]
         self._vt.observe(self._obj, out)
         return [int(x) for x in out]
 
