@@ -76,8 +76,8 @@ use crate::rl::env::Env;
 }
 
 /// tw_launch_info: what tw_debug_last_launch reports (test hook): family (TW_KERNEL_*: 1 mcts_f32, 2 solve_f32, 3 mcts_deep, 4 mcts_big,
-/// 5 solve_big, 6 rollout_big, 7 the one-hot hand-off: nt 4 / 1 / 0 / 2 = onehot4 / onehot / scatter / two-byte scatter, nc = rows per workgroup and trip; 5 and 6 with nt 1: the
-/// kernels of a device-environment module), the
+/// 5 solve_big, 6 rollout_big, 7 the one-hot hand-off: nt 4 / 1 / 0 / 2 = onehot4 / onehot / scatter / two-byte scatter, nc = rows per workgroup and trip; 4, 5 and 6 with nt 1: the
+/// kernels of a device-environment module -- mcts_env_kernel, solve_env_kernel, rollout_env_kernel), the
 /// kernel's template arguments, its grid, and the engine kernel's grid of the split shape.
 #[repr(C)] #[derive(Default)] pub struct TwLaunchInfo { family: i32, nt: i32, nc: i32, nw: i32, nwk: i32, persist: u32, solve: u32, dec: u32, split: u32,
                                                         blocks: u32, threads: u32, engine_blocks: u32, engine_threads: u32 }

@@ -7,7 +7,8 @@
 //
 //     twisterl_amd.build.build_device_env("my_env.hpp", "MyEnv", "my_env")      # -> libtw_env_my_env.so
 //
-// which compiles `#include "my_env.hpp"` + `TW_DEVICE_ENV(MyEnv, my_env)` with the library's own flags, and loaded with
+// which compiles `#include "my_env.hpp"` + `TW_DEVICE_ENV(MyEnv, my_env)` with the library's own flags (search=True:
+// TW_DEVICE_ENV_SEARCH, which adds the self-play / MCTS-evaluate kernel -- at the end of this file), and loaded with
 // twisterl_amd.env.DeviceEnv(path, "my_env", params=[...]).  The contract (checked by static_assert below):
 //
 //   struct MyEnv {                                      // trivially copyable, default-constructible, at most 1 KiB: the prototype AND
@@ -31,7 +32,9 @@
 // Randomness: tw::env_draw(seed, episode, index) -> four 32-bit words (Philox4x32-10 on stream 6).  The environment
 // chooses its own `index` values, e.g. the draw number in reset() and (t << 8) | k in step(); tw::u32_below(word, n) gives an
 // integer in [0, n), tw::u32_to_unit(word) a float in [0, 1).  Everything a method reads must be in the struct: no pointers to host
-// memory, no globals, no virtual functions.  An id outside [0, obs_size()) fails the collect ("index out of bounds: obs id ..."), an
+// memory, no globals, no virtual functions.  step() in particular depends on the struct and the action ALONE -- a step-time draw is
+// keyed by what the struct holds, e.g. its own step counter: the search kernel (TW_DEVICE_ENV_SEARCH below) re-derives a tree
+// node's state by replaying the actions from the move's root, where the host path keeps a clone per node, and the two must agree.  An id outside [0, obs_size()) fails the collect ("index out of bounds: obs id ..."), an
 // episode that has not ended within the collect's max_records_per_episode records fails it too -- as on the host-stepped path.  A
 // collect whose max_records_per_episode is above 1,820 (what the finalize step's LDS tile holds) runs on the host-stepped path.
 // A struct that holds instances of several sizes may add `int n_obs() const`, 1..N_OBS and CONSTANT for the object's lifetime (the
@@ -48,6 +51,7 @@
 
 #include "twisterl_hip.h"
 #include "tw_rollout_env.hpp"
+#include "tw_mcts_env.hpp"
 
 #include <new>
 #include <type_traits>
@@ -118,9 +122,9 @@ struct DeviceEnvModule {
         if (VAR_OBS) v->observe_n = observe_n;
     }
 
-    static const tw_device_env *descriptor(const char *type_name)
+    static const tw_device_env *descriptor(const char *type_name, decltype(tw_device_env::launch_search) search = nullptr)
     {
-        static const tw_device_env d = [type_name]() {
+        static const tw_device_env d = [type_name, search]() {
             tw_device_env x{};
             tw_device_env_layout(x.layout);
             x.num_actions = (uint32_t)A; x.n_obs = (uint32_t)NO; x.state_bytes = (uint32_t)sizeof(T); x.engine_nc = (uint32_t)env_engine_nc(NO);
@@ -128,6 +132,7 @@ struct DeviceEnvModule {
             x.launch_rollout = launch_rollout_env<T>; x.launch_solve = launch_solve_env<T>;
             x.create = create; x.get_difficulty = get_difficulty; x.set_difficulty = set_difficulty; x.obs_size = obs_size; x.n_obs_of = n_obs_of;
             x.fill_vtable = fill_vtable;
+            x.launch_search = search;                                     // (TW_DEVICE_ENV: null, and no third kernel in the module)
             return x;
         }();
         return &d;
@@ -142,4 +147,17 @@ struct DeviceEnvModule {
     extern "C" __attribute__((visibility("default"))) const tw_device_env *tw_device_env_##name(void)      \
     {                                                                                                       \
         return ::tw::DeviceEnvModule<Type>::descriptor(#Type);                                              \
+    }
+
+// The same, and the module also holds mcts_env_kernel (twisterl_amd/csrc/tw_mcts_env.hpp) with its launcher: AZCollector.collect and
+// evaluate with num_mcts_searches > 0 then run on the device too.  That kernel keeps TWO copies of the struct in a lane's registers
+// (the episode's state and the one that walks the tree), so the struct may have at most TW_DEVICE_ENV_SEARCH_MAX_BYTES = 128 bytes
+// here.  build_device_env(..., search=True) emits this form.
+#define TW_DEVICE_ENV_SEARCH_MAX_BYTES 128
+#define TW_DEVICE_ENV_SEARCH(Type, name)                                                                    \
+    static_assert(sizeof(Type) <= TW_DEVICE_ENV_SEARCH_MAX_BYTES,                                           \
+                  "twisterl device environment: TW_DEVICE_ENV_SEARCH needs a struct of at most 128 bytes (the search kernel keeps two copies in registers)"); \
+    extern "C" __attribute__((visibility("default"))) const tw_device_env *tw_device_env_##name(void)      \
+    {                                                                                                       \
+        return ::tw::DeviceEnvModule<Type>::descriptor(#Type, ::tw::launch_mcts_env<Type>);                 \
     }

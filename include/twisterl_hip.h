@@ -100,7 +100,7 @@ int tw_set_launch_option(int option, int value);
 /* Diagnostic counters of the last self-play launch of this process (MctsArgs::eval_count[0..15]); test hook. */
 int tw_debug_counters(uint64_t *out, int n);
 /* Test hook: the kernel the last tw_az_collect / tw_evaluate / tw_solve / big-board tw_ppo_collect / one-hot hand-off
- * (tw_collected_pack_trainer) / tw_ppo_collect_device_env / tw_evaluate_device_env of this process launched, as its
+ * (tw_collected_pack_trainer) / tw_ppo_collect_device_env / tw_az_collect_device_env / tw_evaluate_device_env of this process launched, as its
  * launcher reports it from its own template parameters (family 0: the call launched none of these kernels).  The arguments a family
  * does not have are 0; the split shape of the walker kernel also reports the grid of its mcts_engine_kernel<nt, nc>. */
 enum {
@@ -108,7 +108,7 @@ enum {
     TW_KERNEL_MCTS_F32 = 1,     /* mcts_f32_kernel<nt, nc, nw, PERSIST>                          */
     TW_KERNEL_SOLVE_F32 = 2,    /* solve_f32_kernel<nt, nc, nw>                                  */
     TW_KERNEL_MCTS_DEEP = 3,    /* mcts_deep_kernel<nt, nc, nw, nwk, SOLVE, DEC, SPL>            */
-    TW_KERNEL_MCTS_BIG = 4,     /* mcts_big_kernel<nc>                                           */
+    TW_KERNEL_MCTS_BIG = 4,     /* mcts_big_kernel<nc>; nt 1: mcts_env_kernel<Env, nc> of a device-environment module       */
     TW_KERNEL_SOLVE_BIG = 5,    /* solve_big_kernel<nc>; nt 1: solve_env_kernel<Env, nc> of a device-environment module     */
     TW_KERNEL_ROLLOUT_BIG = 6,  /* rollout_big_kernel<nc>; nt 1: rollout_env_kernel<Env, nc> of a device-environment module */
     TW_KERNEL_ONEHOT = 7        /* nt 4: onehot4_kernel<8>, 1: onehot_kernel, 0: memset + onehot_scatter_kernel, 2: the same on
@@ -353,13 +353,18 @@ int tw_solve_env32(const tw_env_vtable *env, const tw_policy *policy, const tw_s
  * (twisterl_amd.build.build_device_env) that exports `const tw_device_env *tw_device_env_<name>(void)`.  `proto` points to the
  * environment struct (proto_bytes = its size), the prototype every episode clones and resets.  The library refuses a descriptor
  * built against another layout.  tw_ppo_collect_device_env / tw_evaluate_device_env run the whole loop in one kernel (the policy on
- * EngineV, f32); what that kernel does not take -- a policy of the MFMA shape, another precision, evaluate with MCTS -- runs on the
- * host-stepped path over the module's own vtable (tw_ppo_collect_env / tw_evaluate_env: same bytes, same errors). */
+ * EngineV, f32); what that kernel does not take -- a policy of the MFMA shape, another precision -- runs on the host-stepped path over
+ * the module's own vtable (tw_ppo_collect_env / tw_az_collect_env / tw_evaluate_env: same bytes, same errors).  Self-play
+ * (tw_az_collect_device_env) and evaluate with num_mcts_searches > 0 run in one kernel too when the module was built with
+ * TW_DEVICE_ENV_SEARCH (build_device_env(search=True): its descriptor then holds the search kernel's launcher), and on the
+ * host-stepped path otherwise; so does self-play with max_records_per_episode above 2,048 (the finalize step's LDS tile). */
 typedef struct tw_device_env tw_device_env;
 /* fills `out` with the module's host methods over `proto` (borrowed: it must outlive every use of `out`); no device needed */
 int tw_device_env_host_vtable(const tw_device_env *env, const void *proto, size_t proto_bytes, tw_env_vtable *out);
 int tw_ppo_collect_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
                               const tw_ppo_params *params, uint32_t max_records_per_episode, tw_collected **out);
+int tw_az_collect_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                             const tw_az_params *params, uint32_t max_records_per_episode, tw_collected **out);
 int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
                            const tw_solve_params *params, uint64_t num_episodes, uint64_t episode_offset, uint32_t max_steps,
                            float *success_rate, float *mean_reward);

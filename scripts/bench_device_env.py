@@ -8,6 +8,13 @@ device collect is checked byte-equal to the host one first.
 
 --env lamps40: the same comparison for an environment whose observations vary in length (tests/device_envs/lamps.hpp with 40 lamps:
 0 .. 40 ids per state, obs_size 1,600, at most 24 records per episode; policy 1600-64-64-32 + heads): profiles/r07_var_obs.jsonl.
+
+--az: self-play instead.  Whole AZCollector.collect calls of GridWorld 5 x 5 with the same policy, --az-shape episodes x searches
+(4096x100; if the first call takes more than a minute the run goes on at 1024x32 and says so), median of --reps: ONE row, whose
+"path" is what the call ran on -- "device" when the library reports the module's search kernel (a module built with search=True),
+else "host_stepped".  The comparison is this command on two trees: --tree names the checkout whose package, tests/ helpers and
+built library are measured (default: the tree the script lies in); a tree from before the search kernel builds the plain module
+and its collect is host-stepped.  profiles/r08_device_env_search.jsonl holds the two rows.
 """
 import argparse
 import ctypes as C
@@ -17,7 +24,58 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv[1:-1]:
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 sys.path.insert(0, ROOT)
+
+
+def az(args):
+    """One row: AZCollector.collect of GridWorld 5 x 5 on the path this tree takes for it."""
+    import inspect
+    import numpy as np
+    import twisterl_amd
+    from twisterl_amd import _lib, twisterl
+    from twisterl_amd.build import build_device_env
+    from twisterl_amd.env import DeviceEnv
+    from tests.device_env_util import GRIDWORLD_HPP
+    from tests.util import amd_policy, make_deep_policy_arrays
+    if twisterl_amd.device_count() < 1:
+        raise SystemExit("no GPU")
+    can_search = "search" in inspect.signature(build_device_env).parameters
+    name = "gridworld5x5_az" if can_search else "gridworld5x5"
+    so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if can_search else {}))
+    env = DeviceEnv(so, name, [5, 5, 64, 1], max_records=65)
+    pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
+    E, S = (int(x) for x in args.az_shape.lower().split("x"))
+
+    def collect(seed):
+        t0 = time.perf_counter()
+        c = twisterl.collector.AZCollector(E, S, 1.41, 1, 32).collect(env, pol, seed=seed)
+        n = len(c)
+        return time.perf_counter() - t0, n, c.stats
+
+    fell_back = False
+    t, _, _ = collect(100)                                                   # warm-up; also decides the shape
+    if t > 60.0 and (E, S) != (1024, 32):
+        E, S, fell_back = 1024, 32, True
+        collect(100)
+    for i in range(1, args.warmup):
+        collect(100 + i)
+    runs = [collect(1000 + i) for i in range(args.reps)]
+    k = int(np.argsort([r[0] for r in runs])[len(runs) // 2])
+    t, n, stats = runs[k]
+    on_device = _lib.debug_last_launch()["family"] == _lib.TW_KERNEL_MCTS_BIG
+    evals = int(stats.get("forward_evals", 0)) if on_device else None
+    row = {"bench": "az", "env": "GridWorld5x5", "policy": "625-512-128+heads (generic)", "path": "device" if on_device else "host_stepped",
+           "episodes": E, "num_mcts_searches": S, "max_expand_depth": 1, "shape_fell_back": fell_back, "records": n,
+           "wall_ms": round(t * 1e3, 3), "records_per_s": round(n / t, 1),
+           "ms_rollout": round(float(stats.get("ms_rollout", 0.0)), 3) if on_device else None,
+           "evaluations": evals, "evaluations_per_s": round(evals / t, 1) if evals else None,
+           "reps": args.reps, "device": twisterl_amd.device_info()["name"]}
+    print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(json.dumps(row) + "\n")
 
 
 def main():
@@ -27,7 +85,12 @@ def main():
     ap.add_argument("--episodes", default="1024,65536")
     ap.add_argument("--out", default=None)
     ap.add_argument("--env", default="gridworld", choices=["gridworld", "lamps40"])
+    ap.add_argument("--az", action="store_true", help="self-play (AZCollector.collect) instead of the PPO collect; appends one row to --out")
+    ap.add_argument("--az-shape", default="4096x100", help="episodes x num_mcts_searches of --az")
+    ap.add_argument("--tree", default=None, help="the checkout to measure (default: this one)")
     args = ap.parse_args()
+    if args.az:
+        return az(args)
     import numpy as np
     import twisterl_amd
     from twisterl_amd import _lib, twisterl

@@ -164,6 +164,7 @@ SYMBOLS = {
                                  C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
     "tw_device_env_host_vtable": (C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(EnvVTable)]),
     "tw_ppo_collect_device_env": (C.c_int, [_VP, _VP, C.c_size_t, _VP, C.POINTER(PPOParams), C.c_uint32, C.POINTER(_VP)]),
+    "tw_az_collect_device_env": (C.c_int, [_VP, _VP, C.c_size_t, _VP, C.POINTER(AZParams), C.c_uint32, C.POINTER(_VP)]),
     "tw_evaluate_device_env": (C.c_int, [_VP, _VP, C.c_size_t, _VP, C.POINTER(SolveParams), C.c_uint64, C.c_uint64, C.c_uint32,
                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tw_evaluate": (C.c_int, [C.POINTER(PuzzleDesc), _VP, C.POINTER(SolveParams), C.c_uint64, C.c_uint64,

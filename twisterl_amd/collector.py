@@ -516,8 +516,8 @@ PPOCollector._collect_foreign = _collect_foreign
 
 def _collect_device_env(self, env: DeviceEnv, policy: Policy, seed) -> CollectedData:
     """PPOCollector.collect of a device environment: the whole loop on the device (tw_ppo_collect_device_env; the library hands what
-    its kernel does not take to the host-stepped path over the same struct).  AZCollector.collect: self-play steps the struct's host
-    code (tw_az_collect_env over the module's vtable)."""
+    its kernel does not take to the host-stepped path over the same struct).  AZCollector.collect: tw_az_collect_device_env -- self-play
+    inside one kernel for a module built with search=True, else the struct's host code (tw_az_collect_env over the module's vtable)."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
     h = policy._handle()
@@ -530,11 +530,9 @@ def _collect_device_env(self, env: DeviceEnv, policy: Policy, seed) -> Collected
                              int(self.merge_order), 0)
         _lib.check(L.tw_ppo_collect_device_env(desc, proto, nbytes, h, C.byref(prm), env.max_records, C.byref(out)))
     else:
-        vt = _lib.EnvVTable()
-        _lib.check(L.tw_device_env_host_vtable(desc, proto, nbytes, C.byref(vt)))
         prm = _lib.AZParams(self.num_episodes, self.episode_offset, self.num_mcts_searches, self.C, self.max_expand_depth, sd,
                             _lib.PRECISIONS[self.precision], int(self.merge_order), 0)
-        _lib.check(L.tw_az_collect_env(C.byref(vt), h, C.byref(prm), env.max_records, C.byref(out)))
+        _lib.check(L.tw_az_collect_device_env(desc, proto, nbytes, h, C.byref(prm), env.max_records, C.byref(out)))
     return CollectedData._from_device(_DeviceResult(out.value))
 
 
@@ -637,7 +635,7 @@ def evaluate(py_env, policy: Policy, num_episodes, deterministic, num_searches, 
         br.finish(_lib.lib().tw_evaluate_env(_c.byref(br.vt), policy._handle(), _c.byref(prm), _u("num_episodes", num_episodes), 0, br.max_records,
                                              _c.byref(s), _c.byref(r)))
         return float(s.value), float(r.value)
-    if isinstance(py_env, DeviceEnv):                                           # one kernel (tw_evaluate_device_env)
+    if isinstance(py_env, DeviceEnv):                                           # one kernel (tw_evaluate_device_env; MCTS: a search=True module)
         _lib.check(_lib.lib().tw_evaluate_device_env(*py_env._args(), policy._handle(), _c.byref(prm), _u("num_episodes", num_episodes), 0,
                                                      py_env.max_records, _c.byref(s), _c.byref(r)))
         return float(s.value), float(r.value)

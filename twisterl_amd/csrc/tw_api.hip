@@ -1107,6 +1107,11 @@ const void *collected_field(const tw_collected *c, int field) { return c->field_
 // the trajectory workspace and the result-arena pool for the device-environment collectors (tw_device_env.hip)
 std::mutex &workspace_mutex() { return g_ws_mutex; }
 int workspace_reserve(size_t bytes, void **out) { return ws_reserve(bytes, out); }
+size_t workspace_capacity()
+{
+    int dev = 0;
+    return g_ws.ptr && hipGetDevice(&dev) == hipSuccess && g_ws.device == dev ? g_ws.cap : 0;
+}
 int result_arena_acquire(size_t bytes, void **out, size_t *cap) { return arena_acquire(bytes, out, cap); }
 void collected_adopt_stats(tw_collected *c, const tw_collect_stats &st) { c->stats = st; }
 int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uint32_t n_cells, uint32_t n_actions, uint64_t n_records,

@@ -697,6 +697,7 @@ int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uin
 // the cached trajectory workspace (held under workspace_mutex() while in use) and the pooled result arenas (tw_api.hip)
 std::mutex &workspace_mutex();
 int workspace_reserve(size_t bytes, void **out);
+size_t workspace_capacity();      // bytes of the cached workspace on the current device (under workspace_mutex()): what a larger request would replace
 int result_arena_acquire(size_t bytes, void **out, size_t *cap);
 void collected_adopt_stats(tw_collected *c, const tw_collect_stats &st);
 int launch_policy_eval(const PolicyDev &pol, int mode, const int32_t *obs_d, uint32_t n, uint32_t n_obs,

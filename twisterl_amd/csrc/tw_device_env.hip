@@ -4,9 +4,11 @@
 // solve_env_kernel of tw_rollout_env.hpp instantiated over the user's struct -- their launchers and a host adapter.  Everything
 // else is here: the checks, the workspace, the scan / GAE / compaction of the Puzzle path (tw_finalize.hip), the error messages.
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
-// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error),
-// evaluate with MCTS, self-play and solve (the Python layer routes those).  The result is an ordinary tw_collected, byte-equal to
-// tw_ppo_collect_env over the same vtable.
+// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error), solve
+// (the Python layer routes it), and -- for a module built without TW_DEVICE_ENV_SEARCH, whose descriptor has no search launcher --
+// self-play and evaluate with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), which lives in the module
+// alone: tw_az_collect_device_env, and tw_evaluate_device_env with num_mcts_searches > 0.  The result is an ordinary tw_collected,
+// byte-equal to tw_ppo_collect_env / tw_az_collect_env over the same vtable.
 #include "tw_rollout_env.hpp"
 
 #include <cstring>
@@ -101,6 +103,49 @@ int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
     if ((int)vt.num_actions != pd->n_actions) { set_error("environment has %u actions, policy has %d (at most 31)", vt.num_actions, pd->n_actions); return TW_ERR_INVALID; }
     if ((int)vt.obs_size != pd->obs_size) { set_error("index out of bounds: policy obs_size %d != environment obs ids %u", pd->obs_size, vt.obs_size); return TW_ERR_INVALID; }
     return TW_OK;
+}
+
+// launch_finalize_az keeps two floats per record of an episode for each of its four waves in 64 KiB of LDS
+constexpr uint32_t FINALIZE_AZ_MAX_T_PAD = 64 * 1024 / (4 * 2 * sizeof(float));
+
+// what mcts_env_kernel takes of a search: the tree fits 31-bit node indices and a column's evaluation ordinal 32 bits
+bool search_fits(uint32_t A, uint32_t S, uint32_t MED, uint64_t moves, uint64_t *node_cap)
+{
+    const uint64_t per_move = (uint64_t)S * (MED ? MED : 1u);
+    *node_cap = env_mcts_node_cap(A, S, MED);
+    return per_move <= 0x0fffffffull && *node_cap <= 0x7fffffffull && (per_move + 1) * moves <= 0xffffffffull;
+}
+
+// free memory plus the cached workspace this call would replace (az_collect_once's test)
+int check_memory_fit(size_t need, const char *who)
+{
+    size_t free_b = 0, total_b = 0;
+    TW_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t have = workspace_capacity(), avail = free_b + have;
+    if (need > have && need > (size_t)(0.95 * (double)avail)) {
+        set_error("%s: %zu bytes of tree arenas + trajectories exceed the free device memory (%zu free of %zu)", who, need, avail, total_b);
+        return TW_ERR_UNSUPPORTED;
+    }
+    return TW_OK;
+}
+
+// The error the host-stepped path reports for the columns mcts_env_kernel ended (EnvMctsArgs::col_err).  That path evaluates one
+// state per live episode per round and checks the ids as it stages them, episode by episode: the first bad id (count) is the one
+// with the smallest evaluation ordinal, then the smallest column.  It notices an overlong episode only before the NEXT round, so a
+// bad id wins exactly when its ordinal is below the evaluations every overlong column had consumed.  Returns true for a bad id.
+bool first_search_error(const std::vector<uint32_t> &ce, uint64_t n, uint32_t NO, int obs_size)
+{
+    uint64_t bad = n;
+    uint32_t over = 0xffffffffu;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t kind = ce[4 * i], ord = ce[4 * i + 1];
+        if ((kind == 1u || kind == 2u) && (bad == n || ord < ce[4 * bad + 1])) bad = i;
+        else if (kind == 3u && ord < over) over = ord;
+    }
+    if (bad == n || ce[4 * bad + 1] >= over) return false;
+    if (ce[4 * bad] == 2u) set_error("observation of %u ids, at most %u", ce[4 * bad + 2], NO);
+    else set_error("index out of bounds: obs id %d, obs_size %d", (int)ce[4 * bad + 2], obs_size);
+    return true;
 }
 
 }  // namespace
@@ -254,6 +299,142 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     return TW_OK;
 }
 
+// AZCollector::collect (az.rs:51-109) of a device environment whose module holds the search kernel: self-play in mcts_env_kernel, then
+// the tail of az_collect_once -- scan, launch_finalize_az (0 cells: the ids have their own array), the obs compaction of the PPO path
+// above, narrow_logits_kernel for A < 4.  Byte-equal to tw_az_collect_env over the module's vtable, which is also where everything
+// the kernel or the finalize step does not take goes.
+extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                                        const tw_az_params *prm, uint32_t max_records_per_episode, tw_collected **out)
+{
+    if (!policy || !prm || !out) { set_error("tw_az_collect_device_env: null argument"); return TW_ERR_INVALID; }
+    *out = nullptr;
+    int rc = check_descriptor(env, proto, proto_bytes, "tw_az_collect_device_env"); if (rc) return rc;
+    note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);      // (the host-stepped path reports nothing)
+    const tw_env_vtable vt = host_table(env, proto);
+    const PolicyDev *pd = policy_dev(policy);
+    uint64_t node_cap = 0;
+    if (!env->launch_search || !pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > FINALIZE_AZ_MAX_T_PAD ||
+        !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_records_per_episode, &node_cap))
+        return tw_az_collect_env(&vt, policy, prm, max_records_per_episode, out);
+    if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
+    rc = check_env_policy(vt, pd); if (rc) return rc;
+    if (max_records_per_episode == 0) { set_error("tw_az_collect_env: max_records_per_episode must be positive"); return TW_ERR_INVALID; }
+    if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_az_collect_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }
+    rc = require_device(); if (rc) return rc;
+
+    const uint64_t E = prm->num_episodes;
+    const bool ragged = vt.observe_n != nullptr;
+    const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
+    const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
+    const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;
+    if (blocks > 0x7fffffffull) { set_error("tw_az_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
+    const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
+    if (lds_bytes + env_mcts_pending_bytes(env->n_obs) > 159 * 1024) {
+        set_error("mcts: %zu bytes of LDS needed, 159 KiB available", lds_bytes + env_mcts_pending_bytes(env->n_obs)); return TW_ERR_UNSUPPORTED;
+    }
+
+    std::lock_guard<std::mutex> lock(workspace_mutex());
+    hipStream_t s = current_stream();
+    size_t cur = 0;
+    auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
+    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(32), o_scan = seg(scan_scratch_bytes(E)),
+                 o_obs16 = seg(R * NO * 2), o_ce = seg(E * 16), o_arena = seg((size_t)E * node_cap * ENV_MCTS_NODE_BYTES);
+    rc = check_memory_fit(cur, "tw_az_collect_device_env"); if (rc) return rc;
+    void *wsp = nullptr;
+    rc = workspace_reserve(cur, &wsp); if (rc) return rc;
+    uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
+    EnvMctsArgs ma{};
+    ma.struct_bytes = (uint32_t)sizeof(EnvMctsArgs);
+    ma.pol = *pd;
+    ma.out.rec = reinterpret_cast<PaddedRec *>(ws + o_rec); ma.out.ep_len = reinterpret_cast<uint32_t *>(ws + o_len); ma.out.t_pad = (int32_t)t_pad;
+    ma.obs16 = reinterpret_cast<uint16_t *>(ws + o_obs16);
+    ma.err = reinterpret_cast<uint32_t *>(ws + o_total + 8); ma.eval_count = reinterpret_cast<unsigned long long *>(ws + o_total + 16);
+    ma.col_err = reinterpret_cast<uint32_t *>(ws + o_ce);
+    ma.num_columns = E; ma.episode_offset = prm->episode_offset; ma.seed = prm->seed;
+    ma.num_searches = prm->num_mcts_searches; ma.max_expand_depth = prm->max_expand_depth; ma.C = prm->C; ma.node_cap = (uint32_t)node_cap;
+    ma.arena = ws + o_arena;
+    uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
+
+    struct Events { hipEvent_t ev[5] = {}; ~Events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); } } ev;
+    for (auto &e : ev.ev) TW_HIP(hipEventCreate(&e));
+    TW_HIP(hipMemsetAsync(ws + o_total, 0, 32, s));
+    TW_HIP(hipMemsetAsync(ws + o_ce, 0, E * 16, s));
+    TW_HIP(hipEventRecord(ev.ev[0], s));
+    const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
+    if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
+    note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
+    TW_HIP(hipEventRecord(ev.ev[1], s));
+    rc = launch_scan(ma.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
+    if (rc) return rc;
+    TW_HIP(hipEventRecord(ev.ev[2], s));
+    uint64_t hv[3] = {0, 0, 0};
+    TW_HIP(hipMemcpyAsync(hv, ws + o_total, 24, hipMemcpyDeviceToHost, s));
+    TW_HIP(hipStreamSynchronize(s));
+    const uint64_t total = hv[0];
+    const uint32_t err = (uint32_t)hv[1];
+    if (err & 11u) {
+        std::vector<uint32_t> ce(E * 4);
+        TW_HIP(hipMemcpy(ce.data(), ma.col_err, E * 16, hipMemcpyDeviceToHost));
+        if (!first_search_error(ce, E, NO, pd->obs_size)) set_error("tw_az_collect_env: an episode did not end within %u records", max_records_per_episode);
+        return TW_ERR_INVALID;
+    }
+    if (total == 0 || total > R) { set_error("az collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
+
+    // ---- compact result: the fields of tw_az_collect_env, then (A < 4) the four-column probabilities the finalize kernel writes ----------
+    size_t ccur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
+    auto put = [&](int f, size_t b) { bytes[f] = b; off[f] = ccur; ccur = (ccur + b + 255) / 256 * 256; };
+    put(TW_F_OBS, total * NO * OW); put(TW_F_LOGITS, total * A * 4); put(TW_F_PERMS, total); put(TW_F_REMAINING, total * 4);
+    put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
+    const size_t o_lg4 = ccur;
+    if (A < 4) ccur += total * 16;
+    void *arena = nullptr; size_t cap = 0;
+    rc = result_arena_acquire(ccur, &arena, &cap); if (rc) return rc;
+    uint8_t *ca = reinterpret_cast<uint8_t *>(arena);
+    void *fp[TW_F_COUNT] = {};
+    for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) fp[f] = ca + off[f];
+    int dev_id = 0; (void)hipGetDevice(&dev_id);
+    tw_collected *c = nullptr;
+    rc = collected_adopt(arena, cap, dev_id, 0, NO, A, total, E, fp, bytes, &c);
+    if (rc) { (void)hipFree(arena); return rc; }
+    collected_adopt_obs_width(c, OW);
+    collected_adopt_obs_layout(c, (uint32_t)pd->obs_size, false);         // an environment's ids: any of [0, obs_size), in any order
+    if (ragged) collected_adopt_obs_ragged(c);
+#define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
+    TW_HIP_C(hipEventRecord(ev.ev[3], s));
+    rc = launch_finalize_az(ma.out, ep_start_ws, E, 0, ca + off[TW_F_OBS], reinterpret_cast<float *>(A < 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]),
+                            reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]), reinterpret_cast<float *>(ca + off[TW_F_REMAINING]), s);
+    if (rc == TW_OK && OW == 2)
+        rc = launch_compact_obs16(ma.obs16, ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s);
+    if (rc) { tw_collected_free(c); return rc; }
+    if (OW == 1) {
+        hipLaunchKernelGGL(compact_env_obs8_kernel, dim3(grid_for(E, 4)), dim3(256), 0, s, ma.obs16, ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO,
+                           ca + off[TW_F_OBS]);
+        TW_HIP_C(hipGetLastError());
+    }
+    if (A < 4) {
+        hipLaunchKernelGGL(narrow_logits_kernel, dim3(grid_for(total * A, 256)), dim3(256), 0, s, reinterpret_cast<const float *>(ca + o_lg4), total,
+                           (int)A, reinterpret_cast<float *>(ca + off[TW_F_LOGITS]));
+        TW_HIP_C(hipGetLastError());
+    }
+    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_LEN], ma.out.ep_len, E * 4, hipMemcpyDeviceToDevice, s));
+    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_START], ep_start_ws, E * 8, hipMemcpyDeviceToDevice, s));
+    TW_HIP_C(hipEventRecord(ev.ev[4], s));
+    TW_HIP_C(hipStreamSynchronize(s));
+    tw_collect_stats st{};
+    float ms = 0;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1])); st.ms_rollout = ms;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[1], ev.ev[2])); st.ms_scan = ms;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[3], ev.ev[4])); st.ms_finalize = ms;
+    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[4])); st.ms_total = ms;
+#undef TW_HIP_C
+    st.records = total; st.episodes = E; st.padded_bytes = cur;
+    st.forward_evals = hv[2] * (uint64_t)(pd->n_perms > 0 ? pd->n_perms : 1);
+    st.rollout_blocks = (uint32_t)blocks; st.rollout_threads = 256;
+    collected_adopt_stats(c, st);
+    *out = c;
+    return TW_OK;
+}
+
 extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
                                       const tw_solve_params *prm, uint64_t num_episodes, uint64_t episode_offset, uint32_t max_steps,
                                       float *success_rate, float *mean_reward)
@@ -263,8 +444,10 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);
     const tw_env_vtable vt = host_table(env, proto);
     const PolicyDev *pd = policy_dev(policy);
-    if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_mcts_searches != 0 || prm->num_searches == 0 || num_episodes == 0 ||
-        max_steps > 0x7fffffffu)
+    const bool mcts = prm->num_mcts_searches != 0;
+    uint64_t node_cap = 0;
+    if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_searches == 0 || num_episodes == 0 || max_steps > 0x7fffffffu ||
+        (mcts && (!env->launch_search || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, &node_cap))))
         return tw_evaluate_env(&vt, policy, prm, num_episodes, episode_offset, max_steps, success_rate, mean_reward);
     rc = check_env_policy(vt, pd); if (rc) return rc;
     if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_evaluate_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }
@@ -273,12 +456,54 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     const uint64_t blocks = (NA + GEN_COLS - 1) / GEN_COLS;
     if (NA / N != num_episodes || blocks > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
     const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
-    if (lds_bytes > 159 * 1024) { set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
+    if (lds_bytes + (mcts ? env_mcts_pending_bytes(env->n_obs) : 0) > 159 * 1024) {
+        set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes + (mcts ? env_mcts_pending_bytes(env->n_obs) : 0)); return TW_ERR_UNSUPPORTED;
+    }
 
     std::vector<float> succ(NA), tot(NA);
     std::vector<uint32_t> steps(NA);
     uint64_t hv[2] = {0, 0};
-    {
+    if (mcts) {
+        // MCTS-guided attempts (solve.rs:41-47): mcts_env_kernel in solve mode, one column = one attempt; the reduction below is shared
+        std::vector<uint32_t> ce;
+        {
+            std::lock_guard<std::mutex> lock(workspace_mutex());
+            hipStream_t s = current_stream();
+            size_t cur = 0;
+            auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
+            const size_t o_s = seg(NA * 4), o_t = seg(NA * 4), o_n = seg(NA * 4), o_err = seg(32), o_ce = seg(NA * 16),
+                         o_arena = seg((size_t)NA * node_cap * ENV_MCTS_NODE_BYTES);
+            rc = check_memory_fit(cur, "tw_evaluate_device_env"); if (rc) return rc;
+            void *wsp = nullptr;
+            rc = workspace_reserve(cur, &wsp); if (rc) return rc;
+            uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
+            EnvMctsArgs ma{};
+            ma.struct_bytes = (uint32_t)sizeof(EnvMctsArgs);
+            ma.pol = *pd; ma.num_columns = NA; ma.episode_offset = episode_offset; ma.seed = prm->seed;
+            ma.num_searches = prm->num_mcts_searches; ma.max_expand_depth = prm->max_expand_depth; ma.C = prm->C; ma.node_cap = (uint32_t)node_cap;
+            ma.arena = ws + o_arena; ma.err = reinterpret_cast<uint32_t *>(ws + o_err); ma.eval_count = reinterpret_cast<unsigned long long *>(ws + o_err + 8);
+            ma.col_err = reinterpret_cast<uint32_t *>(ws + o_ce);
+            ma.solve_on = 1u; ma.deterministic = prm->deterministic ? 1u : 0u; ma.attempts = (uint32_t)N; ma.max_steps = max_steps ? max_steps : 1u;
+            ma.success = reinterpret_cast<float *>(ws + o_s); ma.total = reinterpret_cast<float *>(ws + o_t); ma.n_steps = reinterpret_cast<uint32_t *>(ws + o_n);
+            TW_HIP(hipMemsetAsync(ws + o_err, 0, 32, s));
+            TW_HIP(hipMemsetAsync(ws + o_ce, 0, NA * 16, s));
+            const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
+            if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
+            note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, true, false, false, (uint32_t)blocks, 256);
+            TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
+            TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
+            TW_HIP(hipMemcpyAsync(hv, ws + o_err, 8, hipMemcpyDeviceToHost, s));
+            TW_HIP(hipStreamSynchronize(s));
+            if ((uint32_t)hv[0] & 13u) {
+                ce.resize(NA * 4);
+                TW_HIP(hipMemcpy(ce.data(), ws + o_ce, NA * 16, hipMemcpyDeviceToHost));
+            }
+        }
+        if ((uint32_t)hv[0] & 13u) {
+            if (!first_search_error(ce, NA, vt.n_obs, pd->obs_size)) set_error("solve: an attempt did not end within %u steps", max_steps ? max_steps : 1u);
+            return TW_ERR_INVALID;
+        }
+    } else {
         std::lock_guard<std::mutex> lock(workspace_mutex());
         hipStream_t s = current_stream();
         size_t cur = 0;

@@ -1,0 +1,354 @@
+// tw_mcts_env.hpp -- AlphaZero self-play and MCTS-guided evaluate of a user-written device environment ON THE DEVICE: the search
+// of tw_mcts_big.hip as a template over the environment struct (include/twisterl_device_env.hpp).
+//
+// The same algorithm, RNG keys and arithmetic as mcts_big_kernel and as HostMcts (tw_env_generic.hip: AZCollector::single_collect,
+// rust/src/collector/az.rs:51-109, over predict_probs_mcts, rust/src/rl/search.rs:104-189; solve mode: single_solve,
+// rust/src/rl/solve.rs:17-71): one column of EngineV = one episode (one attempt), one batched Policy::full_predict per search step
+// across the 16 columns of a workgroup, the per-episode tree in an HBM arena of 32-byte nodes WITHOUT a state, children contiguous.
+// What the Puzzle lines of that kernel were is the struct here:
+//   * reset / step / masks / reward / is_final / success are the struct's; only actions < Env::NUM_ACTIONS are expanded, sampled and
+//     counted, the uniform fallback of the visit counts is 1 / NUM_ACTIONS;
+//   * a node's state is re-derived by replaying the actions from the move's root.  The host path clones the environment per node;
+//     the two agree because a device environment's step() depends on the struct and the action alone (the contract);
+//   * two states per lane: the episode's and the walking one.  The state whose evaluation is pending is always the walking one
+//     (it is set to the episode's wherever a move begins), so no third copy and no choice between two register structs;
+//   * only the owner lane of a column holds its tree and states.  It observes the pending state, guards the ids (env_rows /
+//     env_rows_n: the id guard, the count guard) and hands the ids -- -1 where the observation has none -- to the forward through
+//     LDS; every lane derives its rows per twist pass from them (env_twist_row: both table widths);
+//   * a bad id or a bad observe_n count at ANY evaluated state never indexes anything: the column ends, err gets bit 0 or 3, and
+//     col_err[column] = {1 + kind, the column's evaluation ordinal, the id or the count, 0}.  An episode that has not ended after
+//     t_pad records (solve mode: max_steps steps) sets bit 1 (bit 2) and leaves kind 2 with the evaluations it had consumed.
+// The library (tw_device_env.hip) owns the checks, the workspace, the scan / finalize / compaction and the messages.  A module gets
+// this kernel with TW_DEVICE_ENV_SEARCH; the MFMAs are EngineV's, the intrinsic form only (tw_engine_generic.hpp).
+#pragma once
+#include "tw_rollout_env.hpp"
+
+namespace tw {
+
+struct __attribute__((aligned(16))) EnvNode {     // MCTSNode + Node<T> (search.rs:20-26, tree.rs:18-23) without the state
+    float    value_sum;
+    uint32_t visit;
+    float    prior;
+    uint32_t parent;       // 0xffffffff = None
+    uint32_t child_base;   // children are contiguous in the arena (expand adds them together)
+    uint32_t meta;         // n_children | action_taken << 8 (0xff = None)
+    uint32_t pad[2];
+};
+static_assert(sizeof(EnvNode) == ENV_MCTS_NODE_BYTES, "EnvNode must be 32 bytes");
+
+constexpr uint32_t EN_NONE = 0xffffffffu;
+enum { EP_ROOT = 0, EP_LEAF = 1, EP_DONE = 2 };
+
+// the row of the embedding table an id selects under twist `perm` (-1: none); id < 0: no row
+__device__ __forceinline__ int env_twist_row(const PolicyDev &pol, int perm, int id)
+{
+    if (id < 0) return -1;
+    return perm < 0 ? id : (pol.obs_size > 256 ? (int)pol.obs_perms16[(size_t)perm * pol.obs_size + id]
+                                                 : (int)pol.obs_perms[(size_t)perm * pol.obs_size + id]);
+}
+
+template <class Env, int NC>
+__global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, const Env proto)
+{
+    using Eng = EngineV<NC>;
+    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
+    constexpr uint32_t AMASK = (1u << A) - 1u;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    Eng eng;
+    eng.begin1(a.pol, lds);
+    const int j = eng.j;
+    const uint64_t e_local = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+    const bool valid = e_local < a.num_columns;
+    const bool pub   = eng.h == 0 && eng.owns_lane();                // the lane that publishes column j's ids
+    const bool owner = valid && pub;                                  // ... and walks / mutates its tree
+    const bool solve = a.solve_on != 0;
+    // solve mode: column = ATTEMPT (episode, search); its draws are keyed like single_solve's (solve_env_kernel)
+    const uint64_t sv_ep = solve ? a.episode_offset + e_local / a.attempts : 0;
+    const uint64_t e_global = solve ? sv_ep * (uint64_t)a.attempts + e_local % a.attempts : a.episode_offset + e_local;
+    EnvNode *nodes = reinterpret_cast<EnvNode *>(a.arena) + (valid ? e_local : 0) * (uint64_t)a.node_cap;
+    const uint32_t S = a.num_searches, MED = a.max_expand_depth;
+    const uint64_t rec_base = e_local * (uint64_t)a.out.t_pad;
+    int *pend = reinterpret_cast<int *>(lds + Eng::lds_floats(a.pol)) + j * NO;     // the ids of column j's pending state
+
+    Env st = proto;                                                   // the episode's env (az.rs:56-57 / evaluate.rs:39)
+    if (owner) st.reset(a.seed, solve ? sv_ep : e_global);
+    Env cur = st;                                                     // the state of `node`: the one whose evaluation is pending
+    int      phase = owner ? EP_ROOT : EP_DONE;
+    if (solve && owner && st.is_final()) phase = EP_DONE;             // `while !env.is_final()` (solve.rs:30)
+    float    total = 0.0f;                                            // solve mode: summed rewards (solve.rs:25-34)
+    uint32_t it = 0, expanded = 0, node = 0, n_nodes = 0, evals = 0;
+    int      t = 0;
+    float    value = 0.0f;
+    uint32_t fail_kind = 0;                                           // 1 + (0: a bad id, 1: a bad count, 2: too long)
+
+    auto end_column = [&](uint32_t kind, uint32_t what, uint32_t bit) {   // (owner) the column stops; the library names the first
+        uint32_t *ce = a.col_err + 4 * e_local;
+        ce[0] = kind + 1u; ce[1] = evals; ce[2] = what; ce[3] = 0u;
+        atomicOr(a.err, bit);
+        fail_kind = kind + 1u;
+        phase = EP_DONE;
+    };
+    // the pending state's ids -> the lanes that feed the forward; guarded here: what leaves the owner is an id < obs_size or -1
+    auto publish = [&]() {
+        if (!pub) return;
+        int ids[NO], rows[NC];
+        bool bad = false; int bad_id = 0;
+        [[maybe_unused]] bool bad_count = false;
+        if (phase != EP_DONE) {
+            if constexpr (EnvHasObserveN<Env>::value) (void)env_rows_n<Env, NC>(cur, eng.pol, -1, ids, rows, bad, bad_id, bad_count, nullptr);
+            else env_rows<Env, NC>(cur, eng.pol, -1, ids, rows, bad, bad_id);
+            if (bad) end_column(bad_count ? 1u : 0u, (uint32_t)bad_id, bad_count ? 8u : 1u);
+        }
+        const bool live = phase != EP_DONE;
+#pragma unroll
+        for (int i = 0; i < NO; ++i) pend[i] = (live && i < NC) ? rows[i] : -1;
+    };
+    publish();
+    eng.begin2();
+
+    for (;;) {
+        if (!__syncthreads_or(phase != EP_DONE ? 1 : 0)) break;       // (the barrier publishes the ids)
+        // ---- Policy::full_predict of the pending states (policy.rs:102-126); the engine takes a column's rows from wave 0 ----
+        int pid[NC];
+#pragma unroll
+        for (int i = 0; i < NC; ++i) pid[i] = i < NO ? pend[i] : -1;
+        float lsum[4] = {0.0f, 0.0f, 0.0f, 0.0f}, vsum = 0.0f;
+        const int n_pass = eng.pol.n_perms > 0 ? eng.pol.n_perms : 1;
+        const float np = (float)eng.pol.n_perms;
+        for (int pass = 0; pass < n_pass; ++pass) {
+            const int perm = eng.pol.n_perms > 0 ? pass : -1;
+            int rowoff[NC];
+#pragma unroll
+            for (int i = 0; i < NC; ++i) rowoff[i] = env_twist_row(eng.pol, perm, pid[i]);
+            float lg[4], v;
+            eng.forward(rowoff, lg, v);
+            env_act_perm<A>(eng.pol, perm, lg);
+            if (eng.pol.n_perms > 0) {
+                vsum = vsum + v / np;                                            // policy.rs:111
+#pragma unroll
+                for (int i = 0; i < 4; ++i) lsum[i] = lsum[i] + lg[i] / np;      // policy.rs:112-114
+            } else {
+                vsum = v;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) lsum[i] = lg[i];
+            }
+        }
+
+        // ---- per-episode tree work on the owner lane -------------------------------------------------------------------------
+        if (owner && phase != EP_DONE) {
+            float probs[4];
+            masked_softmax4(lsum, cur.masks() & AMASK, probs);
+            const float nn_value = vsum;
+            ++evals;
+            float pri[4] = {0.0f, 0.0f, 0.0f, 0.0f};                  // priors of the children just created, in child order
+            uint32_t acts = 0;                                        // ... and their actions, 2 bits each
+            // expand (search.rs:56-75): one child per action with prior > 0
+            auto expand = [&](uint32_t idx) -> uint32_t {
+                uint32_t cnt = 0;
+                acts = 0;
+#pragma unroll
+                for (int act = 0; act < A; ++act) {
+                    if (!(probs[act] > 0.0f)) continue;
+                    if (cnt == 0) pri[0] = probs[act]; else if (cnt == 1) pri[1] = probs[act];
+                    else if (cnt == 2) pri[2] = probs[act]; else pri[3] = probs[act];
+                    acts |= (uint32_t)act << (2 * cnt);
+                    EnvNode nn;
+                    nn.value_sum = 0.0f; nn.visit = 0; nn.prior = probs[act]; nn.parent = idx; nn.child_base = 0;
+                    nn.meta = 0u | ((uint32_t)act << 8);
+                    nn.pad[0] = 0; nn.pad[1] = 0;
+                    nodes[n_nodes + cnt] = nn;
+                    ++cnt;
+                }
+                nodes[idx].child_base = n_nodes;
+                nodes[idx].meta = (nodes[idx].meta & ~0xffu) | cnt;
+                n_nodes += cnt;
+                return cnt;
+            };
+            // backpropagate (search.rs:45-53): value_sum += v, visit_count += 1 from the node up to the root
+            auto backprop = [&](uint32_t idx, float val) {
+                while (idx != EN_NONE) {
+                    const EnvNode n = nodes[idx];
+                    uint2 w; w.x = __float_as_uint(n.value_sum + val); w.y = n.visit + 1u;
+                    *reinterpret_cast<uint2 *>(&nodes[idx].value_sum) = w;
+                    idx = n.parent;
+                }
+            };
+
+            if (phase == EP_ROOT) {
+                // root node (search.rs:120-129): visit_count 1, expanded with the root priors
+                EnvNode r;
+                r.value_sum = 0.0f; r.visit = 1; r.prior = 0.0f; r.parent = EN_NONE; r.child_base = 0;
+                r.meta = 0u | (0xffu << 8); r.pad[0] = 0; r.pad[1] = 0;
+                nodes[0] = r; n_nodes = 1;
+                expand(0u);
+                it = 0;
+            } else {
+                // the leaf just evaluated (search.rs:154-159): expand, sample a child by the priors (next_sample, :94-100); the state follows
+                const uint32_t cb = n_nodes;
+                const uint32_t nch = expand(node);
+                if (nch > 0) {
+                    const u32x4 w = rng_draw(a.seed, e_global, it * MED + expanded, STREAM_MCTS | ((uint32_t)t << 8));
+                    const int k = sample_weighted4(pri, (int)nch, u32_to_unit(w.x));
+                    node = cb + (uint32_t)k;
+                    cur.step((int)((acts >> (2 * k)) & 3u));
+                }
+                value = nn_value;
+                ++expanded;
+            }
+            bool resume = (phase == EP_LEAF);
+            for (;;) {
+                if (!resume) {
+                    if (it == S) {
+                        // ---- move finished: visit counts -> probs (search.rs:166-188) -----------------------------------------
+                        float mp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                        const EnvNode root = nodes[0];
+                        const uint32_t rnc = root.meta & 0xffu;
+                        for (uint32_t c = 0; c < rnc; ++c) {
+                            const EnvNode ch = nodes[root.child_base + c];
+                            const int act = (int)((ch.meta >> 8) & 3u);
+                            const float vis = (float)ch.visit;
+                            mp[0] = act == 0 ? vis : mp[0]; mp[1] = act == 1 ? vis : mp[1];
+                            mp[2] = act == 2 ? vis : mp[2]; mp[3] = act == 3 ? vis : mp[3];
+                        }
+                        float sum = 0.0f;
+#pragma unroll
+                        for (int i = 0; i < A; ++i) sum = sum + mp[i];
+                        if (sum > 0.0f) {
+#pragma unroll
+                            for (int i = 0; i < A; ++i) mp[i] = mp[i] / sum;
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < A; ++i) mp[i] = 1.0f / (float)A;
+                        }
+                        if (solve) {
+                            // solve.rs:31-58: total += reward; action = argmax | sample of the MCTS probs; step
+                            total = total + st.reward();
+                            int action = 0;
+                            if (a.deterministic) {
+                                float bv = mp[0];
+#pragma unroll
+                                for (int i = 1; i < A; ++i) if (mp[i] > bv) { bv = mp[i]; action = i; }
+                            } else {
+                                const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_SOLVE);
+                                action = sample_weighted4(mp, A, u32_to_unit(w.x));
+                            }
+                            st.step(action);
+                            ++t;
+                            if (st.is_final()) { phase = EP_DONE; break; }
+                            if ((uint32_t)t >= a.max_steps) { end_column(2u, 0u, 4u); break; }     // the host path's max_steps
+                            phase = EP_ROOT; cur = st;
+                            break;
+                        }
+                        // az.rs:72-81: action = sample(mcts_probs); val = env.reward(); store the record
+                        const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_AZ_ACT);
+                        const int action = sample_weighted4(mp, A, u32_to_unit(w.x));
+                        const uint64_t rec = rec_base + (uint64_t)t;
+                        const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
+                        store_rec(a.out.rec + rec, zero4, mp, 0.0f, st.reward(), 0, -1);
+                        {
+                            // the ids of the state the move's search was rooted in (guarded when it was evaluated)
+                            const int stride = env_n_obs(st);
+                            uint16_t *o = a.obs16 + rec * (uint64_t)stride;
+                            int ids[NO];
+                            int n = stride;
+                            if constexpr (EnvHasObserveN<Env>::value) { n = st.observe_n(ids); if ((unsigned)n > (unsigned)stride) n = 0; }
+                            else st.observe(ids);
+#pragma unroll
+                            for (int i = 0; i < NO; ++i) if (i < stride) o[i] = i < n ? (uint16_t)ids[i] : (uint16_t)0xFFFFu;
+                        }
+                        if (st.is_final()) {                                                             // az.rs:84
+                            a.out.ep_len[e_local] = (uint32_t)t + 1u;
+                            phase = EP_DONE;
+                            break;
+                        }
+                        if (t + 1 >= a.out.t_pad) {                                                      // the host path's max_records_per_episode
+                            a.out.ep_len[e_local] = (uint32_t)t + 1u;
+                            end_column(2u, 0u, 2u);
+                            break;
+                        }
+                        st.step(action);                                                                 // az.rs:89
+                        ++t;
+                        phase = EP_ROOT; cur = st;
+                        break;
+                    }
+                    // ---- descend to a leaf by UCB (search.rs:133-138, next :77-91, ucb :29-39); the state follows the actions ----
+                    node = 0; cur = st;
+                    EnvNode cn = nodes[0];
+                    for (;;) {
+                        const uint32_t nch = cn.meta & 0xffu, cb = cn.child_base;
+                        if (nch == 0) break;
+                        uint32_t best = EN_NONE; float best_ucb = -__builtin_inff();
+                        EnvNode bestn = cn;
+                        const float sq = sqrtf((float)cn.visit);
+                        EnvNode chs[A];
+#pragma unroll
+                        for (int c = 0; c < A; ++c) chs[c] = nodes[cb + ((uint32_t)c < nch ? (uint32_t)c : nch - 1u)];
+#pragma unroll
+                        for (int c = 0; c < A; ++c) {
+                            const EnvNode &ch = chs[c];
+                            const float q = ch.visit == 0 ? 0.0f : ch.value_sum / (float)ch.visit;
+                            float d = sq / ((float)ch.visit + 1.0f);
+                            d = a.C * d;
+                            d = d * ch.prior;
+                            const float u = q + d;
+                            if ((uint32_t)c < nch && u > best_ucb) { best = cb + (uint32_t)c; best_ucb = u; bestn = ch; }
+                        }
+                        if (best == EN_NONE) break;                   // all-NaN UCB: the reference panics here
+                        node = best; cn = bestn;
+                        cur.step((int)((bestn.meta >> 8) & 3u));
+                    }
+                    value = 0.0f; expanded = 0;
+                }
+                resume = false;
+                // leaf phase (search.rs:143-160)
+                bool need_nn = false;
+                while (expanded < MED) {
+                    value = cur.reward();                                             // :146
+                    if (cur.is_final()) break;                                        // :149
+                    phase = EP_LEAF; need_nn = true;                                  // :154 needs the network
+                    break;
+                }
+                if (need_nn) break;
+                backprop(node, value);                                                // :163
+                ++it;
+            }
+        }
+        publish();                                                    // (the ids were read before the forward's first barrier)
+    }
+    if (owner) {
+        if (solve) {
+            total = total + st.reward();                                  // solve.rs:65-66
+            a.success[e_local] = st.success() ? 1.0f : 0.0f;              // solve.rs:68
+            a.total[e_local]   = total;
+            a.n_steps[e_local] = (uint32_t)t;
+        } else if (fail_kind == 1u || fail_kind == 2u) {
+            a.out.ep_len[e_local] = 1u;                                   // (a bad id: the collect fails; the scan still reads a length)
+        }
+        atomicAdd(a.eval_count, (unsigned long long)evals);
+    }
+    eng.end();
+}
+
+// hipFuncSetAttribute (dynamic LDS: the engine's share, which the library passes, plus the pending ids of the 16 columns) + the launch
+template <class Env>
+int launch_mcts_env(const EnvMctsArgs *a, const void *proto, unsigned blocks, size_t engine_lds_bytes, hipStream_t s)
+{
+    constexpr int NC = env_engine_nc(Env::N_OBS);
+    using Eng = EngineV<NC>;
+    const uint64_t need = env_mcts_node_cap(Env::NUM_ACTIONS, a->num_searches, a->max_expand_depth);
+    if (a->struct_bytes != sizeof(EnvMctsArgs) || a->node_cap < need || !a->arena || !a->eval_count || !a->err || !a->col_err ||
+        (a->solve_on ? (!a->success || !a->total || !a->n_steps || a->attempts == 0 || a->max_steps == 0)
+                     : (!a->out.rec || !a->out.ep_len || !a->obs16 || a->out.t_pad < 1)) ||
+        blocks == 0 || (uint64_t)blocks * Eng::EPB < a->num_columns)
+        return (int)hipErrorInvalidValue;
+    const size_t lds_bytes = engine_lds_bytes + env_mcts_pending_bytes(Env::N_OBS);
+    Env p;
+    __builtin_memcpy(&p, proto, sizeof(Env));
+    const void *k = reinterpret_cast<const void *>(&mcts_env_kernel<Env, NC>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((mcts_env_kernel<Env, NC>), dim3(blocks), dim3(Eng::THREADS), lds_bytes, s, *a, p);
+    return (int)hipGetLastError();
+}
+
+}  // namespace tw

@@ -2,7 +2,7 @@
 // environment (include/twisterl_device_env.hpp), and the argument structs a device-environment module shares with the library.
 //
 // A module (twisterl_amd.build.build_device_env) instantiates rollout_env_kernel<Env, NC> / solve_env_kernel<Env, NC> and their
-// launchers through TW_DEVICE_ENV; the library (tw_device_env.hip) owns everything around them: the checks, the workspace, the scan,
+// launchers through TW_DEVICE_ENV (TW_DEVICE_ENV_SEARCH: mcts_env_kernel<Env, NC> of tw_mcts_env.hpp as well); the library (tw_device_env.hip) owns everything around them: the checks, the workspace, the scan,
 // GAE and compaction, the error messages, the hand-off to the host-stepped path for what the kernels do not take.  Per record, in the
 // order of PPOCollector::single_collect (collector/ppo.rs:69-80): observe -> twist of the ids -> EngineV::forward -> act_perm -> mask
 // -> reward -> Gumbel arg-max over the environment's actions; store the record and the ids, then is_final / step.  Same RNG keys and
@@ -39,6 +39,38 @@ struct EnvSolveArgs {
     uint32_t *err;                   // as EnvRolloutArgs::err (|= 4: an attempt did not end within max_steps steps)
 };
 
+// Self-play (solve_on == 0) and MCTS-guided evaluate (solve_on != 0) of mcts_env_kernel (tw_mcts_env.hpp), which a module has when it
+// was built with TW_DEVICE_ENV_SEARCH.  One column = one episode, or one attempt (episode, search) as in EnvSolveArgs.
+struct EnvMctsArgs {
+    uint32_t   struct_bytes, pad0;   // sizeof(EnvMctsArgs) as the caller knows it: the launcher refuses another one (hipErrorInvalidValue)
+    PolicyDev  pol;
+    PaddedTraj out;                  // self-play: records [E][t_pad] with the MCTS probabilities in the four logit slots, value 0, reward =
+                                     // env.reward() of the recorded state; ep_len
+    uint16_t  *obs16;                // self-play: [E][t_pad][n_obs] obs ids, as EnvRolloutArgs::obs16
+    uint32_t  *err;                  // as EnvRolloutArgs::err / EnvSolveArgs::err; zeroed by the library before the launch
+    uint32_t  *col_err;              // [columns][4], zeroed likewise: {0} = the column ended by itself, else {1 + kind, ordinal, what, 0} --
+                                     // kind 0: obs id `what` out of range, 1: observe_n count `what` out of range, at the column's
+                                     // evaluation number `ordinal` (0 = its first); kind 2: not ended within t_pad records / max_steps
+                                     // steps, after `ordinal` evaluations
+    uint64_t   num_columns, episode_offset, seed;
+    uint32_t   num_searches, max_expand_depth;
+    float      C;
+    uint32_t   node_cap;             // nodes per column's tree, at least env_mcts_node_cap()
+    void      *arena;                // [columns][node_cap] nodes of ENV_MCTS_NODE_BYTES
+    unsigned long long *eval_count;  // [1] += the policy evaluations the searches consumed (roots and leaves)
+    uint32_t   solve_on, deterministic, attempts /* per episode */, max_steps;
+    float     *success, *total;      // solve mode: [columns]
+    uint32_t  *n_steps;              // solve mode: [columns]
+};
+constexpr int ENV_MCTS_NODE_BYTES = 32;
+// the most nodes one move's tree can hold: the root, its children, and per search at most max(max_expand_depth, 1) expansions
+constexpr uint64_t env_mcts_node_cap(uint32_t n_actions, uint32_t num_searches, uint32_t max_expand_depth)
+{
+    return 1ull + n_actions + (uint64_t)n_actions * num_searches * (max_expand_depth ? max_expand_depth : 1u);
+}
+// LDS of mcts_env_kernel behind the engine's: the ids of the 16 columns' pending states
+constexpr size_t env_mcts_pending_bytes(uint32_t n_obs) { return (size_t)16 * n_obs * sizeof(int); }
+
 // EngineV column count for an environment of n_obs ids: the smallest instantiation the Puzzle kernels already use
 constexpr int env_engine_nc(int n_obs) { return n_obs <= 4 ? 4 : n_obs <= 9 ? 9 : n_obs <= 16 ? 16 : n_obs <= 25 ? 25 : n_obs <= 36 ? 36 : 64; }
 
@@ -62,6 +94,10 @@ struct tw_device_env {
     int   (*obs_size)(const void *env);
     int   (*n_obs_of)(const void *env);                    // ids per observation of THIS object: n_obs, or the struct's own n_obs() (<= n_obs)
     void  (*fill_vtable)(tw_env_vtable *out);
+    // null unless the module was built with TW_DEVICE_ENV_SEARCH: the launcher of mcts_env_kernel (tw_mcts_env.hpp).  lds_bytes is the
+    // engine's share; the launcher adds env_mcts_pending_bytes(n_obs).  (layout[2], this struct's size, tells the two layouts apart;
+    // the launcher itself checks EnvMctsArgs::struct_bytes.)
+    int (*launch_search)(const tw::EnvMctsArgs *a, const void *proto, unsigned blocks, size_t engine_lds_bytes, hipStream_t s);
 };
 
 inline void tw_device_env_layout(uint32_t (&out)[TW_DEVICE_ENV_LAYOUT_WORDS])

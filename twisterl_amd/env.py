@@ -227,7 +227,8 @@ class DeviceEnvDesc(C.Structure):
                 ("engine_nc", C.c_uint32), ("type_name", C.c_char_p), ("launch_rollout", C.c_void_p), ("launch_solve", C.c_void_p),
                 ("create", C.CFUNCTYPE(C.c_void_p, C.POINTER(C.c_double), C.c_int)),
                 ("get_difficulty", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("set_difficulty", C.CFUNCTYPE(None, C.c_void_p, C.c_int)),
-                ("obs_size", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("n_obs_of", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("fill_vtable", C.c_void_p)]
+                ("obs_size", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("n_obs_of", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("fill_vtable", C.c_void_p),
+                ("launch_search", C.c_void_p)]
 
 
 class DeviceEnv:
@@ -236,7 +237,9 @@ class DeviceEnv:
     tw_device_env_<name>.  `params` go to the struct's init() (the environment's constructor arguments).
 
     PPOCollector.collect and evaluate run its episodes inside one kernel each (tw_ppo_collect_device_env / tw_evaluate_device_env);
-    AZCollector.collect and solve step the same struct's host code (tw_az_collect_env / tw_solve_env32).  The object itself is a
+    a module built with build_device_env(..., search=True) runs AZCollector.collect and evaluate with MCTS inside one kernel too
+    (tw_az_collect_device_env; `search` says whether the module has that kernel), any other module steps the same struct's host
+    code for those (tw_az_collect_env / tw_evaluate_env), and solve always does (tw_solve_env32).  The object itself is a
     host copy of the struct with the PyBaseEnv surface (reset / step / masks / observe / reward / is_final); collectors clone
     it and reset the clones, as the reference does (collector/ppo.rs:59-60).
 
@@ -303,6 +306,11 @@ class DeviceEnv:
     @property
     def obs_size(self) -> int:
         return int(self._desc.obs_size(self._obj))
+
+    @property
+    def search(self) -> bool:
+        """The module holds the search kernel (built with search=True): self-play and MCTS-guided evaluate run on the device."""
+        return bool(self._desc.launch_search)
 
     @property
     def variable_obs(self) -> bool:
