@@ -37,6 +37,9 @@
 // node's state by replaying the actions from the move's root, where the host path keeps a clone per node, and the two must agree.  An id outside [0, obs_size()) fails the collect ("index out of bounds: obs id ..."), an
 // episode that has not ended within the collect's max_records_per_episode records fails it too -- as on the host-stepped path.  A
 // collect whose max_records_per_episode is above 1,820 (what the finalize step's LDS tile holds) runs on the host-stepped path.
+// More episodes than the GPU holds columns at once (the module's own occupancy x the compute units x 16): the PPO collect and the plain
+// evaluate run on a persistent grid whose columns take the next episode from a device-side queue -- reset() is then called again on a
+// fresh clone of the prototype, from the same single place in the kernel; the bytes are those of one column per episode.
 // A struct that holds instances of several sizes may add `int n_obs() const`, 1..N_OBS and CONSTANT for the object's lifetime (the
 // library reads it once, from the prototype): observe() then writes that many ids.
 // Observations of VARIABLE length (the reference's Env::observe returns a Vec of any length and its EmbeddingBag adds however many
@@ -122,9 +125,10 @@ struct DeviceEnvModule {
         if (VAR_OBS) v->observe_n = observe_n;
     }
 
-    static const tw_device_env *descriptor(const char *type_name, decltype(tw_device_env::launch_search) search = nullptr)
+    static const tw_device_env *descriptor(const char *type_name, decltype(tw_device_env::launch_search) search = nullptr,
+                                           decltype(tw_device_env::groups_per_cu) groups = groups_per_cu_env<T>)
     {
-        static const tw_device_env d = [type_name, search]() {
+        static const tw_device_env d = [type_name, search, groups]() {
             tw_device_env x{};
             tw_device_env_layout(x.layout);
             x.num_actions = (uint32_t)A; x.n_obs = (uint32_t)NO; x.state_bytes = (uint32_t)sizeof(T); x.engine_nc = (uint32_t)env_engine_nc(NO);
@@ -133,6 +137,7 @@ struct DeviceEnvModule {
             x.create = create; x.get_difficulty = get_difficulty; x.set_difficulty = set_difficulty; x.obs_size = obs_size; x.n_obs_of = n_obs_of;
             x.fill_vtable = fill_vtable;
             x.launch_search = search;                                     // (TW_DEVICE_ENV: null, and no third kernel in the module)
+            x.groups_per_cu = groups;                                     // (occupancy of the kernels THIS module holds)
             return x;
         }();
         return &d;
@@ -159,5 +164,6 @@ struct DeviceEnvModule {
                   "twisterl device environment: TW_DEVICE_ENV_SEARCH needs a struct of at most 128 bytes (the search kernel keeps two copies in registers)"); \
     extern "C" __attribute__((visibility("default"))) const tw_device_env *tw_device_env_##name(void)      \
     {                                                                                                       \
-        return ::tw::DeviceEnvModule<Type>::descriptor(#Type, ::tw::launch_mcts_env<Type>);                 \
+        return ::tw::DeviceEnvModule<Type>::descriptor(#Type, ::tw::launch_mcts_env<Type>,                  \
+                                                       ::tw::groups_per_cu_search_env<Type>);               \
     }

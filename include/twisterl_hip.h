@@ -86,6 +86,10 @@ enum {
                             /* the stored output of its grandparent (same board): 0 product, 1 no reuse, 3 by the link only, */
                             /* 4 by the link while counting where the path level would have differed; 2 (the path level at   */
                             /* any depth, which returns different bytes) is refused with TW_ERR_INVALID                      */
+    TW_OPT_ENV_RESIDENT_GROUPS = 6, /* device environments (twisterl_device_env.hpp): N > 0 caps the TOTAL number of workgroups  */
+                            /* their three kernels keep resident, so that a handful of episodes reaches the persistent     */
+                            /* grid and its queue (test hook); 0: automatic (what the kernel's occupancy allows on the CUs */
+                            /* that reserve_cus leaves); a negative value is refused with TW_ERR_INVALID                   */
     TW_OPT_AZ_VARIANT = 2   /* self-play with few deep searches: 0 automatic (walker-per-wave kernel where it applies),    */
                             /* 2 always the lane-per-episode kernel; walker kernel with a pinned shape: 3 / 4 / 5 / 6 =    */
                             /* two / one / four / eight walkers per workgroup, + 16 / + 32 = the 16- / 32-column engine,   */

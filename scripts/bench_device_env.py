@@ -15,6 +15,11 @@ device collect is checked byte-equal to the host one first.
 else "host_stepped".  The comparison is this command on two trees: --tree names the checkout whose package, tests/ helpers and
 built library are measured (default: the tree the script lies in); a tree from before the search kernel builds the plain module
 and its collect is host-stepped.  profiles/r08_device_env_search.jsonl holds the two rows.
+
+--no-persist: TW_OPT_NO_PERSIST = 1 for the whole run -- one workgroup per 16 episodes whatever their number, instead of the persistent
+grid with its episode queue that a collect of more episodes than the chip holds columns gets by itself.  Every device row says which
+of the two ran ("persist") and the grid ("blocks").  --skip-host leaves the host-stepped rows (and the byte comparison with them) out:
+the A/B of two trees or two launch forms needs only the device rows.  profiles/r09_device_env_persist.jsonl.
 """
 import argparse
 import ctypes as C
@@ -41,6 +46,8 @@ def az(args):
     from tests.util import amd_policy, make_deep_policy_arrays
     if twisterl_amd.device_count() < 1:
         raise SystemExit("no GPU")
+    if args.no_persist:
+        _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
     can_search = "search" in inspect.signature(build_device_env).parameters
     name = "gridworld5x5_az" if can_search else "gridworld5x5"
     so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if can_search else {}))
@@ -71,6 +78,8 @@ def az(args):
            "wall_ms": round(t * 1e3, 3), "records_per_s": round(n / t, 1),
            "ms_rollout": round(float(stats.get("ms_rollout", 0.0)), 3) if on_device else None,
            "evaluations": evals, "evaluations_per_s": round(evals / t, 1) if evals else None,
+           "persist": _lib.debug_last_launch()["persist"] if on_device else None, "blocks": _lib.debug_last_launch()["blocks"] if on_device else None,
+           "wall_ms_all": [round(r[0] * 1e3, 3) for r in runs],
            "reps": args.reps, "device": twisterl_amd.device_info()["name"]}
     print(json.dumps(row), flush=True)
     if args.out:
@@ -88,6 +97,8 @@ def main():
     ap.add_argument("--az", action="store_true", help="self-play (AZCollector.collect) instead of the PPO collect; appends one row to --out")
     ap.add_argument("--az-shape", default="4096x100", help="episodes x num_mcts_searches of --az")
     ap.add_argument("--tree", default=None, help="the checkout to measure (default: this one)")
+    ap.add_argument("--no-persist", action="store_true", help="TW_OPT_NO_PERSIST = 1: never the persistent grid + episode queue")
+    ap.add_argument("--skip-host", action="store_true", help="device rows only (no host-stepped rows, no byte comparison with them)")
     args = ap.parse_args()
     if args.az:
         return az(args)
@@ -99,6 +110,8 @@ def main():
     from tests.util import amd_policy, make_deep_policy_arrays
     if twisterl_amd.device_count() < 1:
         raise SystemExit("no GPU")
+    if args.no_persist:
+        _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
     if args.env == "lamps40":
         from tests.var_obs_util import lamps, lamps_policy_arrays
         env, pol = lamps(40), amd_policy(lamps_policy_arrays(40))
@@ -122,10 +135,11 @@ def main():
     rows = []
     info = twisterl_amd.device_info()
     for E in [int(x) for x in args.episodes.split(",")]:
-        g, h = device(E, 1), host(E, 1)
-        a, b = g.to_numpy(), h.to_numpy()
-        assert all(a[k].tobytes() == b[k].tobytes() for k in a), "device and host collects differ"
-        for path, fn in (("device", device), ("host_stepped", host)):
+        if not args.skip_host:
+            g, h = device(E, 1), host(E, 1)
+            a, b = g.to_numpy(), h.to_numpy()
+            assert all(a[k].tobytes() == b[k].tobytes() for k in a), "device and host collects differ"
+        for path, fn in (("device", device),) + (() if args.skip_host else (("host_stepped", host),)):
             for i in range(args.warmup):
                 fn(E, 100 + i)
             ts, recs, roll = [], [], []
@@ -140,6 +154,9 @@ def main():
             row = {"env": env_name, "policy": pol_name, "path": path, "episodes": E,
                    "records": recs[k], "wall_ms": round(ts[k] * 1e3, 3), "records_per_s": round(recs[k] / ts[k], 1),
                    "ms_rollout": round(roll[k], 3) if path == "device" else None, "reps": args.reps, "device": info["name"]}
+            if path == "device":
+                last = _lib.debug_last_launch()
+                row.update(persist=last.get("persist"), blocks=last.get("blocks"), wall_ms_all=[round(t * 1e3, 3) for t in ts])
             rows.append(row)
             print(json.dumps(row), flush=True)
     if args.out:

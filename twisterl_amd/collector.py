@@ -527,11 +527,11 @@ def _collect_device_env(self, env: DeviceEnv, policy: Policy, seed) -> Collected
     L = _lib.lib()
     if self._IS_PPO:
         prm = _lib.PPOParams(self.num_episodes, self.episode_offset, self.gamma, self.lambda_, sd, _lib.PRECISIONS[self.precision],
-                             int(self.merge_order), 0)
+                             int(self.merge_order), max(0, int(self.reserve_cus)))
         _lib.check(L.tw_ppo_collect_device_env(desc, proto, nbytes, h, C.byref(prm), env.max_records, C.byref(out)))
     else:
         prm = _lib.AZParams(self.num_episodes, self.episode_offset, self.num_mcts_searches, self.C, self.max_expand_depth, sd,
-                            _lib.PRECISIONS[self.precision], int(self.merge_order), 0)
+                            _lib.PRECISIONS[self.precision], int(self.merge_order), max(0, int(self.reserve_cus)))
         _lib.check(L.tw_az_collect_device_env(desc, proto, nbytes, h, C.byref(prm), env.max_records, C.byref(out)))
     return CollectedData._from_device(_DeviceResult(out.value))
 

@@ -46,8 +46,8 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
 hipStream_t current_stream() { return g_stream; }
 
 // ---------------------------------------------------------------------------------- launch options / per-device caches
-static std::atomic<int> g_force_geom{0}, g_no_persist{0}, g_az_variant{0}, g_az_tree_budget{0}, g_az_tree_budget_min{0}, g_az_reuse{0};
-LaunchOptions launch_options() { return LaunchOptions{g_force_geom.load(), g_no_persist.load(), g_az_variant.load(), g_az_tree_budget.load(), g_az_tree_budget_min.load(), g_az_reuse.load()}; }
+static std::atomic<int> g_force_geom{0}, g_no_persist{0}, g_az_variant{0}, g_az_tree_budget{0}, g_az_tree_budget_min{0}, g_az_reuse{0}, g_env_resident_groups{0};
+LaunchOptions launch_options() { return LaunchOptions{g_force_geom.load(), g_no_persist.load(), g_az_variant.load(), g_az_tree_budget.load(), g_az_tree_budget_min.load(), g_az_reuse.load(), g_env_resident_groups.load()}; }
 // counters of the last self-play launch (eval_count[0..15], see MctsArgs): tw_debug_counters
 static std::mutex g_dbg_mutex;
 static unsigned long long g_dbg_counters[16];
@@ -259,6 +259,9 @@ extern "C" int tw_set_launch_option(int option, int value)
             // (2, the path level whatever the depth, read another board's output below PATH_DEPTH: profiles/r03_az_reuse_probe.txt)
             if (value < 0 || value > 4 || value == 2) { set_error("TW_OPT_AZ_REUSE: value %d not in {0, 1, 3, 4}", value); return TW_ERR_INVALID; }
             g_az_reuse.store(value); return TW_OK;
+        case TW_OPT_ENV_RESIDENT_GROUPS:
+            if (value < 0) { set_error("TW_OPT_ENV_RESIDENT_GROUPS: %d workgroups (0 = automatic, else > 0)", value); return TW_ERR_INVALID; }
+            g_env_resident_groups.store(value); return TW_OK;
         default: set_error("tw_set_launch_option: unknown option %d", option); return TW_ERR_INVALID;
     }
 }
@@ -281,6 +284,12 @@ void note_launch(int family, int nt, int nc, int nw, int nwk, bool persist, bool
 {
     std::lock_guard<std::mutex> lock(g_dbg_mutex);
     g_last_launch = tw_launch_info{family, nt, nc, nw, nwk, persist, solve, dec, split, blocks, threads, engine_blocks, engine_threads};
+}
+void note_attempts(const float *success, const float *total, const uint32_t *n_steps, uint64_t n)
+{
+    std::lock_guard<std::mutex> lock(g_dbg_mutex);
+    g_att_success.assign(success, success + n); g_att_total.assign(total, total + n);
+    if (n_steps) g_att_steps.assign(n_steps, n_steps + n); else g_att_steps.assign(n, 0u);
 }
 }  // namespace tw
 static void forget_last_launch()

@@ -113,7 +113,7 @@ int  hip_fail(hipError_t e, const char *what, const char *file, int line);
 hipStream_t current_stream();
 
 // Diagnostic launch overrides (tw_set_launch_option; the tests pin launch shapes with them).  Read once per collect.
-struct LaunchOptions { int force_geom; int no_persist; int az_variant; int az_tree_budget; int az_tree_budget_min; int az_reuse; };
+struct LaunchOptions { int force_geom; int no_persist; int az_variant; int az_tree_budget; int az_tree_budget_min; int az_reuse; int env_resident_groups; };
 LaunchOptions launch_options();
 // Raises a kernel's dynamic-LDS limit above the 64 KiB default; cached per (kernel, device), thread-safe.
 int ensure_dynamic_lds(const void *kernel, size_t bytes);
@@ -123,6 +123,8 @@ int device_cus();
 // from their own template parameters (one host-side store per launch).
 void note_launch(int family, int nt, int nc, int nw, int nwk, bool persist, bool solve, bool dec, bool split, uint32_t blocks, uint32_t threads,
                  uint32_t engine_blocks = 0, uint32_t engine_threads = 0);
+// Test hook (tw_debug_last_attempts): the per-attempt results an evaluate on the device read back (n_steps may be null: zeros)
+void note_attempts(const float *success, const float *total, const uint32_t *n_steps, uint64_t n);
 
 // ---- RNG streams (see DESIGN.md "RNG spec") -------------------------------------------------
 enum : uint32_t {

@@ -60,7 +60,7 @@ int check_descriptor(const tw_device_env *d, const void *proto, size_t proto_byt
                   mine[0], mine[1], mine[2], mine[3], mine[4], mine[5], mine[6], mine[7]);
         return TW_ERR_INVALID;
     }
-    if (!d->launch_rollout || !d->launch_solve || !d->create || !d->get_difficulty || !d->set_difficulty || !d->obs_size || !d->n_obs_of || !d->fill_vtable) {
+    if (!d->launch_rollout || !d->launch_solve || !d->groups_per_cu || !d->create || !d->get_difficulty || !d->set_difficulty || !d->obs_size || !d->n_obs_of || !d->fill_vtable) {
         set_error("%s: the device environment descriptor lacks a function", who); return TW_ERR_INVALID;
     }
     if (d->num_actions < 1 || d->num_actions > 4 || d->n_obs < 1 || d->n_obs > 64 || d->engine_nc != (uint32_t)env_engine_nc((int)d->n_obs)) {
@@ -102,6 +102,30 @@ int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
 {
     if ((int)vt.num_actions != pd->n_actions) { set_error("environment has %u actions, policy has %d (at most 31)", vt.num_actions, pd->n_actions); return TW_ERR_INVALID; }
     if ((int)vt.obs_size != pd->obs_size) { set_error("index out of bounds: policy obs_size %d != environment obs ids %u", pd->obs_size, vt.obs_size); return TW_ERR_INVALID; }
+    return TW_OK;
+}
+
+// The grid of a module's rollout (0) or solve (1) kernel over `columns` episodes or attempts.  (The search kernel, 2, has no persistent
+// form: a first one faulted on the device and was taken out again -- DESIGN.md §8.)  As many workgroups
+// as the kernel's own occupancy puts on the CUs that reserve_cus leaves are resident at once (TW_OPT_ENV_RESIDENT_GROUPS > 0 caps
+// their total: the test hook); more columns than those hold run on a PERSISTENT grid of that size whose columns take the next
+// episode from a 32-bit counter (EnvRolloutArgs::queue), which starts at the number of slots and is taken once more by every slot that
+// finds it empty: columns + slots must fit 32 bits.  Otherwise -- and with TW_OPT_NO_PERSIST -- one workgroup per 16 columns, as ever.
+struct EnvGrid { uint64_t blocks; bool persist; };
+int env_grid(const tw_device_env *d, int kernel, size_t lds_bytes, uint64_t columns, uint32_t reserve_cus, EnvGrid *g)
+{
+    g->blocks = (columns + GEN_COLS - 1) / GEN_COLS; g->persist = false;
+    const LaunchOptions o = launch_options();
+    if (o.no_persist) return TW_OK;
+    int per_cu = 0;
+    const int e = d->groups_per_cu(kernel, lds_bytes, &per_cu);
+    if (e != (int)hipSuccess) return hip_fail((hipError_t)e, "device environment occupancy query", __FILE__, __LINE__);
+    if (per_cu < 1) { set_error("device environment: the kernel does not fit a compute unit with %zu bytes of LDS", lds_bytes); return TW_ERR_UNSUPPORTED; }
+    const uint64_t cus = (uint64_t)device_cus(), keep = reserve_cus < cus - 1 ? reserve_cus : cus - 1;   // reserve_cus CUs stay free (RCCL beside the grid)
+    uint64_t groups = (uint64_t)per_cu * (cus - keep);
+    if (o.env_resident_groups > 0 && (uint64_t)o.env_resident_groups < groups) groups = (uint64_t)o.env_resident_groups;
+    const uint64_t slots = groups * GEN_COLS;
+    if (columns > slots && columns + slots <= 0xffffffffull) { g->blocks = groups; g->persist = true; }
     return TW_OK;
 }
 
@@ -181,17 +205,19 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     const bool ragged = vt.observe_n != nullptr;                          // observations of variable length: two-byte ids, 0xFFFF = no id
     const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
-    const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;
-    if (blocks > 0x7fffffffull || t_pad > 0x7fffffffull) { set_error("tw_ppo_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
     const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
     if (lds_bytes > 159 * 1024) { set_error("rollout: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
+    EnvGrid grid;
+    rc = env_grid(env, 0, lds_bytes, E, prm->reserve_cus, &grid); if (rc) return rc;
+    const uint64_t blocks = grid.blocks;
+    if (blocks > 0x7fffffffull || t_pad > 0x7fffffffull) { set_error("tw_ppo_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
 
     std::lock_guard<std::mutex> lock(workspace_mutex());
     hipStream_t s = current_stream();
     size_t cur = 0;
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
-    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(16), o_scan = seg(scan_scratch_bytes(E)),
-                 o_obs16 = seg(R * NO * 2);
+    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(32), o_scan = seg(scan_scratch_bytes(E)),
+                 o_obs16 = seg(R * NO * 2);                                // (o_total: record total | err | the episode queue's counter)
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
     uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
@@ -205,11 +231,16 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
 
     struct Events { hipEvent_t ev[5] = {}; ~Events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); } } ev;
     for (auto &e : ev.ev) TW_HIP(hipEventCreate(&e));
-    TW_HIP(hipMemsetAsync(ws + o_total, 0, 16, s));
+    TW_HIP(hipMemsetAsync(ws + o_total, 0, 32, s));
+    if (grid.persist) {                                                   // slot i starts with episode i; the queue starts behind the slots
+        ra.queue = reinterpret_cast<unsigned int *>(ws + o_total + 16);
+        const unsigned int first = (unsigned int)(blocks * GEN_COLS);
+        TW_HIP(hipMemcpyAsync(ra.queue, &first, 4, hipMemcpyHostToDevice, s));
+    }
     TW_HIP(hipEventRecord(ev.ev[0], s));
     const int lr = env->launch_rollout(&ra, proto, (unsigned)blocks, lds_bytes, s);
     if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment rollout launch", __FILE__, __LINE__);
-    note_launch(TW_KERNEL_ROLLOUT_BIG, 1, (int)env->engine_nc, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
+    note_launch(TW_KERNEL_ROLLOUT_BIG, 1, (int)env->engine_nc, 0, 0, grid.persist, false, false, false, (uint32_t)blocks, 256);
     TW_HIP(hipEventRecord(ev.ev[1], s));
     rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;
@@ -326,12 +357,12 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     const bool ragged = vt.observe_n != nullptr;
     const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
-    const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;
-    if (blocks > 0x7fffffffull) { set_error("tw_az_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
     const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
     if (lds_bytes + env_mcts_pending_bytes(env->n_obs) > 159 * 1024) {
         set_error("mcts: %zu bytes of LDS needed, 159 KiB available", lds_bytes + env_mcts_pending_bytes(env->n_obs)); return TW_ERR_UNSUPPORTED;
     }
+    const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;              // (the search kernel has no persistent form: one column per episode)
+    if (blocks > 0x7fffffffull) { set_error("tw_az_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
 
     std::lock_guard<std::mutex> lock(workspace_mutex());
     hipStream_t s = current_stream();
@@ -453,12 +484,16 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_evaluate_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }
     rc = require_device(); if (rc) return rc;
     const uint64_t N = prm->num_searches, NA = num_episodes * N;
-    const uint64_t blocks = (NA + GEN_COLS - 1) / GEN_COLS;
-    if (NA / N != num_episodes || blocks > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
+    if (NA / N != num_episodes) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
     const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
     if (lds_bytes + (mcts ? env_mcts_pending_bytes(env->n_obs) : 0) > 159 * 1024) {
         set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes + (mcts ? env_mcts_pending_bytes(env->n_obs) : 0)); return TW_ERR_UNSUPPORTED;
     }
+    EnvGrid grid;                                                         // (MCTS-guided attempts: the search kernel, one column per attempt)
+    grid.blocks = (NA + GEN_COLS - 1) / GEN_COLS; grid.persist = false;
+    if (!mcts) { rc = env_grid(env, 1, lds_bytes, NA, 0, &grid); if (rc) return rc; }
+    const uint64_t blocks = grid.blocks;
+    if (blocks > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
 
     std::vector<float> succ(NA), tot(NA);
     std::vector<uint32_t> steps(NA);
@@ -492,6 +527,7 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
             note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, true, false, false, (uint32_t)blocks, 256);
             TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
             TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
+            TW_HIP(hipMemcpyAsync(steps.data(), ws + o_n, NA * 4, hipMemcpyDeviceToHost, s));
             TW_HIP(hipMemcpyAsync(hv, ws + o_err, 8, hipMemcpyDeviceToHost, s));
             TW_HIP(hipStreamSynchronize(s));
             if ((uint32_t)hv[0] & 13u) {
@@ -518,9 +554,14 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
         sa.success = reinterpret_cast<float *>(ws + o_s); sa.total = reinterpret_cast<float *>(ws + o_t);
         sa.n_steps = reinterpret_cast<uint32_t *>(ws + o_n); sa.err = reinterpret_cast<uint32_t *>(ws + o_err);
         TW_HIP(hipMemsetAsync(ws + o_err, 0, 16, s));
+        if (grid.persist) {                                               // (o_err: err | the queue's counter)
+            sa.queue = reinterpret_cast<unsigned int *>(ws + o_err + 8);
+            const unsigned int first = (unsigned int)(blocks * GEN_COLS);
+            TW_HIP(hipMemcpyAsync(sa.queue, &first, 4, hipMemcpyHostToDevice, s));
+        }
         const int lr = env->launch_solve(&sa, proto, (unsigned)blocks, lds_bytes, s);
         if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment evaluate launch", __FILE__, __LINE__);
-        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
+        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, 0, 0, grid.persist, false, false, false, (uint32_t)blocks, 256);
         TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
         TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
         TW_HIP(hipMemcpyAsync(steps.data(), ws + o_n, NA * 4, hipMemcpyDeviceToHost, s));
@@ -528,6 +569,7 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
         TW_HIP(hipStreamSynchronize(s));
     }
     const uint32_t err = (uint32_t)hv[0];
+    note_attempts(succ.data(), tot.data(), steps.data(), NA);      // (tw_debug_last_attempts)
     if (err & 9u) {       // the first bad id (or count of observe_n) the host path meets: the smallest move, then the smallest attempt
                           // (its total holds the id / the count; a count: its success is 2.0f)
         uint64_t first = NA;

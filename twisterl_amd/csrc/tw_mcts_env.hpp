@@ -351,4 +351,18 @@ int launch_mcts_env(const EnvMctsArgs *a, const void *proto, unsigned blocks, si
     return (int)hipGetLastError();
 }
 
+// tw_device_env::groups_per_cu of a module with the search kernel (kernel 2: lds_bytes is the engine's share, as for the launcher)
+template <class Env>
+int groups_per_cu_search_env(int kernel, size_t lds_bytes, int *out)
+{
+    constexpr int NC = env_engine_nc(Env::N_OBS);
+    if (kernel != 2) return groups_per_cu_env<Env>(kernel, lds_bytes, out);
+    if (!out) return (int)hipErrorInvalidValue;
+    const size_t all = lds_bytes + env_mcts_pending_bytes(Env::N_OBS);
+    const void *k = reinterpret_cast<const void *>(&mcts_env_kernel<Env, NC>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)all);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, EngineV<NC>::THREADS, all);
+}
+
 }  // namespace tw

@@ -6,7 +6,9 @@
 // GAE and compaction, the error messages, the hand-off to the host-stepped path for what the kernels do not take.  Per record, in the
 // order of PPOCollector::single_collect (collector/ppo.rs:69-80): observe -> twist of the ids -> EngineV::forward -> act_perm -> mask
 // -> reward -> Gumbel arg-max over the environment's actions; store the record and the ids, then is_final / step.  Same RNG keys and
-// the same arithmetic as tw_ppo_collect_env / tw_evaluate_env over the environment's host vtable: bit-equal to them.
+// the same arithmetic as tw_ppo_collect_env / tw_evaluate_env over the environment's host vtable: bit-equal to them.  Both kernels have a
+// persistent form behind a run-time branch on their argument struct's `queue` (fewer columns than episodes; a column whose episode is
+// over takes the next one from a counter), which the library chooses from the kernel's own occupancy (tw_device_env::groups_per_cu).
 #pragma once
 #include "tw_engine_generic.hpp"
 
@@ -26,6 +28,9 @@ struct EnvRolloutArgs {
                                      // An episode that met a bad id (count) at record t ends there: its ep_len is (t + 1) | 1 << 31,
                                      // record t's value field holds the id (the count) as bits and its reward field is 0.0f (1.0f)
     uint64_t   num_episodes, episode_offset, seed;
+    unsigned int *queue;             // null: one column per episode (the grid covers them all).  Else the grid is PERSISTENT: fewer columns
+                                     // than episodes, column i starts with episode i, and a column whose episode is over takes the next
+                                     // index from this counter (which starts at the number of columns) until it passes num_episodes
 };
 
 // evaluate(): one column = one attempt (episode, search), as solve_big_kernel
@@ -37,6 +42,7 @@ struct EnvSolveArgs {
     uint32_t *n_steps;               // [num_attempts]; an attempt that met a bad id (a bad count of observe_n) at move t: t | 1 << 31,
                                      // its total = the id (the count) as bits; a bad count: its success = 2.0f
     uint32_t *err;                   // as EnvRolloutArgs::err (|= 4: an attempt did not end within max_steps steps)
+    unsigned int *queue;             // as EnvRolloutArgs::queue, over attempts
 };
 
 // Self-play (solve_on == 0) and MCTS-guided evaluate (solve_on != 0) of mcts_env_kernel (tw_mcts_env.hpp), which a module has when it
@@ -98,6 +104,10 @@ struct tw_device_env {
     // engine's share; the launcher adds env_mcts_pending_bytes(n_obs).  (layout[2], this struct's size, tells the two layouts apart;
     // the launcher itself checks EnvMctsArgs::struct_bytes.)
     int (*launch_search)(const tw::EnvMctsArgs *a, const void *proto, unsigned blocks, size_t engine_lds_bytes, hipStream_t s);
+    // how many workgroups of one of the module's kernels -- 0: rollout, 1: solve, 2: search -- a CU holds at once with lds_bytes of
+    // dynamic LDS (what the launcher of that kernel is given): the kernel's own answer, hipOccupancyMaxActiveBlocksPerMultiprocessor,
+    // from which the library sizes a persistent grid.  A hipError_t; kernel 2 of a module without the search kernel: hipErrorInvalidValue
+    int (*groups_per_cu)(int kernel, size_t lds_bytes, int *out);
 };
 
 inline void tw_device_env_layout(uint32_t (&out)[TW_DEVICE_ENV_LAYOUT_WORDS])
@@ -211,6 +221,11 @@ __device__ __forceinline__ int env_rows_n(const Env &st, const PolicyDev &pol, i
     return n;
 }
 
+// Persistent form (a.queue != null; a kernel-argument-uniform branch, not a second instantiation): the grid holds fewer columns than
+// there are episodes, and at the end of a step -- where ids and rowoff are dead -- a column whose episode is over takes the next index
+// from the counter.  The writer lane draws it; it goes round to every lane of every wave that carries column j through lds_user and
+// one barrier, which depends on a.queue alone (as rollout_f32_kernel does for Eng::SPLIT).  Records, ids and ep_len are addressed by
+// episode, so the bytes are those of the plain launch whichever column ran an episode.
 template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArgs a, const Env proto)
 {
@@ -221,16 +236,26 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
     eng.begin1(a.pol, lds);
     const int j = eng.j;
     // every lane group of every wave carries the state of column j (the engine's mapping); lanes 0-15 of wave 0 store
-    const uint64_t e_local = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-    const bool valid  = e_local < a.num_episodes;
+    const uint64_t e_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+    const bool valid  = e_first < a.num_episodes;
     const bool writer = eng.h == 0 && eng.primary();
-    const uint64_t e_global = a.episode_offset + e_local;
-    Env st = proto;                                                                   // clone of the prototype (ppo.rs:59)
-    if (valid) st.reset(a.seed, e_global);                                            // ppo.rs:60
-    bool alive = valid, failed = false;
+    uint32_t e_taken = 0xffffffffu;                                                   // the episode taken from the queue; none: e_first
+    Env st = proto;
+    bool alive = valid;
+    bool fresh = valid;                                                               // the column's episode is still to be reset
+    bool more  = valid && a.queue != nullptr;                                         // the queue may still hold episodes
     int  t = 0;
     eng.begin2();
     while (__syncthreads_or(alive ? 1 : 0)) {
+        const uint64_t e_local  = e_taken != 0xffffffffu ? (uint64_t)e_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+        const uint64_t e_global = a.episode_offset + e_local;
+        // the ONE place the struct's reset() is called from, the column's first episode and every one it takes from the queue alike
+        // (with a second call site the compiler stopped inlining it, and the state went to scratch memory)
+        if (fresh) {
+            st = proto;                                                               // clone of the prototype (ppo.rs:59)
+            st.reset(a.seed, e_global);                                               // ppo.rs:60
+            fresh = false;
+        }
         int perm = -1;
         if (eng.pol.n_perms > 0) {                                                    // get_perm_id (policy.rs:67-77)
             const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_PERM);
@@ -258,6 +283,7 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
         const u32x4 gw = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_GUMBEL);
         const int action = gumbel_argmax_n<A>(lg, gw);
         if (alive) {
+            bool failed = false;
             if (bad) {                                                                // (the host path fails the collect here)
                 if (writer) {                                                         // the library names the first one (t, episode)
                     const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
@@ -284,15 +310,33 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
                     alive = false;
                 } else { st.step(action); ++t; }                                      // ppo.rs:79
             }
+            // the episode is over: its length at once (the column may go on with another one)
+            if (!alive && writer) a.out.ep_len[e_local] = ((uint32_t)t + 1u) | (failed ? 0x80000000u : 0u);
+        }
+        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
+            const bool want = !alive && more;
+            unsigned got = 0xffffffffu;
+            if (want && writer) got = atomicAdd(a.queue, 1u);
+            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
+            if (writer) bc[j] = got;
+            __syncthreads();
+            got = bc[j];
+            if (want) {
+                if ((uint64_t)got < a.num_episodes) {
+                    e_taken = got;
+                    t = 0; alive = true; fresh = true;                                // (reset at the top of the next step)
+                } else more = false;
+            }
         }
     }
-    if (valid && writer) a.out.ep_len[e_local] = ((uint32_t)t + 1u) | (failed ? 0x80000000u : 0u);
     eng.end();
 }
 
 // evaluate() (rust/src/rl/evaluate.rs:22-89 over single_solve, rl/solve.rs:17-71), as solve_big_kernel: one column = one attempt
 // (episode e, search a): reset, then while !is_final { total += reward; probs = Policy::predict (masked softmax, random twist);
-// action = argmax | weighted sample; step }.  Best-of-N and the means are reduced on the host.
+// action = argmax | weighted sample; step }.  Best-of-N and the means are reduced on the host.  An attempt's three results are
+// written when it ends; with a.queue its column then takes the next attempt, as rollout_env_kernel takes episodes.  The key of an
+// attempt's draws, ep * num_searches + att % num_searches, is episode_offset * num_searches + att: no division on the step path.
 template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a, const Env proto)
 {
@@ -301,19 +345,30 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.begin1(a.pol, lds);
-    const uint64_t att = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)eng.j;
-    const bool valid = att < a.num_attempts, writer = eng.h == 0 && eng.primary();
-    const uint64_t ep  = a.episode_offset + att / a.num_searches;                    // episode: keys the start state
-    const uint64_t key = ep * (uint64_t)a.num_searches + att % a.num_searches;       // keys this attempt's draws
-    Env st = proto;                                                                   // evaluate.rs:39
-    if (valid) st.reset(a.seed, ep);
-    bool  alive = valid && !st.is_final(), failed = false;                            // solve.rs:29
+    const int j = eng.j;
+    const uint64_t att_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+    const bool valid = att_first < a.num_attempts, writer = eng.h == 0 && eng.primary();
+    uint32_t att_taken = 0xffffffffu;                                                 // the attempt taken from the queue; none: att_first
+    Env st = proto;
+    bool  alive = valid;                                                              // (a fresh attempt: until its reset below says otherwise)
+    bool  fresh = valid;                                                              // the column's attempt is still to be reset
+    bool  more  = valid && a.queue != nullptr;
     float total = 0.0f;
-    int   bad_first = 0;
-    [[maybe_unused]] bool bad_first_count = false;
     int   t = 0;
     eng.begin2();
     while (__syncthreads_or(alive ? 1 : 0)) {
+        const uint64_t att = att_taken != 0xffffffffu ? (uint64_t)att_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+        const uint64_t key = a.episode_offset * (uint64_t)a.num_searches + att;       // keys this attempt's draws
+        bool ended = false;                                                           // the attempt ended by itself in this step
+        // the ONE place reset() is called from (see rollout_env_kernel).  A fresh attempt whose reset state is already final is over
+        // at once (solve.rs:29): its column feeds no row to this step's forward and takes the next attempt at the end of it
+        if (fresh) {
+            st = proto;                                                               // evaluate.rs:39
+            st.reset(a.seed, a.episode_offset + att / a.num_searches);                // the episode keys the start state
+            total = 0.0f; t = 0; fresh = false;
+            alive = !st.is_final();
+            ended = !alive;
+        }
         int perm = -1;
         if (eng.pol.n_perms > 0) {
             const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_PERM);
@@ -337,13 +392,12 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
         masked_softmax4(lg, mb, probs);                                               // policy.rs:43-47 (masked entries add +0.0)
         if (alive) {
             if (bad) {
-                if constexpr (EnvHasObserveN<Env>::value) {
-                    if (writer) atomicOr(a.err, bad_count ? 8u : 1u);
-                    bad_first_count = bad_count;
-                } else {
-                    if (writer) atomicOr(a.err, 1u);
+                if (writer) {
+                    atomicOr(a.err, bad_count ? 8u : 1u);
+                    a.success[att] = bad_count ? 2.0f : (st.success() ? 1.0f : 0.0f);
+                    a.total[att]   = __builtin_bit_cast(float, bad_id);
+                    a.n_steps[att] = (uint32_t)t | 0x80000000u;
                 }
-                failed = true; bad_first = bad_id;
                 alive = false;
             } else {
                 total = total + st.reward();                                          // solve.rs:31
@@ -363,15 +417,29 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
                     if (writer) atomicOr(a.err, 4u);
                     alive = false;
                 }
+                ended = !alive;
             }
         }
-    }
-    if (valid && writer) {
-        total = total + st.reward();                                                  // solve.rs:65-66
-        a.success[att] = st.success() ? 1.0f : 0.0f;                                  // solve.rs:68
-        if constexpr (EnvHasObserveN<Env>::value) { if (bad_first_count) a.success[att] = 2.0f; }
-        a.total[att]   = failed ? __builtin_bit_cast(float, bad_first) : total;
-        a.n_steps[att] = (uint32_t)t | (failed ? 0x80000000u : 0u);
+        if (ended && writer) {                                                        // its results (solve.rs:65-68), after t moves
+            a.success[att] = st.success() ? 1.0f : 0.0f;
+            a.total[att]   = total + st.reward();
+            a.n_steps[att] = (uint32_t)t;
+        }
+        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
+            const bool want = !alive && more;
+            unsigned got = 0xffffffffu;
+            if (want && writer) got = atomicAdd(a.queue, 1u);
+            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
+            if (writer) bc[j] = got;
+            __syncthreads();
+            got = bc[j];
+            if (want) {
+                if ((uint64_t)got < a.num_attempts) {
+                    att_taken = got;
+                    alive = true; fresh = true;                                       // (reset at the top of the next step)
+                } else more = false;
+            }
+        }
     }
     eng.end();
 }
@@ -387,6 +455,18 @@ int launch_rollout_env(const EnvRolloutArgs *a, const void *proto, unsigned bloc
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((rollout_env_kernel<Env, NC>), dim3(blocks), dim3(EngineV<NC>::THREADS), lds_bytes, s, *a, p);
     return (int)hipGetLastError();
+}
+
+// tw_device_env::groups_per_cu of a module without the search kernel (with it: groups_per_cu_search_env, tw_mcts_env.hpp)
+template <class Env>
+int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
+{
+    constexpr int NC = env_engine_nc(Env::N_OBS);
+    if (!out || (kernel != 0 && kernel != 1)) return (int)hipErrorInvalidValue;
+    const void *k = kernel == 0 ? reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>) : reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, EngineV<NC>::THREADS, lds_bytes);
 }
 
 template <class Env>

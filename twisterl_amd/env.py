@@ -228,7 +228,8 @@ class DeviceEnvDesc(C.Structure):
                 ("create", C.CFUNCTYPE(C.c_void_p, C.POINTER(C.c_double), C.c_int)),
                 ("get_difficulty", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("set_difficulty", C.CFUNCTYPE(None, C.c_void_p, C.c_int)),
                 ("obs_size", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("n_obs_of", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("fill_vtable", C.c_void_p),
-                ("launch_search", C.c_void_p)]
+                ("launch_search", C.c_void_p),
+                ("groups_per_cu", C.CFUNCTYPE(C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int)))]
 
 
 class DeviceEnv:
