@@ -46,7 +46,9 @@
 // vectors it is given): define observe_n() instead of observe().  It writes the ids of the current state -- at most N_OBS (n_obs()) of
 // them, WHATEVER it returns, in the order the embedding adds them -- and returns their number; 0 is legal (the embedding is then its
 // bias).  Write ids[i] with indices the compiler can resolve after unrolling (slot i = the i-th id, not ids[k++]), or the array goes to
-// scratch memory.  A count outside 0..N_OBS fails the collect ("observation of %u ids, at most %u") without anything being indexed
+// scratch memory.  So does a struct that holds an array it indexes at run time: that is no build error, the kernels then keep the
+// state in scratch memory, and tests/test_gpu_device_env_matrix.py holds such structs (128 bytes and 1 KiB) to the host path's BYTES,
+// not to a speed.  A count outside 0..N_OBS fails the collect ("observation of %u ids, at most %u") without anything being indexed
 // by it.  The collected obs field is then two-byte ids [records][N_OBS], a record's ids first and 0xFFFF in the slots it leaves free
 // (2 x N_OBS bytes per record however short the observation); the module's host vtable carries observe_n, and observe (the ids,
 // then -1) for hosts that only know the fixed-length member.

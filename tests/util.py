@@ -40,6 +40,12 @@ def make_deep_policy_arrays(n2, seed=0, emb=64, common=(128, 64), policy_layers=
     """Weights of a BasicPolicy with any number of common / policy / value layers (src/twisterl/nn/policy.py:60-113 builds
     them with make_sequential: every hidden Linear is followed by ReLU, the final action / value Linear is not) in the
     reference's export layout (src/twisterl/nn/utils.py:17-42)."""
+    return make_deep_policy_arrays_obs(n2 * n2, seed=seed, emb=emb, common=common, policy_layers=policy_layers, value_layers=value_layers,
+                                       n_actions=n_actions, scale=scale)
+
+
+def make_deep_policy_arrays_obs(obs_size, seed=0, emb=64, common=(128, 64), policy_layers=(), value_layers=(), n_actions=4, scale=1.0):
+    """make_deep_policy_arrays over any obs_size (not only a square): the same draws in the same order."""
     rng = np.random.default_rng(seed)
 
     def lin(i, o, relu):
@@ -48,8 +54,8 @@ def make_deep_policy_arrays(n2, seed=0, emb=64, common=(128, 64), policy_layers=
         bias = rng.uniform(-b, b, size=o).astype(np.float32)
         return (np.ascontiguousarray(w.T).reshape(-1), bias, relu)
 
-    b0 = scale / np.sqrt(n2 * n2)
-    we = rng.uniform(-b0, b0, size=(emb, n2 * n2)).astype(np.float32)
+    b0 = scale / np.sqrt(obs_size)
+    we = rng.uniform(-b0, b0, size=(emb, obs_size)).astype(np.float32)
     be = rng.uniform(-b0, b0, size=emb).astype(np.float32)
     cs, w = [], emb
     for h in common:

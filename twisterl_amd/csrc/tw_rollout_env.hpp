@@ -231,6 +231,10 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
 {
     using Eng = EngineV<NC>;
     constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
+    // EngineV<64> alone takes some 450 registers: a fixed-length observation of 37 .. 64 ids kept alive across the forward on top of
+    // them spilled to scratch memory.  There the ids are stored BEFORE the forward, as env_rows_n stores a variable-length record's
+    // (of an observation with a bad id the row is written all the same; the collect fails and nobody reads it)
+    constexpr bool EARLY_IDS = NC > 36 && !EnvHasObserveN<Env>::value;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.begin1(a.pol, lds);
@@ -268,7 +272,17 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
             if constexpr (EnvHasObserveN<Env>::value)
                 (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count,
                                           writer ? a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)env_n_obs(st) : nullptr);
-            else env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+            else {
+                env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+                if constexpr (EARLY_IDS) {
+                    if (writer) {
+                        const int n = env_n_obs(st);
+                        uint16_t *o = a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)n;
+#pragma unroll
+                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
+                    }
+                }
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < NC; ++i) rowoff[i] = -1;
@@ -297,7 +311,7 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
                     const uint64_t rec = e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
                     const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
                     store_rec(a.out.rec + rec, zero4, lg, value, rew, action, perm);
-                    if constexpr (!EnvHasObserveN<Env>::value) {                      // (observe_n: env_rows_n has stored them)
+                    if constexpr (!EnvHasObserveN<Env>::value && !EARLY_IDS) {        // (observe_n: env_rows_n has stored them)
                         const int n = env_n_obs(st);
                         uint16_t *o = a.obs16 + rec * (uint64_t)n;
 #pragma unroll
