@@ -90,6 +90,9 @@ enum {
                             /* their three kernels keep resident, so that a handful of episodes reaches the persistent     */
                             /* grid and its queue (test hook); 0: automatic (what the kernel's occupancy allows on the CUs */
                             /* that reserve_cus leaves); a negative value is refused with TW_ERR_INVALID                   */
+    TW_OPT_ROLLOUT_REUSE = 8, /* PPO rollout, 256-episode f32 shape: 0 (default) a step whose board and twist the episode     */
+                            /* recorded 2 or 4 steps ago takes that record's logits and value (the same bits) instead of a */
+                            /* forward; 1: every record comes out of a forward (no look-ups).  (7 is not assigned.)        */
     TW_OPT_AZ_VARIANT = 2   /* self-play with few deep searches: 0 automatic (walker-per-wave kernel where it applies),    */
                             /* 2 always the lane-per-episode kernel; walker kernel with a pinned shape: 3 / 4 / 5 / 6 =    */
                             /* two / one / four / eight walkers per workgroup, + 16 / + 32 = the 16- / 32-column engine,   */
@@ -421,7 +424,10 @@ typedef struct {
                             /* idle MFMA columns before a search asked for them (x twists)      */
     uint64_t reused_evals;  /* AZ, few deep searches: of forward_evals, the outputs a node took  */
                             /* from its grandparent (its move took the parent's move back: same */
-                            /* board, same output) instead of a column of a forward (x twists)  */
+                            /* board, same output) instead of a column of a forward (x twists). */
+                            /* PPO, 256-episode f32 rollout: of the records, the ones whose      */
+                            /* logits and value came from the episode's own record of the same  */
+                            /* board and twist 2 or 4 steps earlier (TW_OPT_ROLLOUT_REUSE)      */
 } tw_collect_stats;
 int  tw_collected_stats(const tw_collected *c, tw_collect_stats *out);
 /* Releases the result.  Its device memory goes to a per-process pool (freed by tw_release_cached_memory, or when the device

@@ -46,8 +46,8 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
 hipStream_t current_stream() { return g_stream; }
 
 // ---------------------------------------------------------------------------------- launch options / per-device caches
-static std::atomic<int> g_force_geom{0}, g_no_persist{0}, g_az_variant{0}, g_az_tree_budget{0}, g_az_tree_budget_min{0}, g_az_reuse{0}, g_env_resident_groups{0};
-LaunchOptions launch_options() { return LaunchOptions{g_force_geom.load(), g_no_persist.load(), g_az_variant.load(), g_az_tree_budget.load(), g_az_tree_budget_min.load(), g_az_reuse.load(), g_env_resident_groups.load()}; }
+static std::atomic<int> g_force_geom{0}, g_no_persist{0}, g_az_variant{0}, g_az_tree_budget{0}, g_az_tree_budget_min{0}, g_az_reuse{0}, g_env_resident_groups{0}, g_rollout_reuse_off{0};
+LaunchOptions launch_options() { return LaunchOptions{g_force_geom.load(), g_no_persist.load(), g_az_variant.load(), g_az_tree_budget.load(), g_az_tree_budget_min.load(), g_az_reuse.load(), g_env_resident_groups.load(), g_rollout_reuse_off.load()}; }
 // counters of the last self-play launch (eval_count[0..15], see MctsArgs): tw_debug_counters
 static std::mutex g_dbg_mutex;
 static unsigned long long g_dbg_counters[16];
@@ -259,6 +259,7 @@ extern "C" int tw_set_launch_option(int option, int value)
             // (2, the path level whatever the depth, read another board's output below PATH_DEPTH: profiles/r03_az_reuse_probe.txt)
             if (value < 0 || value > 4 || value == 2) { set_error("TW_OPT_AZ_REUSE: value %d not in {0, 1, 3, 4}", value); return TW_ERR_INVALID; }
             g_az_reuse.store(value); return TW_OK;
+        case TW_OPT_ROLLOUT_REUSE: g_rollout_reuse_off.store(value ? 1 : 0); return TW_OK;
         case TW_OPT_ENV_RESIDENT_GROUPS:
             if (value < 0) { set_error("TW_OPT_ENV_RESIDENT_GROUPS: %d workgroups (0 = automatic, else > 0)", value); return TW_ERR_INVALID; }
             g_env_resident_groups.store(value); return TW_OK;
@@ -1315,7 +1316,7 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
                             : prm->precision == TW_PREC_F32_EXACT ? f32_resident_episodes(E, (int)ra.pol.hidden, false, ra.reserve_cus)
                                                                   : rollout_f32_resident_episodes(ra.reserve_cus);
     const bool persist = E > resident && !launch_options().no_persist && !big;
-    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(16),     // (+8: range_flag)
+    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(16),     // (+8: range_flag, +12: RolloutArgs::reused)
                  o_scan = seg(scan_scratch_bytes(E)), o_init = seg(persist ? E * 16 : 0), o_queue = seg(persist ? 4 : 0),
                  o_obs16 = seg(big ? R * cells * 2 : 0), o_boards = seg(persist ? E * 8 : 0), o_ordscr = seg(persist ? episode_order_scratch_bytes(E) : 0);
     void *wsp = nullptr;
@@ -1328,6 +1329,12 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
 
     EventSet ev; rc = ev.init(); if (rc) return rc;
     tw_collect_stats st{};
+    const bool reuse_path = prm->precision == TW_PREC_F32_EXACT && !big && !ra.pol.generic;    // the launches that can take the 256-episode f32 shape
+    if (reuse_path) {
+        TW_HIP(hipMemsetAsync(ws + o_total + 8, 0, 8, s));
+        ra.reused = reinterpret_cast<unsigned int *>(ws + o_total + 12);
+        ra.reuse_off = launch_options().rollout_reuse_off ? 1u : 0u;
+    }
     if (prm->precision == TW_PREC_F16X2 && ra.pol.split_range) {   // the weight images' own flag, then whatever the kernel adds
         ra.range_flag = reinterpret_cast<uint32_t *>(ws + o_total + 8);
         TW_HIP(hipMemcpyAsync(ra.range_flag, ra.pol.split_range, 4, hipMemcpyDeviceToDevice, s));
@@ -1361,8 +1368,8 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
     rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;
     TW_HIP(hipEventRecord(ev.ev[2], s));
-    uint64_t total_and_flag[2] = {0, 0};          // {record count, range_flag}: one copy
-    TW_HIP(hipMemcpyAsync(total_and_flag, total_d, ra.range_flag ? 16 : 8, hipMemcpyDeviceToHost, s));
+    uint64_t total_and_flag[2] = {0, 0};          // {record count, range_flag | reused << 32}: one copy
+    TW_HIP(hipMemcpyAsync(total_and_flag, total_d, ra.range_flag || ra.reused ? 16 : 8, hipMemcpyDeviceToHost, s));
     TW_HIP(hipStreamSynchronize(s));
     const uint64_t total = total_and_flag[0];
     if (total_and_flag[1] & 0xffffffffull) {
@@ -1412,6 +1419,7 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
     TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[4])); st.ms_total = ms;
 #undef TW_HIP_C
     st.records = total; st.episodes = E; st.padded_bytes = cur; st.forward_evals = total;
+    st.reused_evals = ra.reused ? total_and_flag[1] >> 32 : 0;
     c->stats = st;
     *out = c;
     return TW_OK;

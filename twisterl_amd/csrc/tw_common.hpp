@@ -113,7 +113,7 @@ int  hip_fail(hipError_t e, const char *what, const char *file, int line);
 hipStream_t current_stream();
 
 // Diagnostic launch overrides (tw_set_launch_option; the tests pin launch shapes with them).  Read once per collect.
-struct LaunchOptions { int force_geom; int no_persist; int az_variant; int az_tree_budget; int az_tree_budget_min; int az_reuse; int env_resident_groups; };
+struct LaunchOptions { int force_geom; int no_persist; int az_variant; int az_tree_budget; int az_tree_budget_min; int az_reuse; int env_resident_groups; int rollout_reuse_off; };
 LaunchOptions launch_options();
 // Raises a kernel's dynamic-LDS limit above the 64 KiB default; cached per (kernel, device), thread-safe.
 int ensure_dynamic_lds(const void *kernel, size_t bytes);
@@ -479,6 +479,14 @@ __device__ inline void store_rec(PaddedRec *dst, const uint32_t (&obs4)[4], cons
                       (uint32_t)(action & 0xff) | ((uint32_t)(perm & 0xff) << 8), 0u);
 }
 
+// the three 16-byte words of a stored record: obs bytes | logits | {value, reward, action | perm << 8, 0} (the rollout's
+// fast-forward rounds read the episode's own records back, tw_rollout.hip)
+__device__ inline void load_rec(const PaddedRec *src, uint4 &obs4, uint4 &lg4, uint4 &tail4)
+{
+    const uint4 *d = reinterpret_cast<const uint4 *>(src);
+    obs4 = d[0]; lg4 = d[1]; tail4 = d[2];
+}
+
 // four nibbles (16 bits) -> four bytes
 __host__ __device__ inline uint32_t spread_nibbles4(uint32_t t16)
 {
@@ -526,6 +534,11 @@ struct RolloutArgs {
     // split-f16 mode: starts as the policy's split_range word; the kernel ORs in 1 when an activation leaves the range of the
     // split (EngineS::out_of_range) -- the host then runs the collect again in f32 (tw_ppo_collect)
     uint32_t       *range_flag;
+    // 256-episode f32 shape: a step whose (board, twist) the episode recorded 2 or 4 steps ago takes that record's logits and
+    // value instead of a forward (tw_rollout.hip: fast-forward rounds).  `reused` counts those records (zeroed before the
+    // launch; one atomic per wave at the kernel's end); reuse_off != 0 (TW_OPT_ROLLOUT_REUSE = 1): no look-ups at all.
+    unsigned int   *reused;
+    uint32_t        reuse_off;
 };
 
 // Waves per workgroup of the f32 engine for a batch of n columns (episodes / attempts): 8 (two per SIMD, 256 columns) is

@@ -182,6 +182,72 @@ int launch_episode_order(const PuzzleConsts &env, const uint64_t *boards, uint64
 
 TW_STAMP_ARRAY(g_gen_stamps, 8);   // cycle stamps of the generic engine and the 32- and 16-episode shapes (tw_common.hpp)
 
+// The tail of one step, shared by the forwarded step (RAW: `lg` comes out of the forward) and the fast-forward rounds of the
+// 256-episode shape (`lg` and `value` come out of one of the episode's own records: act-permuted and masked already): reward,
+// Gumbel arg-max, the record, is_final / step, and in persistent mode the next episode off the queue.  `on`: this lane takes the
+// step (the forwarded step: every lane; a round: the lanes that hit).
+template <int NW, bool PERSIST, bool RAW, class Eng>
+__device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleConsts &env, const Eng &eng, bool writer, bool on, int perm, float (&lg)[4], float value,
+                                          uint32_t &e_local, uint64_t &board, int &depth, int &t, bool &alive, bool &more)
+{
+    const int j = eng.j, h = eng.h;
+    PuzzleLane st; st.board = board; st.depth = depth;
+    { const int z = blank_cell(board); st.zx = z % env.width; st.zy = z / env.width; }
+    if constexpr (RAW) {
+        eng.act_perm(perm, lg);
+        const uint32_t mb = puzzle_maskbits(st, env);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lg[i] = ((mb >> i) & 1u) ? lg[i] : -1e10f;   // policy.rs:62
+    }
+    const float rew = puzzle_reward(st, env);
+    const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
+    int action;
+    if constexpr (NW == 8) action = gumbel_argmax4_halves(lg, gw, h != 0);   // (lanes j and j+32: one episode)
+    else action = gumbel_argmax4(lg, gw);
+    // ---- push the record (ppo.rs:71-76), then is_final / step (ppo.rs:78-79) --------------
+    if (alive && on) {
+        if (writer) {
+            const uint64_t rec = (uint64_t)e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
+            uint32_t obs_base[4], pk[4];
+            obs_base_words(env.n_cells, obs_base);
+            obs_bytes(board, obs_base, pk);
+            store_rec(a.out.rec + rec, pk, lg, value, rew, action, perm);
+        }
+        if (puzzle_final(st, env)) {
+            alive = false;
+            if constexpr (PERSIST) { if (writer) a.out.ep_len[e_local] = (uint32_t)t + 1u; }
+        } else { puzzle_step(st, env, action); board = st.board; depth = st.depth; ++t; }
+    }
+    if constexpr (PERSIST) {
+        const bool want = on && !alive && more;       // take the next episode off the queue (every lane of the episode the same one)
+        unsigned got = 0xffffffffu;
+        if (want && writer) got = atomicAdd(a.queue, 1u);
+        if constexpr (Eng::SPLIT) {                   // all waves of the workgroup carry this episode: hand the index round in LDS
+            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
+            if (writer) bc[j] = got;
+            __syncthreads();
+            got = bc[j];
+        } else got = (unsigned)__shfl((int)got, j, 64);
+        if (want) {
+            if ((uint64_t)got < a.num_episodes) {
+                const uint4 ib = a.init_boards[got];
+                e_local = ib.z; board = ((uint64_t)ib.y << 32) | ib.x; depth = env.depth0;
+                alive = true; t = 0;
+            } else more = false;
+        }
+    }
+}
+
+// Fast-forward rounds of the 256-episode shape: after a forwarded step every wave on its own takes up to REUSE_R
+// further steps whose output one of the episode's records of 2, 4, .. 2 * REUSE_LB steps ago holds (same obs bytes, same twist).
+#ifndef TW_REUSE_LB        // (-DTW_REUSE_LB / -DTW_REUSE_R with TW_VARIANT: the pairs measured in profiles/r10_rollout_reuse.txt)
+#define TW_REUSE_LB 2
+#endif
+#ifndef TW_REUSE_R
+#define TW_REUSE_R 2
+#endif
+constexpr int REUSE_LB = TW_REUSE_LB, REUSE_R = TW_REUSE_R;
+
 // (the generic engine's workgroups are small -- 256 threads, exact-size activation buffers: two of them share a CU, and while one
 //  gathers its embeddings from L2 the other one keeps the matrix cores busy)
 template <int NT, int NC, int NW = 8, bool PERSIST = false>
@@ -193,7 +259,7 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
     eng.begin1(a.pol, lds);                               // first weight chunks stream in while the scramble runs
 
     const PuzzleConsts env = a.env;
-    const int j = eng.j, h = eng.h;
+    const int h = eng.h;
     // Loop-carried per-episode state is kept to five registers (board, depth, episode, t): everything derivable (blank position,
     // global episode index, record address, obs-id constants) is recomputed after the forward -- held across it, those were the
     // registers the 8-wave x 256-accumulator shape spilled to scratch.
@@ -218,6 +284,10 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
     // (the barrier inside __syncthreads_or publishes the first two ring slots and the LDS constants)
     TW_STAMP(q_loop);
     TW_STAMP_VARS(n_fwd = 0);
+    // records taken from the trajectory: counted in one LDS word behind the engine's image (launch_geom adds it) -- a counter
+    // in a register would be live across the forward, which has none to spare
+    unsigned *reuse_cnt = nullptr;
+    if constexpr (NW == 8) { reuse_cnt = reinterpret_cast<unsigned *>(lds + Eng::lds_floats(a.pol)); if (threadIdx.x == 0) *reuse_cnt = 0u; }
 
     while (__syncthreads_or(alive ? 1 : 0)) {
         TW_STAMP_COUNT(n_fwd, 1);
@@ -233,48 +303,52 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
         float lg[4]; float value;
         eng.forward(rowoff, lg, value);
 
-        PuzzleLane st; st.board = board; st.depth = depth;
-        { const int z = blank_cell(board); st.zx = z % env.width; st.zy = z / env.width; }
-        eng.act_perm(perm, lg);
-        const uint32_t mb = puzzle_maskbits(st, env);
+        step_tail<NW, PERSIST, true>(a, env, eng, writer, true, perm, lg, value, e_local, board, depth, t, alive, more);
+
+        // ---- fast-forward rounds: a step whose (board, perm) the episode recorded 2k steps ago takes that record's output -----
+        if constexpr (NW == 8) {
+            if (!a.reuse_off) {
+                bool cand = writer;                       // a lane that missed stays where it is: it would miss again
+#pragma unroll 1
+                for (int r = 0; r < REUSE_R; ++r) {
+                    perm = -1;
+                    if (eng.pol.n_perms > 0) {
+                        const u32x4 w = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_PERM);
+                        perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
+                    }
+                    uint32_t obs_base[4], pk[4];
+                    obs_base_words(env.n_cells, obs_base);
+                    obs_bytes(board, obs_base, pk);
+                    const PaddedRec *cur = a.out.rec + (uint64_t)e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
+                    bool hit = false;
+                    uint4 hl = make_uint4(0u, 0u, 0u, 0u); uint32_t hv = 0u;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) lg[i] = ((mb >> i) & 1u) ? lg[i] : -1e10f;   // policy.rs:62
-        const float rew = puzzle_reward(st, env);
-        const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
-        int action;
-        if constexpr (NW == 8) action = gumbel_argmax4_halves(lg, gw, h != 0);   // (lanes j and j+32: one episode)
-        else action = gumbel_argmax4(lg, gw);
-        // ---- push the record (ppo.rs:71-76), then is_final / step (ppo.rs:78-79) --------------
-        if (alive) {
-            if (writer) {
-                const uint64_t rec = (uint64_t)e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
-                uint32_t obs_base[4], pk[4];
-                obs_base_words(env.n_cells, obs_base);
-                obs_bytes(board, obs_base, pk);
-                store_rec(a.out.rec + rec, pk, lg, value, rew, action, perm);
+                    for (int k = REUSE_LB; k >= 1; --k) {             // (the nearer record last: it wins, though any match holds the same bits)
+                        if (cand && alive && t >= 2 * k) {            // the lane that stored the record reads it: program order
+                            uint4 ko, kl, kt;
+                            load_rec(cur - 2 * k, ko, kl, kt);
+                            if (ko.x == pk[0] && ko.y == pk[1] && ko.z == pk[2] && ko.w == pk[3] && (kt.z >> 8) == (uint32_t)(perm & 0xff)) { hit = true; hl = kl; hv = kt.x; }
+                        }
+                    }
+                    const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
+                    if (hm == 0ull) break;
+                    if (hit) atomicAdd(reuse_cnt, 1u);
+                    cand = hit;
+                    // lane j -> lane j + 32 (swap(x, x)[0]: the lower half's x in every lane), as the Gumbel halves cross
+                    auto low = [](uint32_t x) { return __builtin_amdgcn_permlane32_swap(x, x, false, false)[0]; };
+                    const bool on = low(hit ? 1u : 0u) != 0u;
+                    lg[0] = __uint_as_float(low(hl.x)); lg[1] = __uint_as_float(low(hl.y));
+                    lg[2] = __uint_as_float(low(hl.z)); lg[3] = __uint_as_float(low(hl.w));
+                    value = __uint_as_float(low(hv));
+                    step_tail<NW, PERSIST, false>(a, env, eng, writer, on, perm, lg, value, e_local, board, depth, t, alive, more);
+                }
             }
-            if (puzzle_final(st, env)) {
-                alive = false;
-                if constexpr (PERSIST) { if (writer) a.out.ep_len[e_local] = (uint32_t)t + 1u; }
-            } else { puzzle_step(st, env, action); board = st.board; depth = st.depth; ++t; }
         }
-        if constexpr (PERSIST) {
-            const bool want = !alive && more;             // take the next episode off the queue (every lane of the episode the same one)
-            unsigned got = 0xffffffffu;
-            if (want && writer) got = atomicAdd(a.queue, 1u);
-            if constexpr (Eng::SPLIT) {                   // all waves of the workgroup carry this episode: hand the index round in LDS
-                unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
-                if (writer) bc[j] = got;
-                __syncthreads();
-                got = bc[j];
-            } else got = (unsigned)__shfl((int)got, j, 64);
-            if (want) {
-                if ((uint64_t)got < a.num_episodes) {
-                    const uint4 ib = a.init_boards[got];
-                    e_local = ib.z; board = ((uint64_t)ib.y << 32) | ib.x; depth = env.depth0;
-                    alive = true; t = 0;
-                } else more = false;
-            }
+    }
+    if constexpr (NW == 8) {                              // (behind the loop's last barrier) whichever wave comes first takes the count
+        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) {
+            const unsigned n = atomicExch(reuse_cnt, 0u);
+            if (n) atomicAdd(a.reused, n);
         }
     }
     if constexpr (!PERSIST) { if (valid && writer) a.out.ep_len[e_local] = (uint32_t)t + 1u; }
@@ -330,8 +404,9 @@ static int launch_geom(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, ui
     constexpr int EPB = G::Eng::EPB, THREADS = 64 * G::WAVES;
     const uint64_t nb = PERSIST ? persist_blocks(a.reserve_cus) * (NW == -65 ? generic_groups_per_cu(a.pol, a.env.n_cells) : 1) : (a.num_episodes + EPB - 1) / EPB;
     if (nb == 0 || nb > 0x7fffffffull) { set_error("rollout: bad episode count %llu", (unsigned long long)a.num_episodes); return TW_ERR_INVALID; }
-    const size_t lds_bytes = G::Eng::lds_floats(a.pol) * sizeof(float);
+    const size_t lds_bytes = G::Eng::lds_floats(a.pol) * sizeof(float) + (NW == 8 ? 16 : 0);    // (+ the 256-episode shape's reuse counter)
     if (lds_bytes > 159 * 1024) { set_error("rollout: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
+    if (NW == 8 && !a.reused && !a.reuse_off) { set_error("rollout: the 256-episode shape needs RolloutArgs::reused (or reuse_off)"); return TW_ERR_INVALID; }
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&rollout_f32_kernel<NT, NC, NW, PERSIST>), lds_bytes)) return rc;
     constexpr bool STAMPED = NW == -65 || NW == -16 || NW == -4;      // the shapes that take cycle stamps
     if constexpr (STAMPED) TW_STAMPS_CLEAR(g_gen_stamps);
