@@ -13,7 +13,7 @@
 //
 //   struct MyEnv {                                      // trivially copyable, default-constructible, at most 1 KiB: the prototype AND
 //                                                       // the per-episode state
-//       static constexpr int NUM_ACTIONS = 4;           // 1..4 (EngineV's head has four action columns)
+//       static constexpr int NUM_ACTIONS = 4;           // 1..4; 5..31 with TW_DEVICE_ENV_WIDE (below)
 //       static constexpr int N_OBS       = 25;          // observe() writes EXACTLY this many ids, 1..64 (observe_n(): at most)
 //       __host__ __device__ int      obs_size() const;  // every id < obs_size() <= 65535 (the policy's obs_size)
 //       __host__ __device__ int      difficulty() const;
@@ -52,6 +52,13 @@
 // by it.  The collected obs field is then two-byte ids [records][N_OBS], a record's ids first and 0xFFFF in the slots it leaves free
 // (2 x N_OBS bytes per record however short the observation); the module's host vtable carries observe_n, and observe (the ids,
 // then -1) for hosts that only know the fixed-length member.
+// More than four actions: `#define TW_DEVICE_ENV_WIDE` before this header (build_device_env(..., wide=True) emits it) lifts the bound
+// to 1..31, tw_env_vtable's own and what the one mask word holds; masks() stays a uint32_t, bit i < NUM_ACTIONS.  The SAME two kernels
+// then stream over the actions: the action head's outputs stay in LDS, a twist of the actions is an LDS index, the Gumbel words are
+// those of the host path (draw t | ((i >> 2) << 24), word i & 3), and the masked logits go to a workspace array of their own
+// (EnvRolloutArgs::lgw, NUM_ACTIONS floats per record).  Every addition is an `if constexpr (A > 4)`: a struct of at most four actions
+// compiles to the same kernels with or without the define.  TW_DEVICE_ENV_SEARCH does not take such a struct (the search kernel keeps
+// four children per node): its AZCollector.collect and evaluate with MCTS run host-stepped over the module's vtable.
 #pragma once
 
 #include "twisterl_hip.h"
@@ -68,7 +75,11 @@ struct DeviceEnvModule {
     static_assert(std::is_trivially_copyable<T>::value, "twisterl device environment: the struct must be trivially copyable (the kernels clone it by value)");
     static_assert(std::is_default_constructible<T>::value, "twisterl device environment: the struct must be default-constructible (init() fills a default-constructed one)");
     static_assert(sizeof(T) <= 1024, "twisterl device environment: the struct must be at most 1 KiB (it lives in registers on the device)");
-    static_assert(T::NUM_ACTIONS >= 1 && T::NUM_ACTIONS <= 4, "twisterl device environment: NUM_ACTIONS must be 1..4 (EngineV's head has four action columns)");
+#ifdef TW_DEVICE_ENV_WIDE
+    static_assert(T::NUM_ACTIONS >= 1 && T::NUM_ACTIONS <= 31, "twisterl device environment: NUM_ACTIONS must be 1..31 (tw_env_vtable's limit; masks() is one 32-bit word)");
+#else
+    static_assert(T::NUM_ACTIONS >= 1 && T::NUM_ACTIONS <= 4, "twisterl device environment: NUM_ACTIONS must be 1..4 (EngineV's head has four action columns); 5..31: define TW_DEVICE_ENV_WIDE / build_device_env(wide=True)");
+#endif
     static_assert(T::N_OBS >= 1 && T::N_OBS <= 64, "twisterl device environment: N_OBS must be 1..64");
     static constexpr bool VAR_OBS = EnvHasObserveN<T>::value;
     static_assert(VAR_OBS || EnvHasObserve<T>::value, "twisterl device environment: the struct needs `void observe(int *ids) const`, or `int observe_n(int *ids) const` for observations of variable length");
@@ -164,6 +175,8 @@ struct DeviceEnvModule {
 #define TW_DEVICE_ENV_SEARCH(Type, name)                                                                    \
     static_assert(sizeof(Type) <= TW_DEVICE_ENV_SEARCH_MAX_BYTES,                                           \
                   "twisterl device environment: TW_DEVICE_ENV_SEARCH needs a struct of at most 128 bytes (the search kernel keeps two copies in registers)"); \
+    static_assert(Type::NUM_ACTIONS <= 4,                                                                   \
+                  "twisterl device environment: TW_DEVICE_ENV_SEARCH needs NUM_ACTIONS 1..4 (the search kernel keeps four children per node); with 5..31 actions use TW_DEVICE_ENV: self-play and MCTS-evaluate then run host-stepped"); \
     extern "C" __attribute__((visibility("default"))) const tw_device_env *tw_device_env_##name(void)      \
     {                                                                                                       \
         return ::tw::DeviceEnvModule<Type>::descriptor(#Type, ::tw::launch_mcts_env<Type>,                  \

@@ -9,6 +9,10 @@ device collect is checked byte-equal to the host one first.
 --env lamps40: the same comparison for an environment whose observations vary in length (tests/device_envs/lamps.hpp with 40 lamps:
 0 .. 40 ids per state, obs_size 1,600, at most 24 records per episode; policy 1600-64-64-32 + heads): profiles/r07_var_obs.jsonl.
 
+--env perm8: an environment of MORE than four actions (examples/device_env/permutation.hpp with N = 8: 28 transpositions, 8 ids per
+state, obs_size 64, max_steps 32, difficulty 4; a module built with wide=True; policy 64-512-128-64 + heads -- two common layers: with one of 128 units and an obs_size of at most 256 the policy has
+the MFMA shape, which the device environments hand to the host-stepped path): the same two kernels stream over the 28 actions.  profiles/r11_device_env_wide.jsonl.
+
 --az: self-play instead.  Whole AZCollector.collect calls of GridWorld 5 x 5 with the same policy, --az-shape episodes x searches
 (4096x100; if the first call takes more than a minute the run goes on at 1024x32 and says so), median of --reps: ONE row, whose
 "path" is what the call ran on -- "device" when the library reports the module's search kernel (a module built with search=True),
@@ -93,7 +97,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--episodes", default="1024,65536")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--env", default="gridworld", choices=["gridworld", "lamps40"])
+    ap.add_argument("--env", default="gridworld", choices=["gridworld", "lamps40", "perm8"])
     ap.add_argument("--az", action="store_true", help="self-play (AZCollector.collect) instead of the PPO collect; appends one row to --out")
     ap.add_argument("--az-shape", default="4096x100", help="episodes x num_mcts_searches of --az")
     ap.add_argument("--tree", default=None, help="the checkout to measure (default: this one)")
@@ -116,6 +120,14 @@ def main():
         from tests.var_obs_util import lamps, lamps_policy_arrays
         env, pol = lamps(40), amd_policy(lamps_policy_arrays(40))
         env_name, pol_name = "Lamps40 (0..40 ids per state)", "1600-64-64-32+heads (generic)"
+    elif args.env == "perm8":
+        from twisterl_amd.build import build_device_env
+        from twisterl_amd.env import DeviceEnv
+        from tests.util import make_deep_policy_arrays_obs
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", "perm8", wide=True)
+        env = DeviceEnv(so, "perm8", [8, 32, 4], max_records=33)
+        pol = amd_policy(make_deep_policy_arrays_obs(64, seed=0, emb=512, common=(128, 64), n_actions=28))
+        env_name, pol_name = "Permutation8 (28 actions)", "64-512-128-64+heads (generic)"
     else:
         env = gridworld(max_steps=64, difficulty=1, max_records=65)
         pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
@@ -156,6 +168,7 @@ def main():
                    "ms_rollout": round(roll[k], 3) if path == "device" else None, "reps": args.reps, "device": info["name"]}
             if path == "device":
                 last = _lib.debug_last_launch()
+                assert last["family"] == _lib.TW_KERNEL_ROLLOUT_BIG, f"the device rows did not run the module's kernel: {last}"
                 row.update(persist=last.get("persist"), blocks=last.get("blocks"), wall_ms_all=[round(t * 1e3, 3) for t in ts])
             rows.append(row)
             print(json.dumps(row), flush=True)

@@ -6,7 +6,7 @@
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
 // the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error), solve
 // (the Python layer routes it), and -- for a module built without TW_DEVICE_ENV_SEARCH, whose descriptor has no search launcher --
-// self-play and evaluate with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), which lives in the module
+// self-play and evaluate with MCTS, as for every module of more than four actions (TW_DEVICE_ENV_WIDE).  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), which lives in the module
 // alone: tw_az_collect_device_env, and tw_evaluate_device_env with num_mcts_searches > 0.  The result is an ordinary tw_collected,
 // byte-equal to tw_ppo_collect_env / tw_az_collect_env over the same vtable.
 #include "tw_rollout_env.hpp"
@@ -63,7 +63,7 @@ int check_descriptor(const tw_device_env *d, const void *proto, size_t proto_byt
     if (!d->launch_rollout || !d->launch_solve || !d->groups_per_cu || !d->create || !d->get_difficulty || !d->set_difficulty || !d->obs_size || !d->n_obs_of || !d->fill_vtable) {
         set_error("%s: the device environment descriptor lacks a function", who); return TW_ERR_INVALID;
     }
-    if (d->num_actions < 1 || d->num_actions > 4 || d->n_obs < 1 || d->n_obs > 64 || d->engine_nc != (uint32_t)env_engine_nc((int)d->n_obs)) {
+    if (d->num_actions < 1 || d->num_actions > 31 || d->n_obs < 1 || d->n_obs > 64 || d->engine_nc != (uint32_t)env_engine_nc((int)d->n_obs)) {
         set_error("%s: descriptor with %u actions, %u obs ids, %u engine columns", who, d->num_actions, d->n_obs, d->engine_nc); return TW_ERR_INVALID;
     }
     if (proto_bytes != d->state_bytes) {
@@ -217,7 +217,8 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     size_t cur = 0;
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
     const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(32), o_scan = seg(scan_scratch_bytes(E)),
-                 o_obs16 = seg(R * NO * 2);                                // (o_total: record total | err | the episode queue's counter)
+                 o_obs16 = seg(R * NO * 2),                                // (o_total: record total | err | the episode queue's counter)
+                 o_lgw = seg(A > 4 ? R * A * sizeof(float) : 0);           // more than four actions: the masked logits, [E][t_pad][A]
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
     uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
@@ -225,6 +226,7 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     ra.pol = *pd;
     ra.out.rec = reinterpret_cast<PaddedRec *>(ws + o_rec); ra.out.ep_len = reinterpret_cast<uint32_t *>(ws + o_len); ra.out.t_pad = (int32_t)t_pad;
     ra.obs16 = reinterpret_cast<uint16_t *>(ws + o_obs16);
+    if (A > 4) ra.lgw = reinterpret_cast<float *>(ws + o_lgw);
     ra.err = reinterpret_cast<uint32_t *>(ws + o_total + 8);
     ra.num_episodes = E; ra.episode_offset = prm->episode_offset; ra.seed = prm->seed;
     uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
@@ -272,13 +274,14 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     if (err & 2u) { set_error("tw_ppo_collect_env: an episode did not end within %u records", max_records_per_episode); return TW_ERR_INVALID; }
     if (total == 0 || total > R) { set_error("collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
 
-    // ---- compact result: the fields of tw_ppo_collect_env, then (A < 4) the four-column logits the finalize kernel writes ------------
+    // ---- compact result: the fields of tw_ppo_collect_env, then (A != 4) the four-column logits the finalize kernel writes: A < 4
+    // narrows them to the environment's columns, A > 4 throws them away (the logits come from EnvRolloutArgs::lgw) ---------------------
     size_t ccur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
     auto put = [&](int f, size_t b) { bytes[f] = b; off[f] = ccur; ccur = (ccur + b + 255) / 256 * 256; };
     put(TW_F_OBS, total * NO * OW); put(TW_F_LOGITS, total * A * 4); put(TW_F_PERMS, total); put(TW_F_VALUES, total * 4); put(TW_F_REWARDS, total * 4);
     put(TW_F_ACTIONS, total); put(TW_F_ADVS, total * 4); put(TW_F_RETS, total * 4); put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
     const size_t o_lg4 = ccur;
-    if (A < 4) ccur += total * 16;
+    if (A != 4) ccur += total * 16;
     void *arena = nullptr; size_t cap = 0;
     rc = result_arena_acquire(ccur, &arena, &cap); if (rc) return rc;
     uint8_t *ca = reinterpret_cast<uint8_t *>(arena);
@@ -294,13 +297,16 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
 #define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
     CompactTraj ct{};
     ct.obs = nullptr;                                                          // (0 cells: the ids have their own array)
-    ct.logits = reinterpret_cast<float *>(A < 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]); ct.perms = reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]);
+    ct.logits = reinterpret_cast<float *>(A != 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]); ct.perms = reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]);
     ct.values = reinterpret_cast<float *>(ca + off[TW_F_VALUES]); ct.rewards = reinterpret_cast<float *>(ca + off[TW_F_REWARDS]);
     ct.actions = ca + off[TW_F_ACTIONS]; ct.advs = reinterpret_cast<float *>(ca + off[TW_F_ADVS]); ct.rets = reinterpret_cast<float *>(ca + off[TW_F_RETS]);
     TW_HIP_C(hipEventRecord(ev.ev[3], s));
     rc = launch_finalize_ppo(ra.out, ep_start_ws, E, 0, prm->gamma, prm->lambda, ct, s);
     if (rc == TW_OK && OW == 2)
         rc = launch_compact_obs16(ra.obs16, ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s);
+    if (rc == TW_OK && A > 4)                                                  // rows of A floats = 2A two-byte units: the same ragged row mover
+        rc = launch_compact_obs16(reinterpret_cast<const uint16_t *>(ra.lgw), ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)(2 * A),
+                                  reinterpret_cast<uint16_t *>(ca + off[TW_F_LOGITS]), s);
     if (rc) { tw_collected_free(c); return rc; }
     if (OW == 1) {
         hipLaunchKernelGGL(compact_env_obs8_kernel, dim3(grid_for(E, 4)), dim3(256), 0, s, ra.obs16, ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO,
@@ -344,7 +350,7 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     const tw_env_vtable vt = host_table(env, proto);
     const PolicyDev *pd = policy_dev(policy);
     uint64_t node_cap = 0;
-    if (!env->launch_search || !pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > FINALIZE_AZ_MAX_T_PAD ||
+    if (!env->launch_search || env->num_actions > 4 || !pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > FINALIZE_AZ_MAX_T_PAD ||
         !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_records_per_episode, &node_cap))
         return tw_az_collect_env(&vt, policy, prm, max_records_per_episode, out);
     if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
@@ -478,7 +484,7 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     const bool mcts = prm->num_mcts_searches != 0;
     uint64_t node_cap = 0;
     if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_searches == 0 || num_episodes == 0 || max_steps > 0x7fffffffu ||
-        (mcts && (!env->launch_search || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, &node_cap))))
+        (mcts && (!env->launch_search || env->num_actions > 4 || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, &node_cap))))
         return tw_evaluate_env(&vt, policy, prm, num_episodes, episode_offset, max_steps, success_rate, mean_reward);
     rc = check_env_policy(vt, pd); if (rc) return rc;
     if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_evaluate_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }

@@ -199,7 +199,17 @@ struct EngineV {
         return cur;
     }
 
-    __device__ __forceinline__ void forward(const int (&rowoff)[NC], float (&lg)[4], float &value)
+    // The forward of an environment with more than four actions (tw_rollout_env.hpp): the action head's outputs are handed over where
+    // they are, as [unit][column] rows of GEN_STRIDE floats in one of the activation buffers, instead of the four-value copy below.
+    // They stay valid until the next forward starts, and the caller puts a barrier between its last read and that call.
+    __device__ __forceinline__ const float *forward_head(const int (&rowoff)[NC], float &value)
+    {
+        float none[4];
+        return forward<true>(rowoff, none, value);
+    }
+
+    template <bool HEAD_IN_PLACE = false>
+    __device__ __forceinline__ const float *forward(const int (&rowoff)[NC], float (&lg)[4], float &value)
     {
         // EmbeddingBag (layers.rs:56-62,82-84): bias + the rows of the cells, in cell order
         TW_STAMP(c0);
@@ -314,6 +324,12 @@ struct EngineV {
         __syncthreads();
         TW_STAMP(c3);
         if (ao < 0) ao = stack(ls + pol.n_common, pol.n_action, co, co);                       // policy.rs:92
+        if constexpr (HEAD_IN_PLACE) {                                                         // (both heads are behind a barrier here)
+            value = lds_out[j * 8 + 4];
+            TW_STAMP(c4);
+            TW_STAMP_ADD(stq[0], c0, c1); TW_STAMP_ADD(stq[1], c1, c2); TW_STAMP_ADD(stq[2], c2, c3); TW_STAMP_ADD(stq[3], c3, c4);
+            return bufp(ao);
+        }
         if (g == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) lds_out[j * 8 + i] = bufp(ao)[i * GEN_STRIDE + j];
@@ -325,6 +341,7 @@ struct EngineV {
         TW_STAMP(c4);
         TW_STAMP_ADD(stq[0], c0, c1); TW_STAMP_ADD(stq[1], c1, c2); TW_STAMP_ADD(stq[2], c2, c3); TW_STAMP_ADD(stq[3], c3, c4);
         __syncthreads();           // (the buffers and lds_out are rewritten by the next forward)
+        return nullptr;
     }
 };
 

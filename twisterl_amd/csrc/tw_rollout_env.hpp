@@ -31,6 +31,8 @@ struct EnvRolloutArgs {
     unsigned int *queue;             // null: one column per episode (the grid covers them all).  Else the grid is PERSISTENT: fewer columns
                                      // than episodes, column i starts with episode i, and a column whose episode is over takes the next
                                      // index from this counter (which starts at the number of columns) until it passes num_episodes
+    float     *lgw;                  // an environment of more than four actions: [E][t_pad][A] masked logits of the records, addressed by
+                                     // episode like obs16 (the record's four logit slots are then zero and nobody reads them); else null
 };
 
 // evaluate(): one column = one attempt (episode, search), as solve_big_kernel
@@ -169,6 +171,82 @@ __device__ __forceinline__ void env_act_perm(const PolicyDev &pol, int perm, flo
     }
 }
 
+// ---- environments of 5 .. 31 actions (TW_DEVICE_ENV_WIDE) -----------------------------------------------------------------------------
+// The action head's outputs stay where EngineV::forward_head leaves them -- LDS, [unit][column] rows of GEN_STRIDE floats -- and the
+// step STREAMS over the actions instead of holding A values in registers (EngineV<64> alone takes some 450): action i reads unit
+// act_perms[perm][i] (i without a twist) of column j, so a twist is an LDS index, never an index into a register array.
+
+// the head's unit behind action i under twist `perm` (policy.rs:95-97; PolicyDev::act_perms is [n_perms][A])
+template <int A>
+__device__ __forceinline__ int env_head_unit(const PolicyDev &pol, int perm, int i) { return perm < 0 ? i : (int)pol.act_perms[perm * A + i]; }
+
+// The rollout's step: mask (policy.rs:62), sample_from_logits (policy.rs:169-172) with the words the host path takes
+// (tw_env_generic.hip: draw t | ((i >> 2) << 24), word i & 3), first maximum wins.  `row` (null: nothing is stored) is the record's
+// row of EnvRolloutArgs::lgw; all sixteen lane groups of the workgroup carry column j, so group g stores the logits g and g + 16.
+template <int A>
+__device__ __forceinline__ int env_gumbel_stream(const PolicyDev &pol, const float *head, int j, int g, int perm, uint32_t mb, uint64_t seed,
+                                                 uint64_t key, uint32_t t, float *row)
+{
+    // ONE rolled loop (a draw every fourth action): with EngineV<64> around it the kernel is large enough that every basic block counts
+    // towards the compiler's limit for inlining the struct's methods
+    int best = 0; float bv = 0.0f;
+    u32x4 w = {};
+#pragma unroll 1
+    for (int i = 0; i < A; ++i) {
+        if ((i & 3) == 0) w = rng_draw(seed, key, t | ((uint32_t)(i >> 2) << 24), STREAM_GUMBEL);
+        const uint32_t word = (i & 3) == 0 ? w.x : ((i & 3) == 1 ? w.y : ((i & 3) == 2 ? w.z : w.w));
+        const float l  = head[env_head_unit<A>(pol, perm, i) * GEN_STRIDE + j];
+        const float lm = ((mb >> i) & 1u) ? l : -1e10f;
+        if (row && g == (i & 15)) row[i] = lm;
+        const float a1 = tw_logf(u32_to_unit(word));
+        const float gi = lm - tw_logf(__builtin_fabsf(a1));
+        if (i == 0) { bv = gi; best = 0; } else if (gi > bv) { bv = gi; best = i; }
+    }
+    return best;
+}
+
+// evaluate's step: Policy::predict (policy.rs:43-47: tw_expf of the allowed logits, summed in index order, / (sum + 1e-6)) and the
+// arg-max of policy.rs:130-151 or nn::policy::sample (sample_weighted, tw_common.hpp), in passes over the LDS-resident logits: the
+// operations, their order and their bits are those of masked_softmax4 + sample_weighted over A values.
+template <int A>
+__device__ __forceinline__ float env_prob_at(const PolicyDev &pol, const float *head, int j, int perm, uint32_t mb, int i)
+{
+    return ((mb >> i) & 1u) ? tw_expf(head[env_head_unit<A>(pol, perm, i) * GEN_STRIDE + j]) : 0.0f;
+}
+template <int A>
+__device__ __forceinline__ int env_predict_stream(const PolicyDev &pol, const float *head, int j, int perm, uint32_t mb, bool deterministic, float u)
+{
+    // pass 0: the sum of the exponentials (den = 1: x / 1.0f is x); pass 1: the probabilities -- their arg-max, or their validity and
+    // total; pass 2 (sampling): the cumulative weights of the first A - 1 against u * total.  One loop body for all three.
+    float den = 1.0f, acc = 0.0f, bv = 0.0f, chosen = 0.0f;
+    bool bad = false, found = false;
+    int action = 0;
+    const int n_pass = deterministic ? 2 : 3;
+#pragma unroll 1
+    for (int pass = 0; pass < n_pass; ++pass) {
+        acc = 0.0f;
+#pragma unroll 1
+        for (int i = 0; i < A; ++i) {
+            const float p = env_prob_at<A>(pol, head, j, perm, mb, i) / den;
+            acc = acc + p;
+            if (pass == 1) {
+                if (!deterministic) { if (!(p >= 0.0f)) bad = true; }
+                else if (i == 0) bv = p;
+                else if (p > bv) { bv = p; action = i; }
+            } else if (pass == 2) {
+                if (i < A - 1 && !found && !(acc <= chosen)) { action = i; found = true; }
+            }
+        }
+        if (pass == 0) den = acc + 0.000001f;
+        else if (pass == 1 && !deterministic) {
+            if (bad || !(acc > 0.0f)) { action = 0; break; }                          // invalid weights: 0, as the reference
+            chosen = u * acc;
+            action = A - 1;
+        }
+    }
+    return action;
+}
+
 // observe + guard + twist: rows of the forward (-1 = no row) and the raw ids.  An id outside [0, obs_size) is never used as an
 // index: its row is -1, `bad` is set and `bad_id` is the FIRST such id of the observation (the one the host path reports; the
 // caller ends the episode and flags the collect).
@@ -287,15 +365,26 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
 #pragma unroll
             for (int i = 0; i < NC; ++i) rowoff[i] = -1;
         }
-        float lg[4]; float value;
+        float lg[4]; float value, rew; int action;
+        if constexpr (A > 4) {
+            // the masked logits go to their own array (the record's four slots stay zero); a record that is not pushed stores none
+            const float *head = eng.forward_head(rowoff, value);
+            const uint32_t mb = alive ? st.masks() : 0u;
+            rew = alive ? st.reward() : 0.0f;
+            float *row = alive && !bad ? a.lgw + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)A : nullptr;
+            action = env_gumbel_stream<A>(eng.pol, head, j, eng.g, perm, mb, a.seed, e_global, (uint32_t)t, row);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lg[i] = 0.0f;
+        } else {
         eng.forward(rowoff, lg, value);
         env_act_perm<A>(eng.pol, perm, lg);
         const uint32_t mb = alive ? st.masks() : 0u;
 #pragma unroll
         for (int i = 0; i < 4; ++i) lg[i] = (i < A && ((mb >> i) & 1u)) ? lg[i] : -1e10f;    // policy.rs:62
-        const float rew = alive ? st.reward() : 0.0f;
+        rew = alive ? st.reward() : 0.0f;
         const u32x4 gw = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_GUMBEL);
-        const int action = gumbel_argmax_n<A>(lg, gw);
+        action = gumbel_argmax_n<A>(lg, gw);
+        }
         if (alive) {
             bool failed = false;
             if (bad) {                                                                // (the host path fails the collect here)
@@ -399,11 +488,15 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
             for (int i = 0; i < NC; ++i) rowoff[i] = -1;
         }
         float lg[4], value;
-        eng.forward(rowoff, lg, value);
-        env_act_perm<A>(eng.pol, perm, lg);
+        [[maybe_unused]] const float *head = nullptr;
+        if constexpr (A > 4) head = eng.forward_head(rowoff, value);
+        else {
+            eng.forward(rowoff, lg, value);
+            env_act_perm<A>(eng.pol, perm, lg);
+        }
         const uint32_t mb = (alive ? st.masks() : 0u) & ((1u << A) - 1u);
-        float probs[4];
-        masked_softmax4(lg, mb, probs);                                               // policy.rs:43-47 (masked entries add +0.0)
+        [[maybe_unused]] float probs[4];
+        if constexpr (A <= 4) masked_softmax4(lg, mb, probs);                         // policy.rs:43-47 (masked entries add +0.0)
         if (alive) {
             if (bad) {
                 if (writer) {
@@ -416,7 +509,11 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
             } else {
                 total = total + st.reward();                                          // solve.rs:31
                 int action = 0;
-                if (a.deterministic) {
+                if constexpr (A > 4) {
+                    float u = 0.0f;
+                    if (!a.deterministic) u = u32_to_unit(rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE).x);
+                    action = env_predict_stream<A>(eng.pol, head, j, perm, mb, a.deterministic != 0u, u);
+                } else if (a.deterministic) {
                     float bv = probs[0];
 #pragma unroll
                     for (int i = 1; i < A; ++i) if (probs[i] > bv) { bv = probs[i]; action = i; }
