@@ -58,7 +58,10 @@
 // those of the host path (draw t | ((i >> 2) << 24), word i & 3), and the masked logits go to a workspace array of their own
 // (EnvRolloutArgs::lgw, NUM_ACTIONS floats per record).  Every addition is an `if constexpr (A > 4)`: a struct of at most four actions
 // compiles to the same kernels with or without the define.  TW_DEVICE_ENV_SEARCH does not take such a struct (the search kernel keeps
-// four children per node): its AZCollector.collect and evaluate with MCTS run host-stepped over the module's vtable.
+// four children per node there); TW_DEVICE_ENV_WIDE_SEARCH (at the end of this file, build_device_env(..., wide_search=True)) does:
+// self-play and MCTS-guided evaluate of 5..31 actions then run in the same mcts_env_kernel, which loops over a node's children and keeps
+// a column's probabilities in LDS, byte-equal to the host-stepped path.  A module built with the define alone (wide=True) has no search
+// kernel: its AZCollector.collect and evaluate with MCTS run host-stepped over the module's vtable.
 #pragma once
 
 #include "twisterl_hip.h"
@@ -176,9 +179,26 @@ struct DeviceEnvModule {
     static_assert(sizeof(Type) <= TW_DEVICE_ENV_SEARCH_MAX_BYTES,                                           \
                   "twisterl device environment: TW_DEVICE_ENV_SEARCH needs a struct of at most 128 bytes (the search kernel keeps two copies in registers)"); \
     static_assert(Type::NUM_ACTIONS <= 4,                                                                   \
-                  "twisterl device environment: TW_DEVICE_ENV_SEARCH needs NUM_ACTIONS 1..4 (the search kernel keeps four children per node); with 5..31 actions use TW_DEVICE_ENV: self-play and MCTS-evaluate then run host-stepped"); \
+                  "twisterl device environment: TW_DEVICE_ENV_SEARCH needs NUM_ACTIONS 1..4 (the search kernel keeps four children per node); with 5..31 actions use TW_DEVICE_ENV_WIDE_SEARCH / build_device_env(wide_search=True)"); \
     extern "C" __attribute__((visibility("default"))) const tw_device_env *tw_device_env_##name(void)      \
     {                                                                                                       \
         return ::tw::DeviceEnvModule<Type>::descriptor(#Type, ::tw::launch_mcts_env<Type>,                  \
                                                        ::tw::groups_per_cu_search_env<Type>);               \
     }
+
+// The search form for 1..31 actions: needs `#define TW_DEVICE_ENV_WIDE` in front of this header (build_device_env(..., wide_search=True)
+// emits both).  The same mcts_env_kernel: with more than four actions it walks a node's children in a loop and keeps its column's
+// probabilities in LDS; a struct of at most four actions compiles to the kernels of TW_DEVICE_ENV_SEARCH.  The 128-byte bound stays.
+#ifdef TW_DEVICE_ENV_WIDE
+#define TW_DEVICE_ENV_WIDE_SEARCH(Type, name)                                                               \
+    static_assert(sizeof(Type) <= TW_DEVICE_ENV_SEARCH_MAX_BYTES,                                           \
+                  "twisterl device environment: TW_DEVICE_ENV_WIDE_SEARCH needs a struct of at most 128 bytes (the search kernel keeps two copies in registers)"); \
+    extern "C" __attribute__((visibility("default"))) const tw_device_env *tw_device_env_##name(void)      \
+    {                                                                                                       \
+        return ::tw::DeviceEnvModule<Type>::descriptor(#Type, ::tw::launch_mcts_env<Type>,                  \
+                                                       ::tw::groups_per_cu_search_env<Type>);               \
+    }
+#else
+#define TW_DEVICE_ENV_WIDE_SEARCH(Type, name)                                                               \
+    static_assert(sizeof(Type) == 0, "twisterl device environment: TW_DEVICE_ENV_WIDE_SEARCH needs `#define TW_DEVICE_ENV_WIDE` in front of twisterl_device_env.hpp / build_device_env(wide_search=True)");
+#endif

@@ -18,7 +18,9 @@ the MFMA shape, which the device environments hand to the host-stepped path): th
 "path" is what the call ran on -- "device" when the library reports the module's search kernel (a module built with search=True),
 else "host_stepped".  The comparison is this command on two trees: --tree names the checkout whose package, tests/ helpers and
 built library are measured (default: the tree the script lies in); a tree from before the search kernel builds the plain module
-and its collect is host-stepped.  profiles/r08_device_env_search.jsonl holds the two rows.
+and its collect is host-stepped.  profiles/r08_device_env_search.jsonl holds the two rows.  --az --env perm8: the same for the 28 actions of
+Permutation8 with the policy of --env perm8 (a module built with wide_search=True; a tree from before the wide search builds it with
+wide=True and its collect is host-stepped): profiles/r12_device_env_wide_search.jsonl.
 
 --no-persist: TW_OPT_NO_PERSIST = 1 for the whole run -- one workgroup per 16 episodes whatever their number, instead of the persistent
 grid with its episode queue that a collect of more episodes than the chip holds columns gets by itself.  Every device row says which
@@ -39,7 +41,7 @@ sys.path.insert(0, ROOT)
 
 
 def az(args):
-    """One row: AZCollector.collect of GridWorld 5 x 5 on the path this tree takes for it."""
+    """One row: AZCollector.collect of GridWorld 5 x 5 (--env perm8: of the 28-action Permutation8) on the path this tree takes for it."""
     import inspect
     import numpy as np
     import twisterl_amd
@@ -52,11 +54,27 @@ def az(args):
         raise SystemExit("no GPU")
     if args.no_persist:
         _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
-    can_search = "search" in inspect.signature(build_device_env).parameters
-    name = "gridworld5x5_az" if can_search else "gridworld5x5"
-    so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if can_search else {}))
-    env = DeviceEnv(so, name, [5, 5, 64, 1], max_records=65)
-    pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
+    params = inspect.signature(build_device_env).parameters
+    if args.env == "perm8":
+        # 28 actions: the search kernel takes them in a module built with wide_search=True; a tree from before that builds the wide
+        # module without the search kernel and its collect is host-stepped
+        from tests.util import make_deep_policy_arrays_obs
+        can_search = "wide_search" in params
+        name = "perm8_az" if can_search else "perm8"
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", name,
+                              **({"wide_search": True} if can_search else {"wide": True}))
+        env = DeviceEnv(so, name, [8, 32, 4], max_records=33)
+        pol = amd_policy(make_deep_policy_arrays_obs(64, seed=0, emb=512, common=(128, 64), n_actions=28))
+        env_name, pol_name = "Permutation8 (28 actions)", "64-512-128-64+heads (generic)"
+    elif args.env != "gridworld":
+        raise SystemExit("--az: --env gridworld or perm8")
+    else:
+        can_search = "search" in params
+        name = "gridworld5x5_az" if can_search else "gridworld5x5"
+        so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if can_search else {}))
+        env = DeviceEnv(so, name, [5, 5, 64, 1], max_records=65)
+        pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
+        env_name, pol_name = "GridWorld5x5", "625-512-128+heads (generic)"
     E, S = (int(x) for x in args.az_shape.lower().split("x"))
 
     def collect(seed):
@@ -77,7 +95,7 @@ def az(args):
     t, n, stats = runs[k]
     on_device = _lib.debug_last_launch()["family"] == _lib.TW_KERNEL_MCTS_BIG
     evals = int(stats.get("forward_evals", 0)) if on_device else None
-    row = {"bench": "az", "env": "GridWorld5x5", "policy": "625-512-128+heads (generic)", "path": "device" if on_device else "host_stepped",
+    row = {"bench": "az", "env": env_name, "policy": pol_name, "path": "device" if on_device else "host_stepped",
            "episodes": E, "num_mcts_searches": S, "max_expand_depth": 1, "shape_fell_back": fell_back, "records": n,
            "wall_ms": round(t * 1e3, 3), "records_per_s": round(n / t, 1),
            "ms_rollout": round(float(stats.get("ms_rollout", 0.0)), 3) if on_device else None,

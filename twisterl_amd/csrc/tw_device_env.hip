@@ -5,8 +5,9 @@
 // else is here: the checks, the workspace, the scan / GAE / compaction of the Puzzle path (tw_finalize.hip), the error messages.
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
 // the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error), solve
-// (the Python layer routes it), and -- for a module built without TW_DEVICE_ENV_SEARCH, whose descriptor has no search launcher --
-// self-play and evaluate with MCTS, as for every module of more than four actions (TW_DEVICE_ENV_WIDE).  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), which lives in the module
+// (the Python layer routes it), and -- for a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has
+// no search launcher -- self-play and evaluate with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
+// 1..4 actions and (TW_DEVICE_ENV_WIDE_SEARCH) for 5..31, which lives in the module
 // alone: tw_az_collect_device_env, and tw_evaluate_device_env with num_mcts_searches > 0.  The result is an ordinary tw_collected,
 // byte-equal to tw_ppo_collect_env / tw_az_collect_env over the same vtable.
 #include "tw_rollout_env.hpp"
@@ -170,6 +171,14 @@ bool first_search_error(const std::vector<uint32_t> &ce, uint64_t n, uint32_t NO
     if (ce[4 * bad] == 2u) set_error("observation of %u ids, at most %u", ce[4 * bad + 2], NO);
     else set_error("index out of bounds: obs id %d, obs_size %d", (int)ce[4 * bad + 2], obs_size);
     return true;
+}
+
+// launch_search answered hipErrorInvalidValue: it refuses arguments it was not compiled for, above all an EnvMctsArgs of another size
+// (struct_bytes; the descriptor's layout words do not cover that struct)
+int search_launch_refused(const char *who)
+{
+    set_error("%s: the module's search launcher refused the arguments (it was compiled against another EnvMctsArgs): rebuild the module", who);
+    return TW_ERR_INVALID;
 }
 
 }  // namespace
@@ -350,7 +359,7 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     const tw_env_vtable vt = host_table(env, proto);
     const PolicyDev *pd = policy_dev(policy);
     uint64_t node_cap = 0;
-    if (!env->launch_search || env->num_actions > 4 || !pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > FINALIZE_AZ_MAX_T_PAD ||
+    if (!env->launch_search || !pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > FINALIZE_AZ_MAX_T_PAD ||
         !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_records_per_episode, &node_cap))
         return tw_az_collect_env(&vt, policy, prm, max_records_per_episode, out);
     if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
@@ -364,8 +373,9 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
     const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
-    if (lds_bytes + env_mcts_pending_bytes(env->n_obs) > 159 * 1024) {
-        set_error("mcts: %zu bytes of LDS needed, 159 KiB available", lds_bytes + env_mcts_pending_bytes(env->n_obs)); return TW_ERR_UNSUPPORTED;
+    const size_t search_lds = env_mcts_pending_bytes(env->n_obs) + env_mcts_probs_bytes(env->num_actions);      // what the launcher adds
+    if (lds_bytes + search_lds > 159 * 1024) {
+        set_error("mcts: %zu bytes of LDS needed, 159 KiB available", lds_bytes + search_lds); return TW_ERR_UNSUPPORTED;
     }
     const uint64_t blocks = (E + GEN_COLS - 1) / GEN_COLS;              // (the search kernel has no persistent form: one column per episode)
     if (blocks > 0x7fffffffull) { set_error("tw_az_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
@@ -375,7 +385,8 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     size_t cur = 0;
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
     const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(32), o_scan = seg(scan_scratch_bytes(E)),
-                 o_obs16 = seg(R * NO * 2), o_ce = seg(E * 16), o_arena = seg((size_t)E * node_cap * ENV_MCTS_NODE_BYTES);
+                 o_obs16 = seg(R * NO * 2), o_ce = seg(E * 16), o_arena = seg((size_t)E * node_cap * ENV_MCTS_NODE_BYTES),
+                 o_pw = seg(A > 4 ? R * A * sizeof(float) : 0);           // more than four actions: the MCTS probabilities, [E][t_pad][A]
     rc = check_memory_fit(cur, "tw_az_collect_device_env"); if (rc) return rc;
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
@@ -390,6 +401,7 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     ma.num_columns = E; ma.episode_offset = prm->episode_offset; ma.seed = prm->seed;
     ma.num_searches = prm->num_mcts_searches; ma.max_expand_depth = prm->max_expand_depth; ma.C = prm->C; ma.node_cap = (uint32_t)node_cap;
     ma.arena = ws + o_arena;
+    if (A > 4) ma.pw = reinterpret_cast<float *>(ws + o_pw);
     uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
 
     struct Events { hipEvent_t ev[5] = {}; ~Events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); } } ev;
@@ -398,6 +410,7 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     TW_HIP(hipMemsetAsync(ws + o_ce, 0, E * 16, s));
     TW_HIP(hipEventRecord(ev.ev[0], s));
     const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
+    if (lr == (int)hipErrorInvalidValue) return search_launch_refused("tw_az_collect_device_env");
     if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
     note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
     TW_HIP(hipEventRecord(ev.ev[1], s));
@@ -417,13 +430,14 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     }
     if (total == 0 || total > R) { set_error("az collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
 
-    // ---- compact result: the fields of tw_az_collect_env, then (A < 4) the four-column probabilities the finalize kernel writes ----------
+    // ---- compact result: the fields of tw_az_collect_env, then (A != 4) the four-column probabilities the finalize kernel writes: A < 4
+    // narrows them to the environment's columns, A > 4 throws them away (the probabilities come from EnvMctsArgs::pw) -------------------
     size_t ccur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
     auto put = [&](int f, size_t b) { bytes[f] = b; off[f] = ccur; ccur = (ccur + b + 255) / 256 * 256; };
     put(TW_F_OBS, total * NO * OW); put(TW_F_LOGITS, total * A * 4); put(TW_F_PERMS, total); put(TW_F_REMAINING, total * 4);
     put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
     const size_t o_lg4 = ccur;
-    if (A < 4) ccur += total * 16;
+    if (A != 4) ccur += total * 16;
     void *arena = nullptr; size_t cap = 0;
     rc = result_arena_acquire(ccur, &arena, &cap); if (rc) return rc;
     uint8_t *ca = reinterpret_cast<uint8_t *>(arena);
@@ -438,10 +452,13 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     if (ragged) collected_adopt_obs_ragged(c);
 #define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
     TW_HIP_C(hipEventRecord(ev.ev[3], s));
-    rc = launch_finalize_az(ma.out, ep_start_ws, E, 0, ca + off[TW_F_OBS], reinterpret_cast<float *>(A < 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]),
+    rc = launch_finalize_az(ma.out, ep_start_ws, E, 0, ca + off[TW_F_OBS], reinterpret_cast<float *>(A != 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]),
                             reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]), reinterpret_cast<float *>(ca + off[TW_F_REMAINING]), s);
     if (rc == TW_OK && OW == 2)
         rc = launch_compact_obs16(ma.obs16, ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s);
+    if (rc == TW_OK && A > 4)                                                  // rows of A floats = 2A two-byte units (the PPO path's row mover)
+        rc = launch_compact_obs16(reinterpret_cast<const uint16_t *>(ma.pw), ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)(2 * A),
+                                  reinterpret_cast<uint16_t *>(ca + off[TW_F_LOGITS]), s);
     if (rc) { tw_collected_free(c); return rc; }
     if (OW == 1) {
         hipLaunchKernelGGL(compact_env_obs8_kernel, dim3(grid_for(E, 4)), dim3(256), 0, s, ma.obs16, ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO,
@@ -484,7 +501,7 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     const bool mcts = prm->num_mcts_searches != 0;
     uint64_t node_cap = 0;
     if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_searches == 0 || num_episodes == 0 || max_steps > 0x7fffffffu ||
-        (mcts && (!env->launch_search || env->num_actions > 4 || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, &node_cap))))
+        (mcts && (!env->launch_search || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, &node_cap))))
         return tw_evaluate_env(&vt, policy, prm, num_episodes, episode_offset, max_steps, success_rate, mean_reward);
     rc = check_env_policy(vt, pd); if (rc) return rc;
     if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_evaluate_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }
@@ -492,8 +509,9 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     const uint64_t N = prm->num_searches, NA = num_episodes * N;
     if (NA / N != num_episodes) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
     const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
-    if (lds_bytes + (mcts ? env_mcts_pending_bytes(env->n_obs) : 0) > 159 * 1024) {
-        set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes + (mcts ? env_mcts_pending_bytes(env->n_obs) : 0)); return TW_ERR_UNSUPPORTED;
+    const size_t search_lds = mcts ? env_mcts_pending_bytes(env->n_obs) + env_mcts_probs_bytes(env->num_actions) : 0;
+    if (lds_bytes + search_lds > 159 * 1024) {
+        set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes + search_lds); return TW_ERR_UNSUPPORTED;
     }
     EnvGrid grid;                                                         // (MCTS-guided attempts: the search kernel, one column per attempt)
     grid.blocks = (NA + GEN_COLS - 1) / GEN_COLS; grid.persist = false;
@@ -529,6 +547,7 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
             TW_HIP(hipMemsetAsync(ws + o_err, 0, 32, s));
             TW_HIP(hipMemsetAsync(ws + o_ce, 0, NA * 16, s));
             const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
+            if (lr == (int)hipErrorInvalidValue) return search_launch_refused("tw_evaluate_device_env");
             if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
             note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, true, false, false, (uint32_t)blocks, 256);
             TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));

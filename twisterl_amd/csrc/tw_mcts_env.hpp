@@ -20,6 +20,11 @@
 //     t_pad records (solve mode: max_steps steps) sets bit 1 (bit 2) and leaves kind 2 with the evaluations it had consumed.
 // The library (tw_device_env.hip) owns the checks, the workspace, the scan / finalize / compaction and the messages.  A module gets
 // this kernel with TW_DEVICE_ENV_SEARCH; the MFMAs are EngineV's, the intrinsic form only (tw_engine_generic.hpp).
+// More than four actions (TW_DEVICE_ENV_WIDE_SEARCH): the SAME kernel, every difference an `if constexpr (A > 4)`.  The twist average
+// of the action head is kept per (action, column) in LDS behind the pending ids (env_mcts_probs_bytes), the owner lane turns its
+// column's row into the probabilities in place, and everything that was four registers -- the priors of the children just created, the
+// children of a node in the UCB descent, the visit counts at the end of a move -- is a rolled loop over that row or over the nodes
+// themselves: nothing of A values is ever a register array indexed at run time.  A record's A probabilities go to EnvMctsArgs::pw.
 #pragma once
 #include "tw_rollout_env.hpp"
 
@@ -47,12 +52,41 @@ __device__ __forceinline__ int env_twist_row(const PolicyDev &pol, int perm, int
                                                  : (int)pol.obs_perms[(size_t)perm * pol.obs_size + id]);
 }
 
+// sample_weighted (tw_common.hpp; the host path's sample_weighted_host) over n weights that are streamed -- w(i) reads weight i from
+// where it lives, LDS or the nodes just written -- instead of held: a weight that is negative or NaN gives 0, the cumulative sums run
+// in index order, the index is the number of leading sums <= u * total among the first n - 1.
+template <class W>
+__device__ __forceinline__ int env_sample_stream(W w, int n, float u)
+{
+    if (n <= 0) return 0;
+    float total = 0.0f;
+    bool bad = false;
+#pragma unroll 1
+    for (int i = 0; i < n; ++i) {
+        const float x = w(i);
+        if (!(x >= 0.0f)) bad = true;
+        total = total + x;
+    }
+    if (bad || !(total > 0.0f)) return 0;
+    const float chosen = u * total;
+    float cum = 0.0f;
+    int idx = 0;
+#pragma unroll 1
+    for (int i = 0; i < n - 1; ++i) {
+        cum = cum + w(i);
+        if (!(cum <= chosen)) break;
+        idx = i + 1;
+    }
+    return idx;
+}
+
 template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, const Env proto)
 {
     using Eng = EngineV<NC>;
     constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
     constexpr uint32_t AMASK = (1u << A) - 1u;
+    constexpr uint32_t ACT_BITS = A > 4 ? 0xffu : 3u;                 // a node's action is a byte of meta (four actions: two bits of it)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.begin1(a.pol, lds);
@@ -69,6 +103,10 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
     const uint32_t S = a.num_searches, MED = a.max_expand_depth;
     const uint64_t rec_base = e_local * (uint64_t)a.out.t_pad;
     int *pend = reinterpret_cast<int *>(lds + Eng::lds_floats(a.pol)) + j * NO;     // the ids of column j's pending state
+    // A > 4: column j's row of A floats behind the ids -- the twist average of the action head, then (owner lane, in place) the
+    // probabilities of the pending state, then at the end of a move the visit counts and the move's probabilities
+    [[maybe_unused]] float *prow = nullptr;
+    if constexpr (A > 4) prow = lds + Eng::lds_floats(a.pol) + GEN_COLS * NO + j * A;
 
     Env st = proto;                                                   // the episode's env (az.rs:56-57 / evaluate.rs:39)
     if (owner) st.reset(a.seed, solve ? sv_ep : e_global);
@@ -121,6 +159,18 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
 #pragma unroll
             for (int i = 0; i < NC; ++i) rowoff[i] = env_twist_row(eng.pol, perm, pid[i]);
             float lg[4], v;
+            if constexpr (A > 4) {
+                // the head stays in LDS (EngineV::forward_head); lane group g owns the sums of the actions g and g + 16 of its column
+                const float *head = eng.forward_head(rowoff, v);
+                if (eng.pol.n_perms > 0) vsum = vsum + v / np; else vsum = v;
+#pragma unroll 1
+                for (int i = eng.g; i < A; i += GEN_COLS) {
+                    const float x = head[env_head_unit<A>(eng.pol, perm, i) * GEN_STRIDE + j];
+                    if (eng.pol.n_perms > 0) prow[i] = (pass == 0 ? 0.0f : prow[i]) + x / np;    // policy.rs:112-114, from 0.0f in pass order
+                    else prow[i] = x;
+                }
+                __syncthreads();                                                 // (the next forward rewrites the head; the owner reads the sums)
+            } else {
             eng.forward(rowoff, lg, v);
             env_act_perm<A>(eng.pol, perm, lg);
             if (eng.pol.n_perms > 0) {
@@ -132,11 +182,26 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
 #pragma unroll
                 for (int i = 0; i < 4; ++i) lsum[i] = lg[i];
             }
+            }
         }
 
         // ---- per-episode tree work on the owner lane -------------------------------------------------------------------------
         if (owner && phase != EP_DONE) {
             float probs[4];
+            if constexpr (A > 4) {
+                // masked_softmax4 over A values, in place: tw_expf of the allowed sums, added in index order, / (sum + 1e-6f)
+                const uint32_t mb = cur.masks() & AMASK;
+                float sum = 0.0f;
+#pragma unroll 1
+                for (int i = 0; i < A; ++i) {
+                    const float p = ((mb >> i) & 1u) ? tw_expf(prow[i]) : 0.0f;
+                    prow[i] = p;
+                    sum = sum + p;
+                }
+                const float den = sum + 0.000001f;
+#pragma unroll 1
+                for (int i = 0; i < A; ++i) prow[i] = prow[i] / den;
+            } else
             masked_softmax4(lsum, cur.masks() & AMASK, probs);
             const float nn_value = vsum;
             ++evals;
@@ -146,6 +211,19 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
             auto expand = [&](uint32_t idx) -> uint32_t {
                 uint32_t cnt = 0;
                 acts = 0;
+                if constexpr (A > 4) {
+#pragma unroll 1
+                    for (int act = 0; act < A; ++act) {
+                        const float p = prow[act];
+                        if (!(p > 0.0f)) continue;
+                        EnvNode nn;
+                        nn.value_sum = 0.0f; nn.visit = 0; nn.prior = p; nn.parent = idx; nn.child_base = 0;
+                        nn.meta = 0u | ((uint32_t)act << 8);
+                        nn.pad[0] = 0; nn.pad[1] = 0;
+                        nodes[n_nodes + cnt] = nn;
+                        ++cnt;
+                    }
+                } else {
 #pragma unroll
                 for (int act = 0; act < A; ++act) {
                     if (!(probs[act] > 0.0f)) continue;
@@ -158,6 +236,7 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
                     nn.pad[0] = 0; nn.pad[1] = 0;
                     nodes[n_nodes + cnt] = nn;
                     ++cnt;
+                }
                 }
                 nodes[idx].child_base = n_nodes;
                 nodes[idx].meta = (nodes[idx].meta & ~0xffu) | cnt;
@@ -188,9 +267,16 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
                 const uint32_t nch = expand(node);
                 if (nch > 0) {
                     const u32x4 w = rng_draw(a.seed, e_global, it * MED + expanded, STREAM_MCTS | ((uint32_t)t << 8));
+                    if constexpr (A > 4) {
+                        // the priors are read back from the children just written, in child order
+                        const int k = env_sample_stream([&](int c) { return nodes[cb + (uint32_t)c].prior; }, (int)nch, u32_to_unit(w.x));
+                        node = cb + (uint32_t)k;
+                        cur.step((int)((nodes[node].meta >> 8) & ACT_BITS));
+                    } else {
                     const int k = sample_weighted4(pri, (int)nch, u32_to_unit(w.x));
                     node = cb + (uint32_t)k;
                     cur.step((int)((acts >> (2 * k)) & 3u));
+                    }
                 }
                 value = nn_value;
                 ++expanded;
@@ -203,6 +289,24 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
                         float mp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                         const EnvNode root = nodes[0];
                         const uint32_t rnc = root.meta & 0xffu;
+                        if constexpr (A > 4) {
+                            // the visit counts go into the column's row by action (the probabilities it held are used up: the root
+                            // was expanded when they arrived), are summed in index order and divided in place
+#pragma unroll 1
+                            for (int i = 0; i < A; ++i) prow[i] = 0.0f;
+#pragma unroll 1
+                            for (uint32_t c = 0; c < rnc; ++c) {
+                                const EnvNode ch = nodes[root.child_base + c];
+                                const uint32_t act = (ch.meta >> 8) & ACT_BITS;
+                                if (act < (uint32_t)A) prow[act] = (float)ch.visit;
+                            }
+                            float sum = 0.0f;
+#pragma unroll 1
+                            for (int i = 0; i < A; ++i) sum = sum + prow[i];
+                            const bool some = sum > 0.0f;
+#pragma unroll 1
+                            for (int i = 0; i < A; ++i) prow[i] = some ? prow[i] / sum : 1.0f / (float)A;
+                        } else {
                         for (uint32_t c = 0; c < rnc; ++c) {
                             const EnvNode ch = nodes[root.child_base + c];
                             const int act = (int)((ch.meta >> 8) & 3u);
@@ -220,10 +324,21 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
 #pragma unroll
                             for (int i = 0; i < A; ++i) mp[i] = 1.0f / (float)A;
                         }
+                        }
                         if (solve) {
                             // solve.rs:31-58: total += reward; action = argmax | sample of the MCTS probs; step
                             total = total + st.reward();
                             int action = 0;
+                            if constexpr (A > 4) {
+                                if (a.deterministic) {
+                                    float bv = prow[0];
+#pragma unroll 1
+                                    for (int i = 1; i < A; ++i) { const float p = prow[i]; if (p > bv) { bv = p; action = i; } }
+                                } else {
+                                    const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_SOLVE);
+                                    action = env_sample_stream([&](int i) { return prow[i]; }, A, u32_to_unit(w.x));
+                                }
+                            } else
                             if (a.deterministic) {
                                 float bv = mp[0];
 #pragma unroll
@@ -241,10 +356,17 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
                         }
                         // az.rs:72-81: action = sample(mcts_probs); val = env.reward(); store the record
                         const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_AZ_ACT);
-                        const int action = sample_weighted4(mp, A, u32_to_unit(w.x));
+                        int action;
+                        if constexpr (A > 4) action = env_sample_stream([&](int i) { return prow[i]; }, A, u32_to_unit(w.x));
+                        else action = sample_weighted4(mp, A, u32_to_unit(w.x));
                         const uint64_t rec = rec_base + (uint64_t)t;
                         const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
-                        store_rec(a.out.rec + rec, zero4, mp, 0.0f, st.reward(), 0, -1);
+                        store_rec(a.out.rec + rec, zero4, mp, 0.0f, st.reward(), 0, -1);      // (A > 4: the four slots are zero)
+                        if constexpr (A > 4) {
+                            float *row = a.pw + rec * (uint64_t)A;
+#pragma unroll 1
+                            for (int i = 0; i < A; ++i) row[i] = prow[i];
+                        }
                         {
                             // the ids of the state the move's search was rooted in (guarded when it was evaluated)
                             const int stride = env_n_obs(st);
@@ -280,6 +402,18 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
                         uint32_t best = EN_NONE; float best_ucb = -__builtin_inff();
                         EnvNode bestn = cn;
                         const float sq = sqrtf((float)cn.visit);
+                        if constexpr (A > 4) {
+#pragma unroll 1
+                            for (uint32_t c = 0; c < nch; ++c) {          // a rolled loop over the node's own children
+                                const EnvNode ch = nodes[cb + c];
+                                const float q = ch.visit == 0 ? 0.0f : ch.value_sum / (float)ch.visit;
+                                float d = sq / ((float)ch.visit + 1.0f);
+                                d = a.C * d;
+                                d = d * ch.prior;
+                                const float u = q + d;
+                                if (u > best_ucb) { best = cb + c; best_ucb = u; bestn = ch; }
+                            }
+                        } else {
                         EnvNode chs[A];
 #pragma unroll
                         for (int c = 0; c < A; ++c) chs[c] = nodes[cb + ((uint32_t)c < nch ? (uint32_t)c : nch - 1u)];
@@ -293,9 +427,10 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
                             const float u = q + d;
                             if ((uint32_t)c < nch && u > best_ucb) { best = cb + (uint32_t)c; best_ucb = u; bestn = ch; }
                         }
+                        }
                         if (best == EN_NONE) break;                   // all-NaN UCB: the reference panics here
                         node = best; cn = bestn;
-                        cur.step((int)((bestn.meta >> 8) & 3u));
+                        cur.step((int)((bestn.meta >> 8) & ACT_BITS));
                     }
                     value = 0.0f; expanded = 0;
                 }
@@ -329,7 +464,8 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
     eng.end();
 }
 
-// hipFuncSetAttribute (dynamic LDS: the engine's share, which the library passes, plus the pending ids of the 16 columns) + the launch
+// hipFuncSetAttribute (dynamic LDS: the engine's share, which the library passes, plus the pending ids of the 16 columns and, with more
+// than four actions, their rows of A floats) + the launch
 template <class Env>
 int launch_mcts_env(const EnvMctsArgs *a, const void *proto, unsigned blocks, size_t engine_lds_bytes, hipStream_t s)
 {
@@ -338,10 +474,10 @@ int launch_mcts_env(const EnvMctsArgs *a, const void *proto, unsigned blocks, si
     const uint64_t need = env_mcts_node_cap(Env::NUM_ACTIONS, a->num_searches, a->max_expand_depth);
     if (a->struct_bytes != sizeof(EnvMctsArgs) || a->node_cap < need || !a->arena || !a->eval_count || !a->err || !a->col_err ||
         (a->solve_on ? (!a->success || !a->total || !a->n_steps || a->attempts == 0 || a->max_steps == 0)
-                     : (!a->out.rec || !a->out.ep_len || !a->obs16 || a->out.t_pad < 1)) ||
+                     : (!a->out.rec || !a->out.ep_len || !a->obs16 || a->out.t_pad < 1 || (Env::NUM_ACTIONS > 4 && !a->pw))) ||
         blocks == 0 || (uint64_t)blocks * Eng::EPB < a->num_columns)
         return (int)hipErrorInvalidValue;
-    const size_t lds_bytes = engine_lds_bytes + env_mcts_pending_bytes(Env::N_OBS);
+    const size_t lds_bytes = engine_lds_bytes + env_mcts_pending_bytes(Env::N_OBS) + env_mcts_probs_bytes(Env::NUM_ACTIONS);
     Env p;
     __builtin_memcpy(&p, proto, sizeof(Env));
     const void *k = reinterpret_cast<const void *>(&mcts_env_kernel<Env, NC>);
@@ -358,7 +494,7 @@ int groups_per_cu_search_env(int kernel, size_t lds_bytes, int *out)
     constexpr int NC = env_engine_nc(Env::N_OBS);
     if (kernel != 2) return groups_per_cu_env<Env>(kernel, lds_bytes, out);
     if (!out) return (int)hipErrorInvalidValue;
-    const size_t all = lds_bytes + env_mcts_pending_bytes(Env::N_OBS);
+    const size_t all = lds_bytes + env_mcts_pending_bytes(Env::N_OBS) + env_mcts_probs_bytes(Env::NUM_ACTIONS);
     const void *k = reinterpret_cast<const void *>(&mcts_env_kernel<Env, NC>);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)all);
     if (e != hipSuccess) return (int)e;

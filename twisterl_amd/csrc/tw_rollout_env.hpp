@@ -2,7 +2,7 @@
 // environment (include/twisterl_device_env.hpp), and the argument structs a device-environment module shares with the library.
 //
 // A module (twisterl_amd.build.build_device_env) instantiates rollout_env_kernel<Env, NC> / solve_env_kernel<Env, NC> and their
-// launchers through TW_DEVICE_ENV (TW_DEVICE_ENV_SEARCH: mcts_env_kernel<Env, NC> of tw_mcts_env.hpp as well); the library (tw_device_env.hip) owns everything around them: the checks, the workspace, the scan,
+// launchers through TW_DEVICE_ENV (TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH: mcts_env_kernel<Env, NC> of tw_mcts_env.hpp as well); the library (tw_device_env.hip) owns everything around them: the checks, the workspace, the scan,
 // GAE and compaction, the error messages, the hand-off to the host-stepped path for what the kernels do not take.  Per record, in the
 // order of PPOCollector::single_collect (collector/ppo.rs:69-80): observe -> twist of the ids -> EngineV::forward -> act_perm -> mask
 // -> reward -> Gumbel arg-max over the environment's actions; store the record and the ids, then is_final / step.  Same RNG keys and
@@ -48,7 +48,7 @@ struct EnvSolveArgs {
 };
 
 // Self-play (solve_on == 0) and MCTS-guided evaluate (solve_on != 0) of mcts_env_kernel (tw_mcts_env.hpp), which a module has when it
-// was built with TW_DEVICE_ENV_SEARCH.  One column = one episode, or one attempt (episode, search) as in EnvSolveArgs.
+// was built with TW_DEVICE_ENV_SEARCH or TW_DEVICE_ENV_WIDE_SEARCH.  One column = one episode, or one attempt (episode, search) as in EnvSolveArgs.
 struct EnvMctsArgs {
     uint32_t   struct_bytes, pad0;   // sizeof(EnvMctsArgs) as the caller knows it: the launcher refuses another one (hipErrorInvalidValue)
     PolicyDev  pol;
@@ -69,6 +69,8 @@ struct EnvMctsArgs {
     uint32_t   solve_on, deterministic, attempts /* per episode */, max_steps;
     float     *success, *total;      // solve mode: [columns]
     uint32_t  *n_steps;              // solve mode: [columns]
+    float     *pw;                   // self-play of an environment of more than four actions: [E][t_pad][A] MCTS probabilities of the records,
+                                     // addressed like obs16 (the record's four logit slots are then zero and nobody reads them); else null
 };
 constexpr int ENV_MCTS_NODE_BYTES = 32;
 // the most nodes one move's tree can hold: the root, its children, and per search at most max(max_expand_depth, 1) expansions
@@ -78,6 +80,9 @@ constexpr uint64_t env_mcts_node_cap(uint32_t n_actions, uint32_t num_searches, 
 }
 // LDS of mcts_env_kernel behind the engine's: the ids of the 16 columns' pending states
 constexpr size_t env_mcts_pending_bytes(uint32_t n_obs) { return (size_t)16 * n_obs * sizeof(int); }
+// ... and behind those, for an environment of more than four actions, a row of n_actions floats per column: the twist average of the
+// action head, which the column's owner lane turns into the probabilities in place
+constexpr size_t env_mcts_probs_bytes(uint32_t n_actions) { return n_actions > 4 ? (size_t)16 * n_actions * sizeof(float) : 0; }
 
 // EngineV column count for an environment of n_obs ids: the smallest instantiation the Puzzle kernels already use
 constexpr int env_engine_nc(int n_obs) { return n_obs <= 4 ? 4 : n_obs <= 9 ? 9 : n_obs <= 16 ? 16 : n_obs <= 25 ? 25 : n_obs <= 36 ? 36 : 64; }
@@ -102,8 +107,8 @@ struct tw_device_env {
     int   (*obs_size)(const void *env);
     int   (*n_obs_of)(const void *env);                    // ids per observation of THIS object: n_obs, or the struct's own n_obs() (<= n_obs)
     void  (*fill_vtable)(tw_env_vtable *out);
-    // null unless the module was built with TW_DEVICE_ENV_SEARCH: the launcher of mcts_env_kernel (tw_mcts_env.hpp).  lds_bytes is the
-    // engine's share; the launcher adds env_mcts_pending_bytes(n_obs).  (layout[2], this struct's size, tells the two layouts apart;
+    // null unless the module was built with TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH: the launcher of mcts_env_kernel (tw_mcts_env.hpp).
+    // lds_bytes is the engine's share; the launcher adds env_mcts_pending_bytes(n_obs) + env_mcts_probs_bytes(num_actions).  (layout[2], this struct's size, tells the two layouts apart;
     // the launcher itself checks EnvMctsArgs::struct_bytes.)
     int (*launch_search)(const tw::EnvMctsArgs *a, const void *proto, unsigned blocks, size_t engine_lds_bytes, hipStream_t s);
     // how many workgroups of one of the module's kernels -- 0: rollout, 1: solve, 2: search -- a CU holds at once with lds_bytes of

@@ -238,7 +238,7 @@ class DeviceEnv:
     tw_device_env_<name>.  `params` go to the struct's init() (the environment's constructor arguments).
 
     PPOCollector.collect and evaluate run its episodes inside one kernel each (tw_ppo_collect_device_env / tw_evaluate_device_env);
-    a module built with build_device_env(..., search=True) runs AZCollector.collect and evaluate with MCTS inside one kernel too
+    a module built with build_device_env(..., search=True) (1..4 actions; wide_search=True: 1..31) runs AZCollector.collect and evaluate with MCTS inside one kernel too
     (tw_az_collect_device_env; `search` says whether the module has that kernel), any other module steps the same struct's host
     code for those (tw_az_collect_env / tw_evaluate_env), and solve always does (tw_solve_env32).  The object itself is a
     host copy of the struct with the PyBaseEnv surface (reset / step / masks / observe / reward / is_final); collectors clone
@@ -310,7 +310,7 @@ class DeviceEnv:
 
     @property
     def search(self) -> bool:
-        """The module holds the search kernel (built with search=True): self-play and MCTS-guided evaluate run on the device."""
+        """The module holds the search kernel (built with search=True or wide_search=True): self-play and MCTS-guided evaluate run on the device."""
         return bool(self._desc.launch_search)
 
     @property
