@@ -50,6 +50,8 @@ use crate::rl::env::Env;
                                     precision: u32, merge_order: u32, reserve_cus: u32 }
 #[repr(C)] pub struct TwAzParams  { num_episodes: u64, episode_offset: u64, num_mcts_searches: u32, c: f32, max_expand_depth: u32,
                                     seed: u64, precision: u32, merge_order: u32, reserve_cus: u32 }
+#[repr(C)] pub struct TwSolveParams { deterministic: u32, num_searches: u32, num_mcts_searches: u32, c: f32, max_expand_depth: u32, seed: u64,
+                                      precision: u32 }
 
 /// `trait Env` as a table of C functions (tw_env_vtable): what tw_ppo_collect_env / tw_az_collect_env call for an environment
 /// whose dynamics the kernels do not implement (GridWorld-style crates, examples/grid_world/src/lib.rs:84-164).
@@ -95,6 +97,11 @@ extern "C" {
     fn tw_az_collect(env: *const TwPuzzleDesc, policy: *const c_void, prm: *const TwAzParams, out: *mut *mut c_void) -> c_int;
     fn tw_ppo_collect_env(env: *const TwEnvVtable, policy: *const c_void, prm: *const TwPpoParams, max_records: u32, out: *mut *mut c_void) -> c_int;
     fn tw_az_collect_env(env: *const TwEnvVtable, policy: *const c_void, prm: *const TwAzParams, max_records: u32, out: *mut *mut c_void) -> c_int;
+    // a device environment (a module of twisterl_amd.build.build_device_env: `env` = its descriptor, `proto` = the struct in its current
+    // state, not modified): solve() in one kernel launch -- best of prm.num_searches attempts, the played actions of the best one
+    #[allow(dead_code)] fn tw_solve_device_env(env: *const c_void, proto: *const c_void, proto_bytes: usize, policy: *const c_void, prm: *const TwSolveParams,
+                                               max_steps: u32, success: *mut f32, reward: *mut f32, solution_out: *mut u32, solution_cap: u32,
+                                               n_solution: *mut u32) -> c_int;
     fn tw_collected_num_records(c: *const c_void) -> u64;
     fn tw_collected_num_cells(c: *const c_void) -> u32;
     fn tw_collected_num_actions(c: *const c_void) -> u32;

@@ -40,6 +40,9 @@
 // More episodes than the GPU holds columns at once (the module's own occupancy x the compute units x 16): the PPO collect and the plain
 // evaluate run on a persistent grid whose columns take the next episode from a device-side queue -- reset() is then called again on a
 // fresh clone of the prototype, from the same single place in the kernel; the bytes are those of one column per episode.
+// solve (collector.solve / tw_solve_device_env: best of N attempts from the object's CURRENT state, the played actions back) is one launch
+// of the evaluate kernel -- of the search kernel with num_mcts_searches > 0 -- that skips reset(): every attempt starts from a copy of the
+// struct as the caller holds it, which is not modified.  Nothing is asked of the struct for it beyond the methods above.
 // A struct that holds instances of several sizes may add `int n_obs() const`, 1..N_OBS and CONSTANT for the object's lifetime (the
 // library reads it once, from the prototype): observe() then writes that many ids.
 // Observations of VARIABLE length (the reference's Env::observe returns a Vec of any length and its EmbeddingBag adds however many
@@ -88,7 +91,7 @@ struct DeviceEnvModule {
     static_assert(VAR_OBS || EnvHasObserve<T>::value, "twisterl device environment: the struct needs `void observe(int *ids) const`, or `int observe_n(int *ids) const` for observations of variable length");
     static constexpr int A = T::NUM_ACTIONS, NO = T::N_OBS;
 
-    // tw_env_vtable over T (the host-stepped collectors and solve run the same code on the CPU)
+    // tw_env_vtable over T (the host-stepped collectors, and solve for what the kernels do not take, run the same code on the CPU)
     static void *clone(void *e) { return new (std::nothrow) T(*static_cast<const T *>(e)); }
     static void destroy(void *e) { delete static_cast<T *>(e); }
     static void reset(void *e, uint64_t seed, uint64_t episode) { static_cast<T *>(e)->reset(seed, episode); }

@@ -359,7 +359,7 @@ int tw_solve_env32(const tw_env_vtable *env, const tw_policy *policy, const tw_s
 /* ---- a user-written environment ON THE DEVICE: a C++ struct (include/twisterl_device_env.hpp) compiled into a module
  * (twisterl_amd.build.build_device_env) that exports `const tw_device_env *tw_device_env_<name>(void)`.  `proto` points to the
  * environment struct (proto_bytes = its size), the prototype every episode clones and resets.  The library refuses a descriptor
- * built against another layout.  tw_ppo_collect_device_env / tw_evaluate_device_env run the whole loop in one kernel (the policy on
+ * built against another layout.  tw_ppo_collect_device_env / tw_evaluate_device_env / tw_solve_device_env run the whole loop in one kernel (the policy on
  * EngineV, f32); what that kernel does not take -- a policy of the MFMA shape, another precision -- runs on the host-stepped path over
  * the module's own vtable (tw_ppo_collect_env / tw_az_collect_env / tw_evaluate_env: same bytes, same errors).  Self-play
  * (tw_az_collect_device_env) and evaluate with num_mcts_searches > 0 run in one kernel too when the module was built with
@@ -375,6 +375,13 @@ int tw_az_collect_device_env(const tw_device_env *env, const void *proto, size_t
 int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
                            const tw_solve_params *params, uint64_t num_episodes, uint64_t episode_offset, uint32_t max_steps,
                            float *success_rate, float *mean_reward);
+/* solve() of a device environment: the contract of tw_solve_env32 over the module's host vtable -- best of params.num_searches
+ * attempts from `proto` AS IT IS (its current state; it is not modified), the played actions of the best one as 32-bit entries --
+ * in ONE launch of the evaluate kernel (num_mcts_searches > 0: of the search kernel), byte-equal to that call, which is also where
+ * everything the kernels do not take goes (as for tw_evaluate_device_env; besides, action rows num_searches x max_steps above 1 GiB). */
+int tw_solve_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                        const tw_solve_params *params, uint32_t max_steps, float *success, float *reward,
+                        uint32_t *solution_out, uint32_t solution_cap, uint32_t *n_solution);
 
 /* Fields of the result (device-resident, compact, in the order params.merge_order asked for) */
 enum {

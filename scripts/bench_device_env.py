@@ -22,6 +22,12 @@ and its collect is host-stepped.  profiles/r08_device_env_search.jsonl holds the
 Permutation8 with the policy of --env perm8 (a module built with wide_search=True; a tree from before the wide search builds it with
 wide=True and its collect is host-stepped): profiles/r12_device_env_wide_search.jsonl.
 
+--solve: collector.solve (best of N sampled attempts from the environment's CURRENT state, the action list back) of GridWorld 5 x 5 and
+Permutation8, plain and with --solve-mcts searches per move, at --solve-searches 1,64,1024 attempts: the call as the tree runs it (one
+kernel launch since tw_solve_device_env; host-stepped on a --tree from before it) and tw_solve_env32 over the module's host vtable, the
+two results compared in the same run; wall clock of whole calls, median / min / max of --reps after --warmup, rows APPENDED to --out.
+profiles/r13_device_env_solve.jsonl.
+
 --no-persist: TW_OPT_NO_PERSIST = 1 for the whole run -- one workgroup per 16 episodes whatever their number, instead of the persistent
 grid with its episode queue that a collect of more episodes than the chip holds columns gets by itself.  Every device row says which
 of the two ran ("persist") and the grid ("blocks").  --skip-host leaves the host-stepped rows (and the byte comparison with them) out:
@@ -109,8 +115,96 @@ def az(args):
             f.write(json.dumps(row) + "\n")
 
 
+def solve(args):
+    """collector.solve of GridWorld 5 x 5 and Permutation8 from a state one step behind a reset, plain and with MCTS (--solve-mcts searches
+    per move, expansion depth 1), best of 1 / 64 / 1024 sampled attempts: the call as this tree runs it ("device" when the library reports
+    a kernel of the module, else "host_stepped") against tw_solve_env32 over the module's host vtable, whose result must be the same."""
+    import inspect
+    import numpy as np
+    import twisterl_amd
+    from twisterl_amd import _lib, twisterl
+    from twisterl_amd.build import build_device_env
+    from twisterl_amd.env import DeviceEnv
+    from tests.device_env_util import GRIDWORLD_HPP
+    from tests.util import amd_policy, make_deep_policy_arrays, make_deep_policy_arrays_obs
+    if twisterl_amd.device_count() < 1:
+        raise SystemExit("no GPU")
+    if args.no_persist:
+        _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
+    params = inspect.signature(build_device_env).parameters
+    perm_hpp = os.path.join(ROOT, "examples", "device_env", "permutation.hpp")
+    grid_pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
+    perm_pol = amd_policy(make_deep_policy_arrays_obs(64, seed=0, emb=512, common=(128, 64), n_actions=28))
+
+    def grid(search):
+        name = "gridworld5x5_az" if search else "gridworld5x5"
+        so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if search else {}))
+        return DeviceEnv(so, name, [5, 5, 64, 8], max_records=65)
+
+    def perm(search):
+        name = "perm8_az" if search else "perm8"
+        so = build_device_env(perm_hpp, "tw_examples::Permutation8", name, **({"wide_search": True} if search else {"wide": True}))
+        return DeviceEnv(so, name, [8, 32, 4], max_records=33)
+
+    S = args.solve_mcts
+    shapes = [("GridWorld5x5", "625-512-128+heads (generic)", grid, grid_pol, 0), ("GridWorld5x5", "625-512-128+heads (generic)", grid, grid_pol, S),
+              ("Permutation8 (28 actions)", "64-512-128-64+heads (generic)", perm, perm_pol, 0),
+              ("Permutation8 (28 actions)", "64-512-128-64+heads (generic)", perm, perm_pol, S)]
+    info = twisterl_amd.device_info()
+    rows = []
+    for env_name, pol_name, make, pol, mcts in shapes:
+        if mcts and ("wide_search" not in params or "search" not in params):
+            continue
+        env = make(mcts > 0)
+        env.reset(seed=3, episode=5)
+        env.step(next(i for i, m in enumerate(env.masks()) if m))       # the current state is no reset state
+        vt = _lib.EnvVTable()
+        _lib.check(_lib.lib().tw_device_env_host_vtable(*env._args(), C.byref(vt)))
+
+        def call(N, seed):
+            return twisterl.collector.solve(env, pol, False, N, mcts, 1.41, 1, seed=seed)
+
+        def host(N, seed):
+            prm = _lib.SolveParams(0, N, mcts, 1.41, 1, seed, _lib.TW_PREC_F32_EXACT)
+            cap = env.max_records + 1
+            acts = (C.c_uint32 * cap)()
+            s, r, n = C.c_float(), C.c_float(), C.c_uint32()
+            _lib.check(_lib.lib().tw_solve_env32(C.byref(vt), pol._handle(), C.byref(prm), env.max_records, C.byref(s), C.byref(r), acts, cap, C.byref(n)))
+            return (float(s.value), float(r.value)), [int(acts[i]) for i in range(n.value)]
+
+        for N in [int(x) for x in args.solve_searches.split(",")]:
+            a, b = call(N, 1), host(N, 1)
+            same = a[0][0] == b[0][0] and np.float32(a[0][1]).tobytes() == np.float32(b[0][1]).tobytes() and a[1] == b[1]
+            assert same, f"solve() and the host-stepped path differ: {a} {b}"
+            last = _lib.debug_last_launch()
+            on_device = last["family"] in (_lib.TW_KERNEL_SOLVE_BIG, _lib.TW_KERNEL_MCTS_BIG)
+            for path, fn in ((("device" if on_device else "host_stepped"), call),) + ((("host_stepped", host),) if on_device and not args.skip_host else ()):
+                for i in range(args.warmup):
+                    fn(N, 100 + i)
+                ts = []
+                for i in range(args.reps):
+                    t0 = time.perf_counter()
+                    fn(N, 1000 + i)
+                    ts.append(time.perf_counter() - t0)
+                ts_ms = sorted(t * 1e3 for t in ts)
+                row = {"bench": "solve", "env": env_name, "policy": pol_name, "path": path, "entry": "collector.solve" if fn is call else "tw_solve_env32",
+                       "num_searches": N, "num_mcts_searches": mcts, "max_expand_depth": 1, "deterministic": False, "same_result_as_host_stepped": same,
+                       "wall_ms": round(ts_ms[len(ts_ms) // 2], 3), "wall_ms_min": round(ts_ms[0], 3), "wall_ms_max": round(ts_ms[-1], 3),
+                       "wall_ms_all": [round(t * 1e3, 3) for t in ts], "reps": args.reps,
+                       "persist": last["persist"] if fn is call and on_device else None, "blocks": last["blocks"] if fn is call and on_device else None,
+                       "tree": os.path.basename(ROOT) if args.tree else "this", "device": info["name"]}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--solve", action="store_true", help="collector.solve from the current state against the host-stepped path; appends rows to --out")
+    ap.add_argument("--solve-searches", default="1,64,1024", help="num_searches of --solve")
+    ap.add_argument("--solve-mcts", type=int, default=8, help="num_mcts_searches of the MCTS shapes of --solve")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--episodes", default="1024,65536")
@@ -124,6 +218,8 @@ def main():
     args = ap.parse_args()
     if args.az:
         return az(args)
+    if args.solve:
+        return solve(args)
     import numpy as np
     import twisterl_amd
     from twisterl_amd import _lib, twisterl

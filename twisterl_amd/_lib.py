@@ -169,7 +169,9 @@ SYMBOLS = {
     "tw_az_collect_device_env": (C.c_int, [_VP, _VP, C.c_size_t, _VP, C.POINTER(AZParams), C.c_uint32, C.POINTER(_VP)]),
     "tw_evaluate_device_env": (C.c_int, [_VP, _VP, C.c_size_t, _VP, C.POINTER(SolveParams), C.c_uint64, C.c_uint64, C.c_uint32,
                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    "tw_evaluate": (C.c_int, [C.POINTER(PuzzleDesc), _VP, C.POINTER(SolveParams), C.c_uint64, C.c_uint64,
+    "tw_solve_device_env": (C.c_int, [_VP, _VP, C.c_size_t, _VP, C.POINTER(SolveParams), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "tw_evaluate":(C.c_int, [C.POINTER(PuzzleDesc), _VP, C.POINTER(SolveParams), C.c_uint64, C.c_uint64,
                               C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tw_solve": (C.c_int, [_VP, _VP, C.POINTER(SolveParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
                            C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),

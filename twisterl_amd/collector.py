@@ -602,14 +602,12 @@ def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches
         s, r, n = _c.c_float(), _c.c_float(), _c.c_uint32()
         br.finish(_lib.lib().tw_solve_env32(_c.byref(br.vt), policy._handle(), _c.byref(prm), br.max_records, _c.byref(s), _c.byref(r), acts, cap, _c.byref(n)))
         return (float(s.value), float(r.value)), [int(acts[i]) for i in range(n.value)]
-    if isinstance(py_env, DeviceEnv):                                           # the struct's host code (solve.rs:73-101)
-        vt = _lib.EnvVTable()
-        _lib.check(_lib.lib().tw_device_env_host_vtable(*py_env._args(), _c.byref(vt)))
+    if isinstance(py_env, DeviceEnv):                                           # one kernel (tw_solve_device_env; MCTS: a search module)
         cap = py_env.max_records + 1
         acts = (_c.c_uint32 * cap)()
         s, r, n = _c.c_float(), _c.c_float(), _c.c_uint32()
-        _lib.check(_lib.lib().tw_solve_env32(_c.byref(vt), policy._handle(), _c.byref(prm), py_env.max_records, _c.byref(s), _c.byref(r), acts, cap,
-                                             _c.byref(n)))
+        _lib.check(_lib.lib().tw_solve_device_env(*py_env._args(), policy._handle(), _c.byref(prm), py_env.max_records, _c.byref(s), _c.byref(r), acts,
+                                                  cap, _c.byref(n)))
         return (float(s.value), float(r.value)), [int(acts[i]) for i in range(n.value)]
     get_env_desc(py_env)
     cap = int(py_env.depth) + 2

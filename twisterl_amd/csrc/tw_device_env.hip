@@ -4,12 +4,13 @@
 // solve_env_kernel of tw_rollout_env.hpp instantiated over the user's struct -- their launchers and a host adapter.  Everything
 // else is here: the checks, the workspace, the scan / GAE / compaction of the Puzzle path (tw_finalize.hip), the error messages.
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
-// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error), solve
-// (the Python layer routes it), and -- for a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has
-// no search launcher -- self-play and evaluate with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
+// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error), and -- for
+// a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has no search launcher -- self-play,
+// evaluate and solve with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
 // 1..4 actions and (TW_DEVICE_ENV_WIDE_SEARCH) for 5..31, which lives in the module
-// alone: tw_az_collect_device_env, and tw_evaluate_device_env with num_mcts_searches > 0.  The result is an ordinary tw_collected,
-// byte-equal to tw_ppo_collect_env / tw_az_collect_env over the same vtable.
+// alone: tw_az_collect_device_env, and tw_evaluate_device_env / tw_solve_device_env with num_mcts_searches > 0.  The result is an
+// ordinary tw_collected, byte-equal to tw_ppo_collect_env / tw_az_collect_env over the same vtable.  solve (tw_solve_device_env) is
+// evaluate's body started from the prototype as it is, with the played moves kept: attempts_device_env below.
 #include "tw_rollout_env.hpp"
 
 #include <cstring>
@@ -489,22 +490,35 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     return TW_OK;
 }
 
-extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
-                                      const tw_solve_params *prm, uint64_t num_episodes, uint64_t episode_offset, uint32_t max_steps,
-                                      float *success_rate, float *mean_reward)
+namespace {
+
+// the most bytes of action rows (attempts x max_steps) a solve keeps on the device; a longer bound goes to the host-stepped path
+constexpr uint64_t SOLVE_ACTION_BYTES_MAX = 1ull << 30;
+
+// What solve_env_kernel / mcts_env_kernel take of an evaluate or a solve; everything else is the host-stepped path's (the callers
+// hand over to it).  node_cap: the search's tree size, for attempts_device_env.
+bool attempts_on_device(const tw_device_env *env, const PolicyDev *pd, const tw_solve_params *prm, uint64_t num_episodes, uint32_t max_steps,
+                        uint64_t *node_cap)
 {
-    if (!policy || !prm || !success_rate || !mean_reward) { set_error("tw_evaluate_device_env: null argument"); return TW_ERR_INVALID; }
-    int rc = check_descriptor(env, proto, proto_bytes, "tw_evaluate_device_env"); if (rc) return rc;
-    note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);
-    const tw_env_vtable vt = host_table(env, proto);
-    const PolicyDev *pd = policy_dev(policy);
     const bool mcts = prm->num_mcts_searches != 0;
-    uint64_t node_cap = 0;
-    if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_searches == 0 || num_episodes == 0 || max_steps > 0x7fffffffu ||
-        (mcts && (!env->launch_search || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, &node_cap))))
-        return tw_evaluate_env(&vt, policy, prm, num_episodes, episode_offset, max_steps, success_rate, mean_reward);
-    rc = check_env_policy(vt, pd); if (rc) return rc;
-    if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("tw_evaluate_device_env: policy without its two-byte twist table"); return TW_ERR_INVALID; }
+    *node_cap = 0;
+    return !(!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_searches == 0 || num_episodes == 0 || max_steps > 0x7fffffffu ||
+             (mcts && (!env->launch_search || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, node_cap))));
+}
+
+// The attempts of evaluate (from_state == false: episode e of num_episodes starts from reset(seed, episode_offset + e)) and of solve
+// (from_state: ONE episode, every attempt starts from the prototype as it is) in one launch of solve_env_kernel or, with
+// num_mcts_searches > 0, of mcts_env_kernel in solve mode: checks, grid, workspace, launch, the errors of the host-stepped path, and
+// run_attempts_env's reduction -- per episode the first attempt whose (success, total) is strictly better (solve.rs:84-98).
+// best_actions (solve; else null): the moves of that attempt, the only row that is copied back.
+int attempts_device_env(const char *who, const tw_device_env *env, const void *proto, const tw_env_vtable &vt, const PolicyDev *pd,
+                        const tw_solve_params *prm, uint64_t num_episodes, uint64_t episode_offset, bool from_state, uint32_t max_steps_in,
+                        uint64_t node_cap, std::vector<float> &best_s, std::vector<float> &best_r, std::vector<uint32_t> *best_actions)
+{
+    const bool mcts = prm->num_mcts_searches != 0;
+    const uint32_t max_steps = max_steps_in ? max_steps_in : 1u;
+    int rc = check_env_policy(vt, pd); if (rc) return rc;
+    if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("%s: policy without its two-byte twist table", who); return TW_ERR_INVALID; }
     rc = require_device(); if (rc) return rc;
     const uint64_t N = prm->num_searches, NA = num_episodes * N;
     if (NA / N != num_episodes) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
@@ -518,82 +532,70 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     if (!mcts) { rc = env_grid(env, 1, lds_bytes, NA, 0, &grid); if (rc) return rc; }
     const uint64_t blocks = grid.blocks;
     if (blocks > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
+    // the played moves: one row of max_steps bytes per attempt (an attempt that ends has played at most max_steps)
+    const uint32_t stride = best_actions ? max_steps : 0u;
 
     std::vector<float> succ(NA), tot(NA);
-    std::vector<uint32_t> steps(NA);
+    std::vector<uint32_t> steps(NA), ce;
     uint64_t hv[2] = {0, 0};
+    std::lock_guard<std::mutex> lock(workspace_mutex());                  // (to the end: the best attempt's row is read from the workspace)
+    hipStream_t s = current_stream();
+    size_t cur = 0;
+    auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
+    const size_t o_s = seg(NA * 4), o_t = seg(NA * 4), o_n = seg(NA * 4), o_err = seg(32), o_ce = seg(mcts ? NA * 16 : 0),
+                 o_arena = seg(mcts ? (size_t)NA * node_cap * ENV_MCTS_NODE_BYTES : 0), o_act = seg((size_t)NA * stride);
+    if (mcts) { rc = check_memory_fit(cur, who); if (rc) return rc; }
+    void *wsp = nullptr;
+    rc = workspace_reserve(cur, &wsp); if (rc) return rc;
+    uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
+    uint8_t *act_d = stride ? ws + o_act : nullptr;
+    TW_HIP(hipMemsetAsync(ws + o_err, 0, 32, s));                         // (o_err: err | the queue's counter or the evaluation count)
     if (mcts) {
-        // MCTS-guided attempts (solve.rs:41-47): mcts_env_kernel in solve mode, one column = one attempt; the reduction below is shared
-        std::vector<uint32_t> ce;
-        {
-            std::lock_guard<std::mutex> lock(workspace_mutex());
-            hipStream_t s = current_stream();
-            size_t cur = 0;
-            auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
-            const size_t o_s = seg(NA * 4), o_t = seg(NA * 4), o_n = seg(NA * 4), o_err = seg(32), o_ce = seg(NA * 16),
-                         o_arena = seg((size_t)NA * node_cap * ENV_MCTS_NODE_BYTES);
-            rc = check_memory_fit(cur, "tw_evaluate_device_env"); if (rc) return rc;
-            void *wsp = nullptr;
-            rc = workspace_reserve(cur, &wsp); if (rc) return rc;
-            uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
-            EnvMctsArgs ma{};
-            ma.struct_bytes = (uint32_t)sizeof(EnvMctsArgs);
-            ma.pol = *pd; ma.num_columns = NA; ma.episode_offset = episode_offset; ma.seed = prm->seed;
-            ma.num_searches = prm->num_mcts_searches; ma.max_expand_depth = prm->max_expand_depth; ma.C = prm->C; ma.node_cap = (uint32_t)node_cap;
-            ma.arena = ws + o_arena; ma.err = reinterpret_cast<uint32_t *>(ws + o_err); ma.eval_count = reinterpret_cast<unsigned long long *>(ws + o_err + 8);
-            ma.col_err = reinterpret_cast<uint32_t *>(ws + o_ce);
-            ma.solve_on = 1u; ma.deterministic = prm->deterministic ? 1u : 0u; ma.attempts = (uint32_t)N; ma.max_steps = max_steps ? max_steps : 1u;
-            ma.success = reinterpret_cast<float *>(ws + o_s); ma.total = reinterpret_cast<float *>(ws + o_t); ma.n_steps = reinterpret_cast<uint32_t *>(ws + o_n);
-            TW_HIP(hipMemsetAsync(ws + o_err, 0, 32, s));
-            TW_HIP(hipMemsetAsync(ws + o_ce, 0, NA * 16, s));
-            const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
-            if (lr == (int)hipErrorInvalidValue) return search_launch_refused("tw_evaluate_device_env");
-            if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
-            note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, true, false, false, (uint32_t)blocks, 256);
-            TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
-            TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
-            TW_HIP(hipMemcpyAsync(steps.data(), ws + o_n, NA * 4, hipMemcpyDeviceToHost, s));
-            TW_HIP(hipMemcpyAsync(hv, ws + o_err, 8, hipMemcpyDeviceToHost, s));
-            TW_HIP(hipStreamSynchronize(s));
-            if ((uint32_t)hv[0] & 13u) {
-                ce.resize(NA * 4);
-                TW_HIP(hipMemcpy(ce.data(), ws + o_ce, NA * 16, hipMemcpyDeviceToHost));
-            }
-        }
-        if ((uint32_t)hv[0] & 13u) {
-            if (!first_search_error(ce, NA, vt.n_obs, pd->obs_size)) set_error("solve: an attempt did not end within %u steps", max_steps ? max_steps : 1u);
-            return TW_ERR_INVALID;
-        }
+        // MCTS-guided attempts (solve.rs:41-47): mcts_env_kernel in solve mode, one column = one attempt
+        EnvMctsArgs ma{};
+        ma.struct_bytes = (uint32_t)sizeof(EnvMctsArgs);
+        ma.pol = *pd; ma.num_columns = NA; ma.episode_offset = episode_offset; ma.seed = prm->seed;
+        ma.num_searches = prm->num_mcts_searches; ma.max_expand_depth = prm->max_expand_depth; ma.C = prm->C; ma.node_cap = (uint32_t)node_cap;
+        ma.arena = ws + o_arena; ma.err = reinterpret_cast<uint32_t *>(ws + o_err); ma.eval_count = reinterpret_cast<unsigned long long *>(ws + o_err + 8);
+        ma.col_err = reinterpret_cast<uint32_t *>(ws + o_ce);
+        ma.solve_on = 1u; ma.deterministic = prm->deterministic ? 1u : 0u; ma.attempts = (uint32_t)N; ma.max_steps = max_steps;
+        ma.success = reinterpret_cast<float *>(ws + o_s); ma.total = reinterpret_cast<float *>(ws + o_t); ma.n_steps = reinterpret_cast<uint32_t *>(ws + o_n);
+        ma.from_state = from_state ? 1u : 0u; ma.actions = act_d; ma.actions_stride = stride;
+        TW_HIP(hipMemsetAsync(ws + o_ce, 0, NA * 16, s));
+        const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
+        if (lr == (int)hipErrorInvalidValue) return search_launch_refused(who);
+        if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
+        note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, true, false, false, (uint32_t)blocks, 256);
     } else {
-        std::lock_guard<std::mutex> lock(workspace_mutex());
-        hipStream_t s = current_stream();
-        size_t cur = 0;
-        auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
-        const size_t o_s = seg(NA * 4), o_t = seg(NA * 4), o_n = seg(NA * 4), o_err = seg(16);
-        void *wsp = nullptr;
-        rc = workspace_reserve(cur, &wsp); if (rc) return rc;
-        uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
         EnvSolveArgs sa{};
         sa.pol = *pd; sa.num_attempts = NA; sa.episode_offset = episode_offset; sa.seed = prm->seed;
-        sa.num_searches = (uint32_t)N; sa.deterministic = prm->deterministic ? 1u : 0u; sa.max_steps = max_steps ? max_steps : 1u;
+        sa.num_searches = (uint32_t)N; sa.deterministic = prm->deterministic ? 1u : 0u; sa.max_steps = max_steps;
         sa.success = reinterpret_cast<float *>(ws + o_s); sa.total = reinterpret_cast<float *>(ws + o_t);
         sa.n_steps = reinterpret_cast<uint32_t *>(ws + o_n); sa.err = reinterpret_cast<uint32_t *>(ws + o_err);
-        TW_HIP(hipMemsetAsync(ws + o_err, 0, 16, s));
-        if (grid.persist) {                                               // (o_err: err | the queue's counter)
+        sa.from_state = from_state ? 1u : 0u; sa.actions = act_d; sa.actions_stride = stride;
+        if (grid.persist) {
             sa.queue = reinterpret_cast<unsigned int *>(ws + o_err + 8);
             const unsigned int first = (unsigned int)(blocks * GEN_COLS);
             TW_HIP(hipMemcpyAsync(sa.queue, &first, 4, hipMemcpyHostToDevice, s));
         }
         const int lr = env->launch_solve(&sa, proto, (unsigned)blocks, lds_bytes, s);
         if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment evaluate launch", __FILE__, __LINE__);
-        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, 0, 0, grid.persist, false, false, false, (uint32_t)blocks, 256);
-        TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
-        TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
-        TW_HIP(hipMemcpyAsync(steps.data(), ws + o_n, NA * 4, hipMemcpyDeviceToHost, s));
-        TW_HIP(hipMemcpyAsync(hv, ws + o_err, 8, hipMemcpyDeviceToHost, s));
-        TW_HIP(hipStreamSynchronize(s));
+        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, 0, 0, grid.persist, from_state, false, false, (uint32_t)blocks, 256);
     }
+    TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
+    TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
+    TW_HIP(hipMemcpyAsync(steps.data(), ws + o_n, NA * 4, hipMemcpyDeviceToHost, s));
+    TW_HIP(hipMemcpyAsync(hv, ws + o_err, 8, hipMemcpyDeviceToHost, s));
+    TW_HIP(hipStreamSynchronize(s));
     const uint32_t err = (uint32_t)hv[0];
+    if (mcts) {
+        if (err & 13u) {
+            ce.resize(NA * 4);
+            TW_HIP(hipMemcpy(ce.data(), ws + o_ce, NA * 16, hipMemcpyDeviceToHost));
+            if (!first_search_error(ce, NA, vt.n_obs, pd->obs_size)) set_error("solve: an attempt did not end within %u steps", max_steps);
+            return TW_ERR_INVALID;
+        }
+    }
     note_attempts(succ.data(), tot.data(), steps.data(), NA);      // (tw_debug_last_attempts)
     if (err & 9u) {       // the first bad id (or count of observe_n) the host path meets: the smallest move, then the smallest attempt
                           // (its total holds the id / the count; a count: its success is 2.0f)
@@ -605,19 +607,78 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
         else set_error("index out of bounds: obs id %d, obs_size %d", (int)id, pd->obs_size);
         return TW_ERR_INVALID;
     }
-    if (err & 4u) { set_error("solve: an attempt did not end within %u steps", max_steps ? max_steps : 1u); return TW_ERR_INVALID; }
-    // best of N per episode (solve.rs:84-98: `if next_val.0 > best.0` on (success, total) tuples), then the means in episode order
-    // (evaluate.rs:36-52) -- tw_evaluate_env's reduction
-    float successes = 0.0f, rewards = 0.0f;
+    if (err & 4u) { set_error("solve: an attempt did not end within %u steps", max_steps); return TW_ERR_INVALID; }
+    // best of N per episode (solve.rs:84-98: `if next_val.0 > best.0` on (success, total) tuples) -- run_attempts_env's reduction
+    best_s.assign(num_episodes, 0.0f); best_r.assign(num_episodes, -__builtin_inff());
+    uint64_t best_att = (uint64_t)-1;                                    // (of the last episode: solve has one)
     for (uint64_t ep = 0; ep < num_episodes; ++ep) {
-        float bs = 0.0f, br = -__builtin_inff();
+        best_att = (uint64_t)-1;
         for (uint64_t k = 0; k < N; ++k) {
             const float sc = succ[ep * N + k], tr = tot[ep * N + k];
-            if (sc > bs || (sc == bs && tr > br)) { bs = sc; br = tr; }
+            if (sc > best_s[ep] || (sc == best_s[ep] && tr > best_r[ep])) { best_s[ep] = sc; best_r[ep] = tr; best_att = ep * N + k; }
         }
-        successes = successes + bs; rewards = rewards + br;
     }
+    if (best_actions) {
+        best_actions->clear();
+        if (num_episodes == 1 && best_att != (uint64_t)-1) {
+            const uint32_t n = steps[best_att] < stride ? steps[best_att] : stride;
+            std::vector<uint8_t> row(n);
+            if (n) { TW_HIP(hipMemcpy(row.data(), act_d + best_att * (uint64_t)stride, n, hipMemcpyDeviceToHost)); }
+            best_actions->assign(row.begin(), row.end());                 // widened to the 32-bit entries of tw_solve_env32
+        }
+    }
+    return TW_OK;
+}
+
+}  // namespace
+
+extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                                      const tw_solve_params *prm, uint64_t num_episodes, uint64_t episode_offset, uint32_t max_steps,
+                                      float *success_rate, float *mean_reward)
+{
+    if (!policy || !prm || !success_rate || !mean_reward) { set_error("tw_evaluate_device_env: null argument"); return TW_ERR_INVALID; }
+    int rc = check_descriptor(env, proto, proto_bytes, "tw_evaluate_device_env"); if (rc) return rc;
+    note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);
+    const tw_env_vtable vt = host_table(env, proto);
+    const PolicyDev *pd = policy_dev(policy);
+    uint64_t node_cap = 0;
+    if (!attempts_on_device(env, pd, prm, num_episodes, max_steps, &node_cap))
+        return tw_evaluate_env(&vt, policy, prm, num_episodes, episode_offset, max_steps, success_rate, mean_reward);
+    std::vector<float> bs, br;
+    rc = attempts_device_env("tw_evaluate_device_env", env, proto, vt, pd, prm, num_episodes, episode_offset, false, max_steps, node_cap, bs, br, nullptr);
+    if (rc) return rc;
+    // the means in episode order (evaluate.rs:36-52) -- tw_evaluate_env's reduction
+    float successes = 0.0f, rewards = 0.0f;
+    for (uint64_t ep = 0; ep < num_episodes; ++ep) { successes = successes + bs[ep]; rewards = rewards + br[ep]; }
     *success_rate = successes / (float)num_episodes;
     *mean_reward = rewards / (float)num_episodes;
     return TW_OK;
 }
+
+// solve() (solve.rs:73-101) of a device environment: best of num_searches attempts from the prototype AS IT IS, in one launch; the
+// contract and the bytes of tw_solve_env32 over the module's host vtable, which is also where everything the kernels do not take goes
+extern "C" int tw_solve_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
+                                   const tw_solve_params *prm, uint32_t max_steps, float *success, float *reward,
+                                   uint32_t *solution_out, uint32_t solution_cap, uint32_t *n_solution)
+{
+    if (!policy || !prm || !success || !reward) { set_error("tw_solve_device_env: null argument"); return TW_ERR_INVALID; }
+    int rc = check_descriptor(env, proto, proto_bytes, "tw_solve_device_env"); if (rc) return rc;
+    note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);
+    const tw_env_vtable vt = host_table(env, proto);
+    const PolicyDev *pd = policy_dev(policy);
+    uint64_t node_cap = 0;
+    if (!attempts_on_device(env, pd, prm, 1, max_steps, &node_cap) ||
+        (uint64_t)prm->num_searches * (uint64_t)(max_steps ? max_steps : 1u) > SOLVE_ACTION_BYTES_MAX)
+        return tw_solve_env32(&vt, policy, prm, max_steps, success, reward, solution_out, solution_cap, n_solution);
+    std::vector<float> bs, br; std::vector<uint32_t> acts;
+    rc = attempts_device_env("tw_solve_device_env", env, proto, vt, pd, prm, 1, 0, true, max_steps, node_cap, bs, br, &acts);
+    if (rc) return rc;
+    *success = bs[0]; *reward = br[0];
+    if (n_solution) *n_solution = (uint32_t)acts.size();
+    if (solution_out) {
+        if (acts.size() > solution_cap) { set_error("tw_solve_env: %zu entries, caller's buffer holds %u", acts.size(), solution_cap); return TW_ERR_INVALID; }
+        if (!acts.empty()) memcpy(solution_out, acts.data(), acts.size() * sizeof(uint32_t));
+    }
+    return TW_OK;
+}
+

@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
     if constexpr (A > 4) prow = lds + Eng::lds_floats(a.pol) + GEN_COLS * NO + j * A;
 
     Env st = proto;                                                   // the episode's env (az.rs:56-57 / evaluate.rs:39)
-    if (owner) st.reset(a.seed, solve ? sv_ep : e_global);
+    if (owner && !a.from_state) st.reset(a.seed, solve ? sv_ep : e_global);       // (from_state: the prototype as it is, solve.rs:85)
     Env cur = st;                                                     // the state of `node`: the one whose evaluation is pending
     int      phase = owner ? EP_ROOT : EP_DONE;
     if (solve && owner && st.is_final()) phase = EP_DONE;             // `while !env.is_final()` (solve.rs:30)
@@ -347,6 +347,9 @@ __global__ void __launch_bounds__(256, 1) mcts_env_kernel(const EnvMctsArgs a, c
                                 const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_SOLVE);
                                 action = sample_weighted4(mp, A, u32_to_unit(w.x));
                             }
+                            // solve.rs:56-59: the move, into the column's own row (owner: e_local < num_columns), and the step.  A 32-bit
+                            // index: the launcher refuses rows beyond 4 GiB, and EngineV<64> has no register to spare for a wider one
+                            if (a.actions != nullptr && (uint32_t)t < a.actions_stride) a.actions[(uint32_t)e_local * a.actions_stride + (uint32_t)t] = (uint8_t)action;
                             st.step(action);
                             ++t;
                             if (st.is_final()) { phase = EP_DONE; break; }
@@ -475,7 +478,8 @@ int launch_mcts_env(const EnvMctsArgs *a, const void *proto, unsigned blocks, si
     if (a->struct_bytes != sizeof(EnvMctsArgs) || a->node_cap < need || !a->arena || !a->eval_count || !a->err || !a->col_err ||
         (a->solve_on ? (!a->success || !a->total || !a->n_steps || a->attempts == 0 || a->max_steps == 0)
                      : (!a->out.rec || !a->out.ep_len || !a->obs16 || a->out.t_pad < 1 || (Env::NUM_ACTIONS > 4 && !a->pw))) ||
-        blocks == 0 || (uint64_t)blocks * Eng::EPB < a->num_columns)
+        blocks == 0 || (uint64_t)blocks * Eng::EPB < a->num_columns ||
+        (a->actions && (!a->solve_on || a->num_columns * (uint64_t)a->actions_stride > 0xffffffffull)))       // (the kernel's 32-bit row index)
         return (int)hipErrorInvalidValue;
     const size_t lds_bytes = engine_lds_bytes + env_mcts_pending_bytes(Env::N_OBS) + env_mcts_probs_bytes(Env::NUM_ACTIONS);
     Env p;

@@ -39,12 +39,16 @@ struct EnvRolloutArgs {
 struct EnvSolveArgs {
     PolicyDev pol;
     uint64_t  num_attempts, episode_offset, seed;
-    uint32_t  num_searches, deterministic, max_steps, pad;
+    uint32_t  num_searches, deterministic, max_steps;
+    uint32_t  from_state;            // solve(): every attempt starts from the prototype AS IT IS (solve.rs:85) -- no reset; its draw key is
+                                     // the attempt's index (episode_offset 0, one episode)
     float    *success, *total;       // [num_attempts]
     uint32_t *n_steps;               // [num_attempts]; an attempt that met a bad id (a bad count of observe_n) at move t: t | 1 << 31,
                                      // its total = the id (the count) as bits; a bad count: its success = 2.0f
     uint32_t *err;                   // as EnvRolloutArgs::err (|= 4: an attempt did not end within max_steps steps)
     unsigned int *queue;             // as EnvRolloutArgs::queue, over attempts
+    uint8_t  *actions;               // null, or [num_attempts][actions_stride]: the moves an attempt played, one byte each (A <= 31),
+    uint32_t  actions_stride;        // addressed by attempt like the three results; a move at or beyond the stride is not stored
 };
 
 // Self-play (solve_on == 0) and MCTS-guided evaluate (solve_on != 0) of mcts_env_kernel (tw_mcts_env.hpp), which a module has when it
@@ -71,6 +75,8 @@ struct EnvMctsArgs {
     uint32_t  *n_steps;              // solve mode: [columns]
     float     *pw;                   // self-play of an environment of more than four actions: [E][t_pad][A] MCTS probabilities of the records,
                                      // addressed like obs16 (the record's four logit slots are then zero and nobody reads them); else null
+    uint32_t   from_state, actions_stride;   // solve mode, as EnvSolveArgs: no reset of the prototype; the row stride of `actions`
+    uint8_t   *actions;              // solve mode: null, or [columns][actions_stride] the moves a column played
 };
 constexpr int ENV_MCTS_NODE_BYTES = 32;
 // the most nodes one move's tree can hold: the root, its children, and per search at most max(max_expand_depth, 1) expansions
@@ -471,8 +477,8 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
         // the ONE place reset() is called from (see rollout_env_kernel).  A fresh attempt whose reset state is already final is over
         // at once (solve.rs:29): its column feeds no row to this step's forward and takes the next attempt at the end of it
         if (fresh) {
-            st = proto;                                                               // evaluate.rs:39
-            st.reset(a.seed, a.episode_offset + att / a.num_searches);                // the episode keys the start state
+            st = proto;                                                               // evaluate.rs:39 / solve.rs:85
+            if (!a.from_state) st.reset(a.seed, a.episode_offset + att / a.num_searches);   // the episode keys the start state
             total = 0.0f; t = 0; fresh = false;
             alive = !st.is_final();
             ended = !alive;
@@ -527,6 +533,8 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
                     action = sample_weighted4(probs, A, u32_to_unit(w.x));
                 }
                 st.step(action);                                                      // solve.rs:56
+                // solve.rs:57-59: the move, into the attempt's own row (alive: att < num_attempts)
+                if (writer && a.actions != nullptr && (uint32_t)t < a.actions_stride) a.actions[att * (uint64_t)a.actions_stride + (uint64_t)t] = (uint8_t)action;
                 ++t;
                 if (st.is_final()) alive = false;
                 else if ((uint32_t)t >= a.max_steps) {                                // the host path's max_steps

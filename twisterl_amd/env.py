@@ -240,7 +240,8 @@ class DeviceEnv:
     PPOCollector.collect and evaluate run its episodes inside one kernel each (tw_ppo_collect_device_env / tw_evaluate_device_env);
     a module built with build_device_env(..., search=True) (1..4 actions; wide_search=True: 1..31) runs AZCollector.collect and evaluate with MCTS inside one kernel too
     (tw_az_collect_device_env; `search` says whether the module has that kernel), any other module steps the same struct's host
-    code for those (tw_az_collect_env / tw_evaluate_env), and solve always does (tw_solve_env32).  The object itself is a
+    code for those (tw_az_collect_env / tw_evaluate_env).  solve runs from the object's CURRENT state in one kernel as evaluate does
+    (tw_solve_device_env; with MCTS: a search module, else the host code, tw_solve_env32).  The object itself is a
     host copy of the struct with the PyBaseEnv surface (reset / step / masks / observe / reward / is_final); collectors clone
     it and reset the clones, as the reference does (collector/ppo.rs:59-60).
 
