@@ -1114,16 +1114,26 @@ int collected_describe(const tw_collected *c, int *is_ppo, uint32_t *n_cells, ui
     return TW_OK;
 }
 const void *collected_field(const tw_collected *c, int field) { return c->field_ptr[field]; }
-// the trajectory workspace and the result-arena pool for the device-environment collectors (tw_device_env.hip)
+// the trajectory workspace for the device-environment collectors (tw_device_env.hip)
 std::mutex &workspace_mutex() { return g_ws_mutex; }
 int workspace_reserve(size_t bytes, void **out) { return ws_reserve(bytes, out); }
-size_t workspace_capacity()
+static size_t workspace_capacity()      // bytes of the cached workspace on the current device (under workspace_mutex()): what a larger request would replace
 {
     int dev = 0;
     return g_ws.ptr && hipGetDevice(&dev) == hipSuccess && g_ws.device == dev ? g_ws.cap : 0;
 }
-int result_arena_acquire(size_t bytes, void **out, size_t *cap) { return arena_acquire(bytes, out, cap); }
-void collected_adopt_stats(tw_collected *c, const tw_collect_stats &st) { c->stats = st; }
+// what can actually be had: free memory plus the cached workspace this call would replace
+int check_memory_fit(size_t need, const char *who)
+{
+    size_t free_b = 0, total_b = 0;
+    TW_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t have = workspace_capacity(), avail = free_b + have;
+    if (need > have && need > (size_t)(0.95 * (double)avail)) {
+        set_error("%s: %zu bytes of tree arenas + trajectories exceed the free device memory (%zu free of %zu)", who, need, avail, total_b);
+        return TW_ERR_UNSUPPORTED;
+    }
+    return TW_OK;
+}
 int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uint32_t n_cells, uint32_t n_actions, uint64_t n_records,
                     uint64_t n_episodes, void *const (&field_ptr)[TW_F_COUNT], const size_t (&field_bytes)[TW_F_COUNT], tw_collected **out)
 {
@@ -1133,6 +1143,69 @@ int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uin
     c->is_ppo = is_ppo; c->n_cells = n_cells; c->n_actions = n_actions; c->n_records = n_records; c->n_episodes = n_episodes;
     for (int f = 0; f < TW_F_COUNT; ++f) { c->field_ptr[f] = field_ptr[f]; c->field_bytes[f] = field_bytes[f]; }
     c->stats.records = n_records; c->stats.episodes = n_episodes;
+    *out = c;
+    return TW_OK;
+}
+
+// ---- the tail of every device collector (CollectTail, tw_common.hpp) ---------------------------------------------------------
+int collect_tail(const CollectTail &d, tw_collected **out)
+{
+    const uint64_t total = d.total, E = d.E;
+    const uint32_t A = d.n_actions, OW = d.obs16 ? d.obs_width : 1u;
+    const int t_pad = d.traj.t_pad;
+    hipStream_t s = d.stream;
+    tw_collected *c = new tw_collected();
+    c->stream = s;
+    c->n_records = total; c->n_episodes = E; c->n_cells = d.n_cells; c->n_actions = A; c->is_ppo = d.is_ppo ? 1 : 0;
+    c->obs_width = OW; c->obs_size = d.obs_size; c->cell_major = d.cell_major; c->ragged = d.ragged;
+    // The fields in arena order, each at 256-byte alignment.  Behind them (A != 4) the four-column logits the finalize kernel writes:
+    // A < 4 narrows them to the result's columns, A > 4 throws them away (the logits come from CollectTail::wide).
+    size_t cur = 0, off[TW_F_COUNT] = {};
+    auto put = [&](int f, size_t bytes) { c->field_bytes[f] = bytes; off[f] = cur; cur = align_up(cur + bytes, 256); };
+    put(TW_F_OBS, total * d.n_cells * OW); put(TW_F_LOGITS, total * A * 4); put(TW_F_PERMS, total);
+    if (d.is_ppo) { put(TW_F_VALUES, total * 4); put(TW_F_REWARDS, total * 4); put(TW_F_ACTIONS, total); put(TW_F_ADVS, total * 4); put(TW_F_RETS, total * 4); }
+    else put(TW_F_REMAINING, total * 4);
+    put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
+    const size_t o_lg4 = A != 4 ? cur : off[TW_F_LOGITS];
+    if (A != 4) cur += total * 16;
+    int rc = hipGetDevice(&c->device) == hipSuccess ? arena_acquire(cur, &c->arena, &c->arena_cap) : TW_ERR_HIP;
+    if (rc) { delete c; return rc; }
+    uint8_t *ca = reinterpret_cast<uint8_t *>(c->arena);
+    for (int f = 0; f < TW_F_COUNT; ++f) c->field_ptr[f] = c->field_bytes[f] ? ca + off[f] : nullptr;
+    auto at = [&](int f) { return reinterpret_cast<float *>(ca + off[f]); };
+
+    // from here on every failing step frees the result (the arena goes back to the pool) and returns what the step returned
+#define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
+    TW_HIP_C(hipEventRecord(d.ev->ev[3], s));
+    const int rec_cells = d.obs16 ? 0 : (int)d.n_cells;                   // (0 cells: the obs ids come from their own array)
+    if (d.is_ppo) {
+        CompactTraj ct{};
+        ct.obs = ca + off[TW_F_OBS]; ct.logits = reinterpret_cast<float *>(ca + o_lg4); ct.perms = reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]);
+        ct.values = at(TW_F_VALUES); ct.rewards = at(TW_F_REWARDS); ct.actions = ca + off[TW_F_ACTIONS]; ct.advs = at(TW_F_ADVS); ct.rets = at(TW_F_RETS);
+        rc = launch_finalize_ppo(d.traj, d.ep_start, E, rec_cells, d.gamma, d.lambda, ct, s);
+    } else {
+        rc = launch_finalize_az(d.traj, d.ep_start, E, rec_cells, ca + off[TW_F_OBS], reinterpret_cast<float *>(ca + o_lg4),
+                                reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]), at(TW_F_REMAINING), s);
+    }
+    if (rc == TW_OK && d.obs16)
+        rc = OW == 2 ? launch_compact_obs16(d.obs16, d.traj.ep_len, d.ep_start, E, t_pad, (int)d.n_cells, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s)
+                     : launch_compact_obs8(d.obs16, d.traj.ep_len, d.ep_start, E, t_pad, (int)d.n_cells, ca + off[TW_F_OBS], s);
+    if (rc == TW_OK && A > 4)                                              // rows of A floats = 2A two-byte units: the same ragged row mover
+        rc = launch_compact_obs16(reinterpret_cast<const uint16_t *>(d.wide), d.traj.ep_len, d.ep_start, E, t_pad, (int)(2 * A),
+                                  reinterpret_cast<uint16_t *>(ca + off[TW_F_LOGITS]), s);
+    if (rc == TW_OK && A < 4) rc = launch_narrow_logits(reinterpret_cast<const float *>(ca + o_lg4), total, (int)A, at(TW_F_LOGITS), s);
+    if (rc) { tw_collected_free(c); return rc; }
+    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_LEN], d.traj.ep_len, E * 4, hipMemcpyDeviceToDevice, s));
+    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_START], d.ep_start, E * 8, hipMemcpyDeviceToDevice, s));
+    TW_HIP_C(hipEventRecord(d.ev->ev[4], s));
+    TW_HIP_C(hipStreamSynchronize(s));
+    c->stats = d.stats;
+    TW_HIP_C(hipEventElapsedTime(&c->stats.ms_rollout, d.ev->ev[0], d.ev->ev[1]));
+    TW_HIP_C(hipEventElapsedTime(&c->stats.ms_scan, d.ev->ev[1], d.ev->ev[2]));
+    TW_HIP_C(hipEventElapsedTime(&c->stats.ms_finalize, d.ev->ev[3], d.ev->ev[4]));
+    TW_HIP_C(hipEventElapsedTime(&c->stats.ms_total, d.ev->ev[0], d.ev->ev[4]));
+#undef TW_HIP_C
+    c->stats.records = total; c->stats.episodes = E;
     *out = c;
     return TW_OK;
 }
@@ -1147,13 +1220,6 @@ extern "C" void tw_collected_free(tw_collected *c)
 
 // ====================================================================================== PPO collect
 namespace {
-
-struct EventSet {
-    hipEvent_t ev[5] = {};
-    int n = 0;
-    ~EventSet() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
-    int init() { for (; n < 5; ++n) TW_HIP(hipEventCreate(&ev[n])); return TW_OK; }
-};
 
 int make_env_consts(const tw_puzzle_desc *env, PuzzleConsts *out, uint64_t max_cells = 16)
 {
@@ -1379,50 +1445,15 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
     }
     if (total == 0 || total > R) { set_error("collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
 
-    // ---- compact result ----------------------------------------------------------------------
-    tw_collected *c = new tw_collected();
-    c->stream = current_stream();
-    c->n_records = total; c->n_episodes = E; c->n_cells = (uint32_t)ra.env.n_cells; c->n_actions = 4; c->is_ppo = 1;
-    size_t ccur = 0;
-    auto cseg = [&](int f, size_t bytes) { c->field_bytes[f] = bytes; size_t o = ccur; ccur = align_up(ccur + bytes, 256); return o; };
-    if (big) c->obs_width = 2;
-    c->obs_size = c->n_cells * c->n_cells; c->cell_major = !big;         // (boards up to 16 cells: cell k holds k * n_cells + tile)
-    const size_t c_obs = cseg(TW_F_OBS, total * c->n_cells * c->obs_width), c_lg = cseg(TW_F_LOGITS, total * 16), c_prm = cseg(TW_F_PERMS, total),
-                 c_val = cseg(TW_F_VALUES, total * 4), c_rew = cseg(TW_F_REWARDS, total * 4), c_act = cseg(TW_F_ACTIONS, total),
-                 c_adv = cseg(TW_F_ADVS, total * 4), c_ret = cseg(TW_F_RETS, total * 4), c_len = cseg(TW_F_EP_LEN, E * 4),
-                 c_start = cseg(TW_F_EP_START, E * 8);
-    rc = hipGetDevice(&c->device) == hipSuccess ? arena_acquire(ccur, &c->arena, &c->arena_cap) : TW_ERR_HIP;
-    if (rc) { delete c; return rc; }
-    uint8_t *ca = reinterpret_cast<uint8_t *>(c->arena);
-    const size_t offs[TW_F_COUNT] = {c_obs, c_lg, c_prm, c_val, c_rew, c_act, c_adv, c_ret, 0, c_len, c_start};
-    for (int f = 0; f < TW_F_COUNT; ++f) c->field_ptr[f] = c->field_bytes[f] ? ca + offs[f] : nullptr;
-    CompactTraj ct{};
-    ct.obs = ca + c_obs; ct.logits = reinterpret_cast<float *>(ca + c_lg); ct.perms = reinterpret_cast<int8_t *>(ca + c_prm);
-    ct.values = reinterpret_cast<float *>(ca + c_val); ct.rewards = reinterpret_cast<float *>(ca + c_rew);
-    ct.actions = ca + c_act; ct.advs = reinterpret_cast<float *>(ca + c_adv); ct.rets = reinterpret_cast<float *>(ca + c_ret);
-
-#define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
-    TW_HIP_C(hipEventRecord(ev.ev[3], s));
-    rc = launch_finalize_ppo(ra.out, ep_start_ws, E, big ? 0 : ra.env.n_cells, prm->gamma, prm->lambda, ct, s);      // (0 cells: the obs ids come from their own array)
-    if (rc == TW_OK && big)
-        rc = launch_compact_obs16(reinterpret_cast<const uint16_t *>(ws + o_obs16), ra.out.ep_len, ep_start_ws, E, t_pad, ra.env.n_cells,
-                                  reinterpret_cast<uint16_t *>(ca + c_obs), s);
-    if (rc) { tw_collected_free(c); return rc; }
-    TW_HIP_C(hipMemcpyAsync(ca + c_len, ra.out.ep_len, E * 4, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipMemcpyAsync(ca + c_start, ep_start_ws, E * 8, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipEventRecord(ev.ev[4], s));
-    TW_HIP_C(hipStreamSynchronize(s));
-    float ms = 0;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1])); st.ms_rollout = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[1], ev.ev[2])); st.ms_scan = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[3], ev.ev[4])); st.ms_finalize = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[4])); st.ms_total = ms;
-#undef TW_HIP_C
-    st.records = total; st.episodes = E; st.padded_bytes = cur; st.forward_evals = total;
+    st.padded_bytes = cur; st.forward_evals = total;
     st.reused_evals = ra.reused ? total_and_flag[1] >> 32 : 0;
-    c->stats = st;
-    *out = c;
-    return TW_OK;
+    CollectTail tail{};
+    tail.is_ppo = true; tail.traj = ra.out; tail.ep_start = ep_start_ws; tail.E = E; tail.total = total;
+    tail.n_cells = (uint32_t)ra.env.n_cells; tail.n_actions = 4; tail.obs_size = tail.n_cells * tail.n_cells;
+    tail.cell_major = !big;                                                       // (boards up to 16 cells: cell k holds k * n_cells + tile)
+    if (big) { tail.obs16 = reinterpret_cast<const uint16_t *>(ws + o_obs16); tail.obs_width = 2; }
+    tail.gamma = prm->gamma; tail.lambda = prm->lambda; tail.ev = &ev; tail.stream = s; tail.stats = st;
+    return collect_tail(tail, out);
 }
 
 static int az_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, const tw_az_params *prm, tw_collected **out, bool *split_watchdog);
@@ -1505,16 +1536,7 @@ static int az_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, c
     const size_t o_tbl = seg(tbl_bytes);
     const bool split = deep && mcts_deep_split(E, ma.reserve_cus, ma.num_searches);      // walkers and engine as two kernels: a 256-byte mailbox per walker
     const size_t o_mb = seg(split ? (size_t)arenas * 256 + 256 : 0);          // (+ the engines' residency counter)
-    size_t free_b = 0, total_b = 0;
-    TW_HIP(hipMemGetInfo(&free_b, &total_b));
-    {   // what can actually be had: free memory plus the cached workspace this call would replace
-        int dev_now = 0; TW_HIP(hipGetDevice(&dev_now));
-        const size_t avail = free_b + (g_ws.ptr && g_ws.device == dev_now ? g_ws.cap : 0);
-        if (cur > g_ws.cap && cur > (size_t)(0.95 * (double)avail)) {
-            set_error("tw_az_collect: %zu bytes of tree arenas + trajectories exceed the free device memory (%zu free of %zu)", cur, avail, total_b);
-            return TW_ERR_UNSUPPORTED;
-        }
-    }
+    rc = check_memory_fit(cur, "tw_az_collect"); if (rc) return rc;
     void *wsp = nullptr;
     rc = ws_reserve(cur, &wsp); if (rc) return rc;
     uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
@@ -1582,46 +1604,17 @@ static int az_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, c
     }
     if (total == 0 || total > R) { set_error("az collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
 
-    tw_collected *c = new tw_collected();
-    c->stream = current_stream();
-    c->n_records = total; c->n_episodes = E; c->n_cells = (uint32_t)ma.env.n_cells; c->n_actions = 4; c->is_ppo = 0;
-    size_t ccur = 0;
-    auto cseg = [&](int f, size_t bytes) { c->field_bytes[f] = bytes; size_t o = ccur; ccur = align_up(ccur + bytes, 256); return o; };
-    if (big) c->obs_width = 2;
-    c->obs_size = c->n_cells * c->n_cells; c->cell_major = !big;         // (boards up to 16 cells: cell k holds k * n_cells + tile)
-    const size_t c_obs = cseg(TW_F_OBS, total * c->n_cells * c->obs_width), c_lg = cseg(TW_F_LOGITS, total * 16), c_prm = cseg(TW_F_PERMS, total),
-                 c_rem = cseg(TW_F_REMAINING, total * 4), c_len = cseg(TW_F_EP_LEN, E * 4), c_start = cseg(TW_F_EP_START, E * 8);
-    rc = hipGetDevice(&c->device) == hipSuccess ? arena_acquire(ccur, &c->arena, &c->arena_cap) : TW_ERR_HIP;
-    if (rc) { delete c; return rc; }
-    uint8_t *ca = reinterpret_cast<uint8_t *>(c->arena);
-    c->field_ptr[TW_F_OBS] = ca + c_obs; c->field_ptr[TW_F_LOGITS] = ca + c_lg; c->field_ptr[TW_F_PERMS] = ca + c_prm;
-    c->field_ptr[TW_F_REMAINING] = ca + c_rem; c->field_ptr[TW_F_EP_LEN] = ca + c_len; c->field_ptr[TW_F_EP_START] = ca + c_start;
-
-#define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
-    TW_HIP_C(hipEventRecord(ev.ev[3], s));
-    rc = launch_finalize_az(ma.out, ep_start_ws, E, big ? 0 : ma.env.n_cells, ca + c_obs, reinterpret_cast<float *>(ca + c_lg),      // (0 cells: the obs ids come from their own array)
-                            reinterpret_cast<int8_t *>(ca + c_prm), reinterpret_cast<float *>(ca + c_rem), s);
-    if (rc == TW_OK && big)
-        rc = launch_compact_obs16(reinterpret_cast<const uint16_t *>(ws + o_obs16), ma.out.ep_len, ep_start_ws, E, t_pad, (int)cells,
-                                  reinterpret_cast<uint16_t *>(ca + c_obs), s);
-    if (rc) { tw_collected_free(c); return rc; }
-    TW_HIP_C(hipMemcpyAsync(ca + c_len, ma.out.ep_len, E * 4, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipMemcpyAsync(ca + c_start, ep_start_ws, E * 8, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipEventRecord(ev.ev[4], s));
-    TW_HIP_C(hipStreamSynchronize(s));
-    float ms = 0;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1])); st.ms_rollout = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[1], ev.ev[2])); st.ms_scan = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[3], ev.ev[4])); st.ms_finalize = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[4])); st.ms_total = ms;
-#undef TW_HIP_C
-    st.records = total; st.episodes = E; st.padded_bytes = cur;
+    st.padded_bytes = cur;
     st.forward_evals = host_tot[1] * (uint64_t)(ma.pol.n_perms > 0 ? ma.pol.n_perms : 1);
     st.speculative_evals = host_tot[2] * (uint64_t)(ma.pol.n_perms > 0 ? ma.pol.n_perms : 1);
     st.reused_evals = host_tot[3] * (uint64_t)(ma.pol.n_perms > 0 ? ma.pol.n_perms : 1);
-    c->stats = st;
-    *out = c;
-    return TW_OK;
+    CollectTail tail{};
+    tail.is_ppo = false; tail.traj = ma.out; tail.ep_start = ep_start_ws; tail.E = E; tail.total = total;
+    tail.n_cells = (uint32_t)ma.env.n_cells; tail.n_actions = 4; tail.obs_size = tail.n_cells * tail.n_cells;
+    tail.cell_major = !big;                                                       // (boards up to 16 cells: cell k holds k * n_cells + tile)
+    if (big) { tail.obs16 = reinterpret_cast<const uint16_t *>(ws + o_obs16); tail.obs_width = 2; }
+    tail.ev = &ev; tail.stream = s; tail.stats = st;
+    return collect_tail(tail, out);
 }
 
 // ====================================================================================== solve / evaluate

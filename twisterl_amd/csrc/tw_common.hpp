@@ -559,6 +559,10 @@ uint64_t rollout_generic_resident_episodes(const PolicyDev &pol, int n_cells, in
 int launch_rollout_big(const RolloutArgs &a, uint16_t *obs16, hipStream_t s, uint32_t *blocks, uint32_t *threads);
 int launch_compact_obs16(const uint16_t *obs16, const uint32_t *ep_len, const uint64_t *ep_start, uint64_t E, int t_pad, int n_cells,
                          uint16_t *out, hipStream_t s);
+// the same ids as one byte each (environments with at most 256 ids), and four-column logits -> A < 4 columns (tw_device_env.hip)
+int launch_compact_obs8(const uint16_t *obs16, const uint32_t *ep_len, const uint64_t *ep_start, uint64_t E, int t_pad, int n_obs,
+                        uint8_t *out, hipStream_t s);
+int launch_narrow_logits(const float *lg4, uint64_t n, int A, float *out, hipStream_t s);
 int launch_init_boards(const PuzzleConsts &env, uint64_t seed, uint64_t episode_offset, uint64_t n, uint64_t *out, hipStream_t s, uint4 *entries = nullptr);   // entries: {board, episode i} in index order
 // episodes by decreasing distance of their start board from the solved one (sum of the tiles' Manhattan distances): the order the
 // self-play walkers take them in -- the episodes that are likely to run to the depth limit start first (tw_rollout.hip)
@@ -712,9 +716,31 @@ int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uin
 // the cached trajectory workspace (held under workspace_mutex() while in use) and the pooled result arenas (tw_api.hip)
 std::mutex &workspace_mutex();
 int workspace_reserve(size_t bytes, void **out);
-size_t workspace_capacity();      // bytes of the cached workspace on the current device (under workspace_mutex()): what a larger request would replace
-int result_arena_acquire(size_t bytes, void **out, size_t *cap);
-void collected_adopt_stats(tw_collected *c, const tw_collect_stats &st);
+// refuses `need` bytes of workspace that neither the cached workspace nor 95 % of (free memory + that workspace) holds
+int check_memory_fit(size_t need, const char *who);
+// the five events of a device collect: 0 | rollout | 1 | scan | 2 ... 3 | finalize | 4
+struct EventSet {
+    hipEvent_t ev[5] = {};
+    int n = 0;
+    ~EventSet() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
+    int init() { for (; n < 5; ++n) TW_HIP(hipEventCreate(&ev[n])); return TW_OK; }
+};
+// What a device collector hands to collect_tail() once its kernel has run, the episodes are scanned and the record count is in range
+struct CollectTail {
+    bool is_ppo;
+    PaddedTraj traj; const uint64_t *ep_start;        // [E][t_pad] records + ep_len; [E] from launch_scan
+    uint64_t E, total;                                // episodes, records
+    uint32_t n_cells, n_actions, obs_size;            // ids per record, columns of TW_F_LOGITS, the ids' range
+    bool cell_major, ragged;
+    const uint16_t *obs16; uint32_t obs_width;        // null: one-byte ids in the records; else [E][t_pad][n_cells], written out at 1 or 2 bytes per id
+    const float *wide;                                // A > 4: the logits / probabilities [E][t_pad][A]; else the records' four columns (A < 4: narrowed)
+    float gamma, lambda;                              // PPO only
+    const EventSet *ev; hipStream_t stream;           // events 0..2 are the caller's
+    tw_collect_stats stats;                           // the caller's: rollout_blocks / _threads, padded_bytes, *_evals; the tail's: ms_*, records, episodes
+};
+// The one ending of the device collectors: the fields in a pooled arena, finalize (GAE or remaining values + compaction), the obs and
+// logits steps the descriptor asks for, ep_len / ep_start, the timings.  On failure nothing is left behind.
+int collect_tail(const CollectTail &d, tw_collected **out);
 int launch_policy_eval(const PolicyDev &pol, int mode, const int32_t *obs_d, uint32_t n, uint32_t n_obs,
                        const uint8_t *masks_d, const int32_t *perms_d, float *out_actions_d, float *out_values_d,
                        hipStream_t s);

@@ -2,7 +2,10 @@
 //
 // A device-environment module (twisterl_amd.build.build_device_env) holds the environment's kernels -- rollout_env_kernel /
 // solve_env_kernel of tw_rollout_env.hpp instantiated over the user's struct -- their launchers and a host adapter.  Everything
-// else is here: the checks, the workspace, the scan / GAE / compaction of the Puzzle path (tw_finalize.hip), the error messages.
+// else is here: the checks, the workspace, the scan, the error messages.  The result is built by collect_tail (tw_api.hip), the one
+// ending of every device collector: the ids always have their own array here (CollectTail::obs16, written out as one or two bytes per
+// id), and an environment with other than four actions has its logits narrowed (A < 4) or moved from a wide array (A > 4).  The two
+// small kernels that serves, compact_env_obs8_kernel and narrow_logits_kernel, live here behind launch_compact_obs8 / launch_narrow_logits.
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
 // the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error), and -- for
 // a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has no search launcher -- self-play,
@@ -142,19 +145,6 @@ bool search_fits(uint32_t A, uint32_t S, uint32_t MED, uint64_t moves, uint64_t 
     return per_move <= 0x0fffffffull && *node_cap <= 0x7fffffffull && (per_move + 1) * moves <= 0xffffffffull;
 }
 
-// free memory plus the cached workspace this call would replace (az_collect_once's test)
-int check_memory_fit(size_t need, const char *who)
-{
-    size_t free_b = 0, total_b = 0;
-    TW_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t have = workspace_capacity(), avail = free_b + have;
-    if (need > have && need > (size_t)(0.95 * (double)avail)) {
-        set_error("%s: %zu bytes of tree arenas + trajectories exceed the free device memory (%zu free of %zu)", who, need, avail, total_b);
-        return TW_ERR_UNSUPPORTED;
-    }
-    return TW_OK;
-}
-
 // The error the host-stepped path reports for the columns mcts_env_kernel ended (EnvMctsArgs::col_err).  That path evaluates one
 // state per live episode per round and checks the ids as it stages them, episode by episode: the first bad id (count) is the one
 // with the smallest evaluation ordinal, then the smallest column.  It notices an overlong episode only before the NEXT round, so a
@@ -183,6 +173,21 @@ int search_launch_refused(const char *who)
 }
 
 }  // namespace
+
+int tw::launch_compact_obs8(const uint16_t *obs16, const uint32_t *ep_len, const uint64_t *ep_start, uint64_t E, int t_pad, int n_obs,
+                            uint8_t *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(compact_env_obs8_kernel, dim3(grid_for(E, 4)), dim3(256), 0, s, obs16, ep_len, ep_start, E, t_pad, n_obs, out);
+    TW_HIP(hipGetLastError());
+    return TW_OK;
+}
+
+int tw::launch_narrow_logits(const float *lg4, uint64_t n, int A, float *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(narrow_logits_kernel, dim3(grid_for(n * (uint64_t)A, 256)), dim3(256), 0, s, lg4, n, A, out);
+    TW_HIP(hipGetLastError());
+    return TW_OK;
+}
 
 extern "C" int tw_device_env_host_vtable(const tw_device_env *env, const void *proto, size_t proto_bytes, tw_env_vtable *out)
 {
@@ -241,8 +246,7 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     ra.num_episodes = E; ra.episode_offset = prm->episode_offset; ra.seed = prm->seed;
     uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
 
-    struct Events { hipEvent_t ev[5] = {}; ~Events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); } } ev;
-    for (auto &e : ev.ev) TW_HIP(hipEventCreate(&e));
+    EventSet ev; rc = ev.init(); if (rc) return rc;
     TW_HIP(hipMemsetAsync(ws + o_total, 0, 32, s));
     if (grid.persist) {                                                   // slot i starts with episode i; the queue starts behind the slots
         ra.queue = reinterpret_cast<unsigned int *>(ws + o_total + 16);
@@ -284,71 +288,19 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     if (err & 2u) { set_error("tw_ppo_collect_env: an episode did not end within %u records", max_records_per_episode); return TW_ERR_INVALID; }
     if (total == 0 || total > R) { set_error("collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
 
-    // ---- compact result: the fields of tw_ppo_collect_env, then (A != 4) the four-column logits the finalize kernel writes: A < 4
-    // narrows them to the environment's columns, A > 4 throws them away (the logits come from EnvRolloutArgs::lgw) ---------------------
-    size_t ccur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
-    auto put = [&](int f, size_t b) { bytes[f] = b; off[f] = ccur; ccur = (ccur + b + 255) / 256 * 256; };
-    put(TW_F_OBS, total * NO * OW); put(TW_F_LOGITS, total * A * 4); put(TW_F_PERMS, total); put(TW_F_VALUES, total * 4); put(TW_F_REWARDS, total * 4);
-    put(TW_F_ACTIONS, total); put(TW_F_ADVS, total * 4); put(TW_F_RETS, total * 4); put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
-    const size_t o_lg4 = ccur;
-    if (A != 4) ccur += total * 16;
-    void *arena = nullptr; size_t cap = 0;
-    rc = result_arena_acquire(ccur, &arena, &cap); if (rc) return rc;
-    uint8_t *ca = reinterpret_cast<uint8_t *>(arena);
-    void *fp[TW_F_COUNT] = {};
-    for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) fp[f] = ca + off[f];
-    int dev_id = 0; (void)hipGetDevice(&dev_id);
-    tw_collected *c = nullptr;
-    rc = collected_adopt(arena, cap, dev_id, 1, NO, A, total, E, fp, bytes, &c);
-    if (rc) { (void)hipFree(arena); return rc; }
-    collected_adopt_obs_width(c, OW);
-    collected_adopt_obs_layout(c, (uint32_t)pd->obs_size, false);         // an environment's ids: any of [0, obs_size), in any order
-    if (ragged) collected_adopt_obs_ragged(c);
-#define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
-    CompactTraj ct{};
-    ct.obs = nullptr;                                                          // (0 cells: the ids have their own array)
-    ct.logits = reinterpret_cast<float *>(A != 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]); ct.perms = reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]);
-    ct.values = reinterpret_cast<float *>(ca + off[TW_F_VALUES]); ct.rewards = reinterpret_cast<float *>(ca + off[TW_F_REWARDS]);
-    ct.actions = ca + off[TW_F_ACTIONS]; ct.advs = reinterpret_cast<float *>(ca + off[TW_F_ADVS]); ct.rets = reinterpret_cast<float *>(ca + off[TW_F_RETS]);
-    TW_HIP_C(hipEventRecord(ev.ev[3], s));
-    rc = launch_finalize_ppo(ra.out, ep_start_ws, E, 0, prm->gamma, prm->lambda, ct, s);
-    if (rc == TW_OK && OW == 2)
-        rc = launch_compact_obs16(ra.obs16, ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s);
-    if (rc == TW_OK && A > 4)                                                  // rows of A floats = 2A two-byte units: the same ragged row mover
-        rc = launch_compact_obs16(reinterpret_cast<const uint16_t *>(ra.lgw), ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)(2 * A),
-                                  reinterpret_cast<uint16_t *>(ca + off[TW_F_LOGITS]), s);
-    if (rc) { tw_collected_free(c); return rc; }
-    if (OW == 1) {
-        hipLaunchKernelGGL(compact_env_obs8_kernel, dim3(grid_for(E, 4)), dim3(256), 0, s, ra.obs16, ra.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO,
-                           ca + off[TW_F_OBS]);
-        TW_HIP_C(hipGetLastError());
-    }
-    if (A < 4) {
-        hipLaunchKernelGGL(narrow_logits_kernel, dim3(grid_for(total * A, 256)), dim3(256), 0, s, reinterpret_cast<const float *>(ca + o_lg4), total,
-                           (int)A, reinterpret_cast<float *>(ca + off[TW_F_LOGITS]));
-        TW_HIP_C(hipGetLastError());
-    }
-    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_LEN], ra.out.ep_len, E * 4, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_START], ep_start_ws, E * 8, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipEventRecord(ev.ev[4], s));
-    TW_HIP_C(hipStreamSynchronize(s));
-    tw_collect_stats st{};
-    float ms = 0;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1])); st.ms_rollout = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[1], ev.ev[2])); st.ms_scan = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[3], ev.ev[4])); st.ms_finalize = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[4])); st.ms_total = ms;
-#undef TW_HIP_C
-    st.records = total; st.episodes = E; st.padded_bytes = cur; st.forward_evals = total;
-    st.rollout_blocks = (uint32_t)blocks; st.rollout_threads = 256;
-    collected_adopt_stats(c, st);
-    *out = c;
-    return TW_OK;
+    CollectTail tail{};
+    tail.is_ppo = true; tail.traj = ra.out; tail.ep_start = ep_start_ws; tail.E = E; tail.total = total;
+    tail.n_cells = NO; tail.n_actions = A; tail.obs_size = (uint32_t)pd->obs_size; tail.ragged = ragged;
+    tail.cell_major = false;                                              // an environment's ids: any of [0, obs_size), in any order
+    tail.obs16 = ra.obs16; tail.obs_width = OW; tail.wide = ra.lgw;
+    tail.gamma = prm->gamma; tail.lambda = prm->lambda; tail.ev = &ev; tail.stream = s;
+    tail.stats.padded_bytes = cur; tail.stats.forward_evals = total;
+    tail.stats.rollout_blocks = (uint32_t)blocks; tail.stats.rollout_threads = 256;
+    return collect_tail(tail, out);
 }
 
-// AZCollector::collect (az.rs:51-109) of a device environment whose module holds the search kernel: self-play in mcts_env_kernel, then
-// the tail of az_collect_once -- scan, launch_finalize_az (0 cells: the ids have their own array), the obs compaction of the PPO path
-// above, narrow_logits_kernel for A < 4.  Byte-equal to tw_az_collect_env over the module's vtable, which is also where everything
+// AZCollector::collect (az.rs:51-109) of a device environment whose module holds the search kernel: self-play in mcts_env_kernel, the
+// scan, then collect_tail as above.  Byte-equal to tw_az_collect_env over the module's vtable, which is also where everything
 // the kernel or the finalize step does not take goes.
 extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
                                         const tw_az_params *prm, uint32_t max_records_per_episode, tw_collected **out)
@@ -405,8 +357,7 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     if (A > 4) ma.pw = reinterpret_cast<float *>(ws + o_pw);
     uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
 
-    struct Events { hipEvent_t ev[5] = {}; ~Events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); } } ev;
-    for (auto &e : ev.ev) TW_HIP(hipEventCreate(&e));
+    EventSet ev; rc = ev.init(); if (rc) return rc;
     TW_HIP(hipMemsetAsync(ws + o_total, 0, 32, s));
     TW_HIP(hipMemsetAsync(ws + o_ce, 0, E * 16, s));
     TW_HIP(hipEventRecord(ev.ev[0], s));
@@ -431,63 +382,16 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     }
     if (total == 0 || total > R) { set_error("az collect: inconsistent record count %llu (max %llu)", (unsigned long long)total, (unsigned long long)R); return TW_ERR_HIP; }
 
-    // ---- compact result: the fields of tw_az_collect_env, then (A != 4) the four-column probabilities the finalize kernel writes: A < 4
-    // narrows them to the environment's columns, A > 4 throws them away (the probabilities come from EnvMctsArgs::pw) -------------------
-    size_t ccur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
-    auto put = [&](int f, size_t b) { bytes[f] = b; off[f] = ccur; ccur = (ccur + b + 255) / 256 * 256; };
-    put(TW_F_OBS, total * NO * OW); put(TW_F_LOGITS, total * A * 4); put(TW_F_PERMS, total); put(TW_F_REMAINING, total * 4);
-    put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
-    const size_t o_lg4 = ccur;
-    if (A != 4) ccur += total * 16;
-    void *arena = nullptr; size_t cap = 0;
-    rc = result_arena_acquire(ccur, &arena, &cap); if (rc) return rc;
-    uint8_t *ca = reinterpret_cast<uint8_t *>(arena);
-    void *fp[TW_F_COUNT] = {};
-    for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) fp[f] = ca + off[f];
-    int dev_id = 0; (void)hipGetDevice(&dev_id);
-    tw_collected *c = nullptr;
-    rc = collected_adopt(arena, cap, dev_id, 0, NO, A, total, E, fp, bytes, &c);
-    if (rc) { (void)hipFree(arena); return rc; }
-    collected_adopt_obs_width(c, OW);
-    collected_adopt_obs_layout(c, (uint32_t)pd->obs_size, false);         // an environment's ids: any of [0, obs_size), in any order
-    if (ragged) collected_adopt_obs_ragged(c);
-#define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
-    TW_HIP_C(hipEventRecord(ev.ev[3], s));
-    rc = launch_finalize_az(ma.out, ep_start_ws, E, 0, ca + off[TW_F_OBS], reinterpret_cast<float *>(A != 4 ? ca + o_lg4 : ca + off[TW_F_LOGITS]),
-                            reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]), reinterpret_cast<float *>(ca + off[TW_F_REMAINING]), s);
-    if (rc == TW_OK && OW == 2)
-        rc = launch_compact_obs16(ma.obs16, ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s);
-    if (rc == TW_OK && A > 4)                                                  // rows of A floats = 2A two-byte units (the PPO path's row mover)
-        rc = launch_compact_obs16(reinterpret_cast<const uint16_t *>(ma.pw), ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)(2 * A),
-                                  reinterpret_cast<uint16_t *>(ca + off[TW_F_LOGITS]), s);
-    if (rc) { tw_collected_free(c); return rc; }
-    if (OW == 1) {
-        hipLaunchKernelGGL(compact_env_obs8_kernel, dim3(grid_for(E, 4)), dim3(256), 0, s, ma.obs16, ma.out.ep_len, ep_start_ws, E, (int)t_pad, (int)NO,
-                           ca + off[TW_F_OBS]);
-        TW_HIP_C(hipGetLastError());
-    }
-    if (A < 4) {
-        hipLaunchKernelGGL(narrow_logits_kernel, dim3(grid_for(total * A, 256)), dim3(256), 0, s, reinterpret_cast<const float *>(ca + o_lg4), total,
-                           (int)A, reinterpret_cast<float *>(ca + off[TW_F_LOGITS]));
-        TW_HIP_C(hipGetLastError());
-    }
-    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_LEN], ma.out.ep_len, E * 4, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipMemcpyAsync(ca + off[TW_F_EP_START], ep_start_ws, E * 8, hipMemcpyDeviceToDevice, s));
-    TW_HIP_C(hipEventRecord(ev.ev[4], s));
-    TW_HIP_C(hipStreamSynchronize(s));
-    tw_collect_stats st{};
-    float ms = 0;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1])); st.ms_rollout = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[1], ev.ev[2])); st.ms_scan = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[3], ev.ev[4])); st.ms_finalize = ms;
-    TW_HIP_C(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[4])); st.ms_total = ms;
-#undef TW_HIP_C
-    st.records = total; st.episodes = E; st.padded_bytes = cur;
-    st.forward_evals = hv[2] * (uint64_t)(pd->n_perms > 0 ? pd->n_perms : 1);
-    st.rollout_blocks = (uint32_t)blocks; st.rollout_threads = 256;
-    collected_adopt_stats(c, st);
-    *out = c;
-    return TW_OK;
+    CollectTail tail{};
+    tail.is_ppo = false; tail.traj = ma.out; tail.ep_start = ep_start_ws; tail.E = E; tail.total = total;
+    tail.n_cells = NO; tail.n_actions = A; tail.obs_size = (uint32_t)pd->obs_size; tail.ragged = ragged;
+    tail.cell_major = false;                                              // an environment's ids: any of [0, obs_size), in any order
+    tail.obs16 = ma.obs16; tail.obs_width = OW; tail.wide = ma.pw;
+    tail.ev = &ev; tail.stream = s;
+    tail.stats.padded_bytes = cur;
+    tail.stats.forward_evals = hv[2] * (uint64_t)(pd->n_perms > 0 ? pd->n_perms : 1);
+    tail.stats.rollout_blocks = (uint32_t)blocks; tail.stats.rollout_threads = 256;
+    return collect_tail(tail, out);
 }
 
 namespace {

@@ -39,6 +39,34 @@ int observe_checked(const tw_env_vtable *env, void *st, int32_t *row, uint32_t N
     return TW_OK;
 }
 
+// The ending of both host-stepped collectors: the host images of the compact fields (src[f] of bytes[f]; 0 bytes: the result has no such
+// field) go into ONE device allocation, in field order at 256-byte alignment, which becomes the result object.
+int upload_collected(const void *const (&src)[TW_F_COUNT], const size_t (&bytes)[TW_F_COUNT], int is_ppo, uint32_t NO, uint32_t A, uint64_t total,
+                     uint64_t E, uint32_t OW, uint32_t obs_size, bool ragged, tw_collected **out)
+{
+    hipStream_t s = current_stream();
+    size_t cur = 0, off[TW_F_COUNT] = {};
+    for (int f = 0; f < TW_F_COUNT; ++f) { off[f] = cur; cur = (cur + bytes[f] + 255) / 256 * 256; }
+    void *arena = nullptr;
+    TW_HIP(hipMalloc(&arena, cur ? cur : 256));
+    void *fp[TW_F_COUNT] = {};
+    hipError_t he = hipSuccess;
+    for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) {
+        fp[f] = reinterpret_cast<uint8_t *>(arena) + off[f];
+        he = hipMemcpyAsync(fp[f], src[f], bytes[f], hipMemcpyHostToDevice, s);
+        if (he != hipSuccess) { (void)hipFree(arena); return hip_fail(he, "upload of the collected fields", __FILE__, __LINE__); }
+    }
+    he = hipStreamSynchronize(s);
+    if (he != hipSuccess) { (void)hipFree(arena); return hip_fail(he, "upload of the collected fields", __FILE__, __LINE__); }
+    int dev_id = 0; (void)hipGetDevice(&dev_id);
+    const int rc = collected_adopt(arena, cur ? cur : 256, dev_id, is_ppo, NO, A, total, E, fp, bytes, out);
+    if (rc) { (void)hipFree(arena); return rc; }
+    collected_adopt_obs_width(*out, OW);
+    collected_adopt_obs_layout(*out, obs_size, false);                    // an environment's ids: any of [0, obs_size), in any order
+    if (ragged) collected_adopt_obs_ragged(*out);
+    return TW_OK;
+}
+
 }  // namespace
 
 extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *policy, const tw_ppo_params *prm,
@@ -170,29 +198,12 @@ extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *pol
         pos += nrec;
     }
     // ---- the result object: one device allocation ---------------------------------------------------------------------
-    size_t cur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
-    const void *src[TW_F_COUNT] = {};
-    auto put = [&](int f, const void *p, size_t b) { src[f] = p; bytes[f] = b; off[f] = cur; cur = (cur + b + 255) / 256 * 256; };
+    const void *src[TW_F_COUNT] = {}; size_t bytes[TW_F_COUNT] = {};
+    auto put = [&](int f, const void *p, size_t b) { src[f] = p; bytes[f] = b; };
     put(TW_F_OBS, f_obs.data(), f_obs.size()); put(TW_F_LOGITS, f_lg.data(), f_lg.size() * 4); put(TW_F_PERMS, f_perm.data(), f_perm.size());
     put(TW_F_VALUES, f_val.data(), total * 4); put(TW_F_REWARDS, f_rew.data(), total * 4); put(TW_F_ACTIONS, f_act.data(), total);
     put(TW_F_ADVS, f_adv.data(), total * 4); put(TW_F_RETS, f_ret.data(), total * 4); put(TW_F_EP_LEN, f_len.data(), E * 4); put(TW_F_EP_START, f_start.data(), E * 8);
-    void *arena = nullptr;
-    TW_HIP(hipMalloc(&arena, cur ? cur : 256));
-    void *fp[TW_F_COUNT] = {};
-    for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) {
-        fp[f] = reinterpret_cast<uint8_t *>(arena) + off[f];
-        he = hipMemcpyAsync(fp[f], src[f], bytes[f], hipMemcpyHostToDevice, s);
-        if (he != hipSuccess) { (void)hipFree(arena); return hip_fail(he, "upload of the collected fields", __FILE__, __LINE__); }
-    }
-    he = hipStreamSynchronize(s);
-    if (he != hipSuccess) { (void)hipFree(arena); return hip_fail(he, "upload of the collected fields", __FILE__, __LINE__); }
-    int dev_id = 0; (void)hipGetDevice(&dev_id);
-    rc = collected_adopt(arena, cur ? cur : 256, dev_id, 1, NO, A, total, E, fp, bytes, out);
-    if (rc) { (void)hipFree(arena); return rc; }
-    collected_adopt_obs_width(*out, OW);
-    collected_adopt_obs_layout(*out, (uint32_t)pd->obs_size, false);      // an environment's ids: any of [0, obs_size), in any order
-    if (ragged) collected_adopt_obs_ragged(*out);
-    return TW_OK;
+    return upload_collected(src, bytes, 1, NO, A, total, E, OW, (uint32_t)pd->obs_size, ragged, out);
 }
 
 // ======================================================================================================================
@@ -471,30 +482,11 @@ extern "C" int tw_az_collect_env(const tw_env_vtable *env, const tw_policy *poli
         pos += nrec;
     }
     cleanup();
-    hipStream_t s = current_stream();
-    size_t cur = 0, off[TW_F_COUNT] = {}, bytes[TW_F_COUNT] = {};
-    const void *src[TW_F_COUNT] = {};
-    auto put = [&](int f, const void *p, size_t b) { src[f] = p; bytes[f] = b; off[f] = cur; cur = (cur + b + 255) / 256 * 256; };
+    const void *src[TW_F_COUNT] = {}; size_t bytes[TW_F_COUNT] = {};
+    auto put = [&](int f, const void *p, size_t b) { src[f] = p; bytes[f] = b; };
     put(TW_F_OBS, f_obs.data(), f_obs.size()); put(TW_F_LOGITS, f_lg.data(), f_lg.size() * 4); put(TW_F_PERMS, f_perm.data(), f_perm.size());
     put(TW_F_REMAINING, f_rem.data(), total * 4); put(TW_F_EP_LEN, f_len.data(), E * 4); put(TW_F_EP_START, f_start.data(), E * 8);
-    void *arena = nullptr;
-    TW_HIP(hipMalloc(&arena, cur ? cur : 256));
-    void *fp[TW_F_COUNT] = {};
-    hipError_t he = hipSuccess;
-    for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) {
-        fp[f] = reinterpret_cast<uint8_t *>(arena) + off[f];
-        he = hipMemcpyAsync(fp[f], src[f], bytes[f], hipMemcpyHostToDevice, s);
-        if (he != hipSuccess) { (void)hipFree(arena); return hip_fail(he, "upload of the collected fields", __FILE__, __LINE__); }
-    }
-    he = hipStreamSynchronize(s);
-    if (he != hipSuccess) { (void)hipFree(arena); return hip_fail(he, "upload of the collected fields", __FILE__, __LINE__); }
-    int dev_id = 0; (void)hipGetDevice(&dev_id);
-    rc = collected_adopt(arena, cur ? cur : 256, dev_id, 0, NO, A, total, E, fp, bytes, out);
-    if (rc) { (void)hipFree(arena); return rc; }
-    collected_adopt_obs_width(*out, OW);
-    collected_adopt_obs_layout(*out, (uint32_t)pd->obs_size, false);      // an environment's ids: any of [0, obs_size), in any order
-    if (ragged) collected_adopt_obs_ragged(*out);
-    return TW_OK;
+    return upload_collected(src, bytes, 0, NO, A, total, E, OW, (uint32_t)pd->obs_size, ragged, out);
 }
 
 // ---- single_solve / solve / evaluate (solve.rs:17-101, evaluate.rs:22-89) -------------------------------------------------
