@@ -113,6 +113,9 @@ extern "C" {
     // evaluate / solve (attempt a of episode e at e * num_searches + a; *n attempts, up to cap copied)
     #[allow(dead_code)] fn tw_debug_last_launch(out: *mut TwLaunchInfo) -> c_int;
     #[allow(dead_code)] fn tw_debug_last_attempts(success: *mut f32, total: *mut f32, n_steps: *mut u32, cap: u64, n: *mut u64) -> c_int;
+    // test hook: a policy's device image (*bytes in all, up to cap copied) and the (offset, length) ranges of it that hold device pointers
+    #[allow(dead_code)] fn tw_debug_policy_image(policy: *mut c_void, out: *mut c_void, cap: u64, bytes: *mut u64, ptr_ranges: *mut u64, range_cap: u32,
+                                                 n_ranges: *mut u32) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {

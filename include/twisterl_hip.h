@@ -134,6 +134,14 @@ int tw_debug_last_launch(tw_launch_info *out);
  * device, attempt a of episode e at index e * num_searches + a -- what the best-of-num_searches reduction and the two means are
  * taken from.  *n: the number of attempts; up to cap of them are copied to each array that is not NULL. */
 int tw_debug_last_attempts(float *success, float *total, uint32_t *n_steps, uint64_t cap, uint64_t *n);
+/* Test hook: the device image of a policy (the one allocation that holds every weight image the kernels read), as it stands once the
+ * calling thread's library stream has finished.  *bytes: its full size; up to cap bytes of it are copied to out (host).  *n_ranges: how
+ * many byte ranges of the image hold device pointers -- the layer table of a stack of any depth, three per layer; none in the image of
+ * the one-common-layer shape -- and up to range_cap of them go to ptr_ranges as (offset, length) pairs.  Outside those ranges two
+ * policies of the same shape and weights have the same image, however each came by its weights (tw_policy_create,
+ * tw_policy_update_device, tw_policy_update_device_layers). */
+struct tw_policy;
+int tw_debug_policy_image(struct tw_policy *p, void *out, uint64_t cap, uint64_t *bytes, uint64_t *ptr_ranges, uint32_t range_cap, uint32_t *n_ranges);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Env: host object with the PyBaseEnv / Puzzle surface.  Collectors only read its          */

@@ -48,8 +48,8 @@ OTHER = {
     "compact_obs16_kernel": ("tw_rollout_big", "test_gpu_parity.py", "test_boards_of_17_to_64_cells_roll_out_on_the_device"),
     "policy_eval_kernel": ("tw_eval", "test_gpu_parity.py", "test_policy_evaluate_matches_oracle"),
     "policy_eval_generic_kernel": ("tw_eval", "test_gpu_parity.py", "test_policies_of_any_depth"),
-    "policy_sync_kernel": ("tw_sync", "test_gpu_parity.py", "test_policy_update_from_torch_equals_rebuilding"),
-    "policy_sync_generic_kernel": ("tw_sync", "test_gpu_parity.py", "test_policy_update_from_torch_for_any_depth"),
+    "policy_sync_kernel": ("tw_sync", "test_gpu_policy_sync.py", "test_synced_image_equals_the_host_built_image"),
+    "policy_sync_generic_kernel": ("tw_sync", "test_gpu_policy_sync.py", "test_synced_image_equals_the_host_built_image"),
     "onehot_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),
     "onehot_scatter_kernel": ("tw_trainer", "test_gpu_trainer_handoff.py", "test_one_hot_of_ids_that_follow_no_layout"),
     "onehot4_kernel<8>": ("tw_trainer", "test_gpu_parity.py", "test_trainer_one_hot_of_boards_whose_cells_own_multiples_of_four_ids"),

@@ -17,8 +17,13 @@ def puzzle_transpose_twist(n):
 def make_policy_arrays(n2, seed=0, emb=512, hidden=256, n_actions=4, scale=1.0):
     """Synthetic BasicPolicy weights in the reference's export layout
     (src/twisterl/nn/utils.py:17-79): torch.nn.Linear default init U(-1/sqrt(fan_in), ..)."""
+    return make_policy_arrays_obs(n2 * n2, seed=seed, emb=emb, hidden=hidden, n_actions=n_actions, scale=scale)
+
+
+def make_policy_arrays_obs(obs_size, seed=0, emb=512, hidden=256, n_actions=4, scale=1.0):
+    """make_policy_arrays over any obs_size (not only a square of a square) and any number of actions: the same draws in the
+    same order."""
     rng = np.random.default_rng(seed)
-    obs_size = n2 * n2
 
     def lin(i, o):
         b = scale / np.sqrt(i)

@@ -125,6 +125,7 @@ SYMBOLS = {
     "tw_debug_last_launch": (C.c_int, [C.POINTER(LaunchInfo)]),
     "tw_debug_last_attempts": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]),
     "tw_debug_episode_order": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "tw_debug_policy_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     "tw_puzzle_create": (_VP, [C.c_uint32] * 5),
     "tw_puzzle_clone": (_VP, [_VP]),
     "tw_puzzle_destroy": (None, [_VP]),
@@ -305,6 +306,20 @@ def debug_episode_order(desc, seed: int, episode_offset: int, n: int):
     check(lib().tw_debug_episode_order(C.byref(desc), seed, episode_offset, n, boards.ctypes.data_as(C.POINTER(C.c_uint64)),
                                        order.ctypes.data_as(C.POINTER(C.c_uint32))))
     return boards, order
+
+
+def debug_policy_image(policy):
+    """(image, ptr_ranges) of a twisterl_amd.nn.Policy (tw_debug_policy_image; test hook): its device image as a uint8 array, read
+    once the library's stream has finished, and the (offset, length) byte ranges of it that hold device pointers -- the layer table
+    of a stack of any depth; none for the one-common-layer shape."""
+    import numpy as np
+    h = policy._handle()
+    size, n = C.c_uint64(), C.c_uint32()
+    check(lib().tw_debug_policy_image(h, None, 0, C.byref(size), None, 0, C.byref(n)))
+    img, ranges = np.zeros(size.value, dtype=np.uint8), np.zeros((max(n.value, 1), 2), dtype=np.uint64)
+    check(lib().tw_debug_policy_image(h, img.ctypes.data_as(C.c_void_p), size.value, C.byref(size), ranges.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      n.value, C.byref(n)))
+    return img, [(int(o), int(b)) for o, b in ranges[:n.value]]
 
 
 def release_cached_memory() -> None:

@@ -931,6 +931,28 @@ extern "C" void tw_policy_destroy(tw_policy *p)
 extern "C" uint32_t tw_policy_num_actions(const tw_policy *p) { return p ? (uint32_t)p->dev.n_actions : 0; }
 extern "C" uint32_t tw_policy_num_perms(const tw_policy *p) { return p ? (uint32_t)p->dev.n_perms : 0; }
 
+// tw_debug_policy_image (test hook): the arena as the kernels read it, after whatever the library's stream still had to write to it
+extern "C" int tw_debug_policy_image(tw_policy *p, void *out, uint64_t cap, uint64_t *bytes, uint64_t *ptr_ranges, uint32_t range_cap, uint32_t *n_ranges)
+{
+    if (!p || !bytes || !n_ranges || (cap && !out) || (range_cap && !ptr_ranges)) { set_error("tw_debug_policy_image: null argument"); return TW_ERR_INVALID; }
+    int rc = require_device(); if (rc) return rc;
+    if (!p->arena) { set_error("policy: no device image"); return TW_ERR_INVALID; }
+    TW_HIP(hipStreamSynchronize(current_stream()));
+    *bytes = (uint64_t)p->arena_bytes;
+    const size_t take = cap < (uint64_t)p->arena_bytes ? (size_t)cap : p->arena_bytes;
+    if (take) TW_HIP(hipMemcpy(out, p->arena, take, hipMemcpyDeviceToHost));
+    uint32_t n = 0;
+    if (p->dev.generic && !p->gen_layers.empty()) {     // the layer table's three pointers per layer; the one-common-layer image holds none
+        const uint64_t tab = (uint64_t)(reinterpret_cast<const uint8_t *>(p->dev.layers) - reinterpret_cast<const uint8_t *>(p->arena));
+        const size_t field[3] = {offsetof(LayerDev, w), offsetof(LayerDev, b), offsetof(LayerDev, wm)};
+        for (size_t l = 0; l < p->gen_layers.size(); ++l)
+            for (int f = 0; f < 3; ++f, ++n)
+                if (n < range_cap) { ptr_ranges[2 * n] = tab + l * sizeof(LayerDev) + field[f]; ptr_ranges[2 * n + 1] = sizeof(const float *); }
+    }
+    *n_ranges = n;
+    return TW_OK;
+}
+
 extern "C" int tw_policy_evaluate(const tw_policy *p, int mode, uint32_t precision, const int32_t *obs, uint32_t n,
                                   uint32_t n_obs, const uint8_t *masks, const int32_t *perms, float *out_actions,
                                   float *out_values)
