@@ -84,6 +84,10 @@ use crate::rl::env::Env;
 #[repr(C)] #[derive(Default)] pub struct TwLaunchInfo { family: i32, nt: i32, nc: i32, nw: i32, nwk: i32, persist: u32, solve: u32, dec: u32, split: u32,
                                                         blocks: u32, threads: u32, engine_blocks: u32, engine_threads: u32 }
 
+// a diagnostic launch override (tw_set_launch_option): the hand-over of the persistent 256-episode f32 rollout -- 0 automatic,
+// 1 .. 256 = the live episodes per workgroup at which it leaves them to the drain launch, -1 none
+#[allow(dead_code)] const TW_OPT_ROLLOUT_DRAIN: c_int = 9;
+
 // fields of the result (TW_F_*)
 const F_OBS: c_int = 0; const F_LOGITS: c_int = 1; const F_PERMS: c_int = 2; const F_VALUES: c_int = 3; const F_REWARDS: c_int = 4;
 const F_ACTIONS: c_int = 5; const F_ADVS: c_int = 6; const F_RETS: c_int = 7; const F_REMAINING: c_int = 8;

@@ -93,6 +93,11 @@ enum {
     TW_OPT_ROLLOUT_REUSE = 8, /* PPO rollout, 256-episode f32 shape: 0 (default) a step whose board and twist the episode     */
                             /* recorded 2 or 4 steps ago takes that record's logits and value (the same bits) instead of a */
                             /* forward; 1: every record comes out of a forward (no look-ups).  (7 is not assigned.)        */
+    TW_OPT_ROLLOUT_DRAIN = 9, /* PPO rollout, persistent 256-episode f32 shape (hidden >= 128): once the episode queue is dry  */
+                            /* and at most N episodes of a workgroup still run, the workgroup leaves them to a second launch */
+                            /* of the 32-episode shape on the same stream (the same bytes).  N = 1 .. 256; 0: automatic;     */
+                            /* -1: no hand-over; anything else is refused with TW_ERR_INVALID.  tw_debug_counters after an   */
+                            /* f32 tw_ppo_collect: [0] the episodes handed over, [1] the second launch's workgroups (0: none) */
     TW_OPT_AZ_VARIANT = 2   /* self-play with few deep searches: 0 automatic (walker-per-wave kernel where it applies),    */
                             /* 2 always the lane-per-episode kernel; walker kernel with a pinned shape: 3 / 4 / 5 / 6 =    */
                             /* two / one / four / eight walkers per workgroup, + 16 / + 32 = the 16- / 32-column engine,   */
@@ -104,7 +109,8 @@ enum {
                             /*        + 2048 (test hook) launches the split shape's two kernels one after the other        */
 };
 int tw_set_launch_option(int option, int value);
-/* Diagnostic counters of the last self-play launch of this process (MctsArgs::eval_count[0..15]); test hook. */
+/* Diagnostic counters of the last self-play launch of this process (MctsArgs::eval_count[0..15]), or of its last f32
+ * tw_ppo_collect (TW_OPT_ROLLOUT_DRAIN: two counters, the rest 0), whichever came later; test hook. */
 int tw_debug_counters(uint64_t *out, int n);
 /* Test hook: the kernel the last tw_az_collect / tw_evaluate / tw_solve / big-board tw_ppo_collect / one-hot hand-off
  * (tw_collected_pack_trainer) / tw_ppo_collect_device_env / tw_az_collect_device_env / tw_evaluate_device_env of this process launched, as its

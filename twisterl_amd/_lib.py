@@ -18,6 +18,7 @@ TW_EVAL_FORWARD, TW_EVAL_PREDICT, TW_EVAL_FULL_PREDICT = 0, 1, 2
 TW_OPT_FORCE_GEOM, TW_OPT_NO_PERSIST, TW_OPT_AZ_VARIANT, TW_OPT_AZ_TREE_BUDGET, TW_OPT_AZ_TREE_BUDGET_MIN, TW_OPT_AZ_REUSE = 0, 1, 2, 3, 4, 5
 TW_OPT_ENV_RESIDENT_GROUPS = 6
 TW_OPT_ROLLOUT_REUSE = 8       # (7 stays unassigned: tw_set_launch_option refuses it)
+TW_OPT_ROLLOUT_DRAIN = 9       # hand-over of the persistent 256-episode f32 rollout: 0 automatic, 1 .. 256 live episodes, -1 off
 ABI_VERSION = 6
 (TW_F_OBS, TW_F_LOGITS, TW_F_PERMS, TW_F_VALUES, TW_F_REWARDS, TW_F_ACTIONS, TW_F_ADVS, TW_F_RETS,
  TW_F_REMAINING, TW_F_EP_LEN, TW_F_EP_START, TW_F_COUNT) = range(12)
@@ -270,7 +271,8 @@ class launch_option:
 
 
 def debug_counters(n: int = 16) -> list:
-    """Diagnostic counters of this process's last self-play launch (tw_debug_counters)."""
+    """Diagnostic counters of this process's last self-play launch (tw_debug_counters); after an f32 PPO collect: [0] the episodes
+    the persistent 256-episode launch handed over, [1] the workgroups of the drain launch (TW_OPT_ROLLOUT_DRAIN), the rest 0."""
     buf = (C.c_uint64 * n)()
     check(lib().tw_debug_counters(buf, n))
     return [int(x) for x in buf]

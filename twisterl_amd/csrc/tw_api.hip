@@ -46,8 +46,8 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
 hipStream_t current_stream() { return g_stream; }
 
 // ---------------------------------------------------------------------------------- launch options / per-device caches
-static std::atomic<int> g_force_geom{0}, g_no_persist{0}, g_az_variant{0}, g_az_tree_budget{0}, g_az_tree_budget_min{0}, g_az_reuse{0}, g_env_resident_groups{0}, g_rollout_reuse_off{0};
-LaunchOptions launch_options() { return LaunchOptions{g_force_geom.load(), g_no_persist.load(), g_az_variant.load(), g_az_tree_budget.load(), g_az_tree_budget_min.load(), g_az_reuse.load(), g_env_resident_groups.load(), g_rollout_reuse_off.load()}; }
+static std::atomic<int> g_force_geom{0}, g_no_persist{0}, g_az_variant{0}, g_az_tree_budget{0}, g_az_tree_budget_min{0}, g_az_reuse{0}, g_env_resident_groups{0}, g_rollout_reuse_off{0}, g_rollout_drain{0};
+LaunchOptions launch_options() { return LaunchOptions{g_force_geom.load(), g_no_persist.load(), g_az_variant.load(), g_az_tree_budget.load(), g_az_tree_budget_min.load(), g_az_reuse.load(), g_env_resident_groups.load(), g_rollout_reuse_off.load(), g_rollout_drain.load()}; }
 // counters of the last self-play launch (eval_count[0..15], see MctsArgs): tw_debug_counters
 static std::mutex g_dbg_mutex;
 static unsigned long long g_dbg_counters[16];
@@ -260,6 +260,9 @@ extern "C" int tw_set_launch_option(int option, int value)
             if (value < 0 || value > 4 || value == 2) { set_error("TW_OPT_AZ_REUSE: value %d not in {0, 1, 3, 4}", value); return TW_ERR_INVALID; }
             g_az_reuse.store(value); return TW_OK;
         case TW_OPT_ROLLOUT_REUSE: g_rollout_reuse_off.store(value ? 1 : 0); return TW_OK;
+        case TW_OPT_ROLLOUT_DRAIN:
+            if (value < -1 || value > 256) { set_error("TW_OPT_ROLLOUT_DRAIN: %d live episodes (0 = automatic, -1 = no hand-over, else 1 .. 256)", value); return TW_ERR_INVALID; }
+            g_rollout_drain.store(value); return TW_OK;
         case TW_OPT_ENV_RESIDENT_GROUPS:
             if (value < 0) { set_error("TW_OPT_ENV_RESIDENT_GROUPS: %d workgroups (0 = automatic, else > 0)", value); return TW_ERR_INVALID; }
             g_env_resident_groups.store(value); return TW_OK;
@@ -1404,7 +1407,21 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
                             : prm->precision == TW_PREC_F32_EXACT ? f32_resident_episodes(E, (int)ra.pol.hidden, false, ra.reserve_cus)
                                                                   : rollout_f32_resident_episodes(ra.reserve_cus);
     const bool persist = E > resident && !launch_options().no_persist && !big;
-    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(16),     // (+8: range_flag, +12: RolloutArgs::reused)
+    // Hand-over of the persistent 256-episode shape (RolloutArgs::resume): TW_OPT_ROLLOUT_DRAIN, or automatically where the queue
+    // holds at least as many episodes as the lanes took at launch -- below that the launch is over soon after the queue is dry, the
+    // lanes' episodes are of one age and end together, and there is no long tail of a few columns to take away
+    // (profiles/r14_rollout_drain.txt).
+    // (96: the smallest threshold of the plateau measured over {32, 64, 96, 128, 160} -- it leaves the most steps to the shape that
+    //  has the fast-forward rounds)
+    constexpr uint32_t ROLLOUT_DRAIN_LIVE_AUTO = 96;
+    uint32_t drain_live = 0;
+    if (persist && prm->precision == TW_PREC_F32_EXACT && rollout_f32_hands_over(ra.pol, resident, ra.reserve_cus)) {
+        const int opt = launch_options().rollout_drain;
+        drain_live = opt > 0 ? (uint32_t)opt : (opt == 0 && E >= 2 * resident ? ROLLOUT_DRAIN_LIVE_AUTO : 0u);
+    }
+    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8),
+                 o_total = seg(32),     // (+8: range_flag, +12: RolloutArgs::reused, +16: resume_cnt, +20: drain_queue)
+                 o_resume = seg(drain_live ? resident * 16 : 0),
                  o_scan = seg(scan_scratch_bytes(E)), o_init = seg(persist ? E * 16 : 0), o_queue = seg(persist ? 4 : 0),
                  o_obs16 = seg(big ? R * cells * 2 : 0), o_boards = seg(persist ? E * 8 : 0), o_ordscr = seg(persist ? episode_order_scratch_bytes(E) : 0);
     void *wsp = nullptr;
@@ -1419,7 +1436,7 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
     tw_collect_stats st{};
     const bool reuse_path = prm->precision == TW_PREC_F32_EXACT && !big && !ra.pol.generic;    // the launches that can take the 256-episode f32 shape
     if (reuse_path) {
-        TW_HIP(hipMemsetAsync(ws + o_total + 8, 0, 8, s));
+        TW_HIP(hipMemsetAsync(ws + o_total + 8, 0, 12, s));                      // (range_flag, reused, resume_cnt)
         ra.reused = reinterpret_cast<unsigned int *>(ws + o_total + 12);
         ra.reuse_off = launch_options().rollout_reuse_off ? 1u : 0u;
     }
@@ -1432,6 +1449,14 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
         ra.queue = reinterpret_cast<unsigned int *>(ws + o_queue);
         const unsigned int first = (unsigned int)resident;      // episodes handed out at launch
         TW_HIP(hipMemcpyAsync(ws + o_queue, &first, 4, hipMemcpyHostToDevice, s));
+        if (drain_live) {                                       // (every word of it reset on the stream, every collect)
+            ra.resume = reinterpret_cast<uint4 *>(ws + o_resume);
+            ra.resume_cnt = reinterpret_cast<unsigned int *>(ws + o_total + 16);
+            ra.drain_queue = reinterpret_cast<unsigned int *>(ws + o_total + 20);
+            ra.drain_live = drain_live;
+            const unsigned int drain_first = (unsigned int)(resident / 8);      // the drain's lanes: 32 per workgroup of the same grid
+            TW_HIP(hipMemcpyAsync(ra.drain_queue, &drain_first, 4, hipMemcpyHostToDevice, s));
+        }
         // the lanes take the episodes longest-looking first (as the self-play walkers do): with a policy that solves the puzzle an episode
         // is about as long as its start board is far from the solved one, and the collect ends with its last long episode -- trained
         // Puzzle-8 policy, 262,144 envs: D = 32 12.2 -> 11.5 ms, D = 12 4.85 -> 3.36 ms; 1,048,576 envs 25.2 -> 22.8 ms
@@ -1447,18 +1472,24 @@ static int ppo_collect_once(const tw_puzzle_desc *env, const tw_policy *policy, 
     }
     TW_HIP(hipEventRecord(ev.ev[0], s));
     if (big) forget_last_launch();         // (tw_debug_last_launch: launch_rollout_big reports itself)
+    uint32_t drain_blocks = 0;
     rc = big                               ? launch_rollout_big(ra, reinterpret_cast<uint16_t *>(ws + o_obs16), s, &st.rollout_blocks, &st.rollout_threads)
          : prm->precision == TW_PREC_F16   ? launch_rollout_f16(ra, s, &st.rollout_blocks, &st.rollout_threads)
          : prm->precision == TW_PREC_F16X2 ? launch_rollout_f16x2(ra, s, &st.rollout_blocks, &st.rollout_threads)
-                                           : launch_rollout_f32(ra, s, &st.rollout_blocks, &st.rollout_threads);
+                                           : launch_rollout_f32(ra, s, &st.rollout_blocks, &st.rollout_threads, &drain_blocks);
     if (rc) return rc;
     TW_HIP(hipEventRecord(ev.ev[1], s));
     rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;
     TW_HIP(hipEventRecord(ev.ev[2], s));
-    uint64_t total_and_flag[2] = {0, 0};          // {record count, range_flag | reused << 32}: one copy
-    TW_HIP(hipMemcpyAsync(total_and_flag, total_d, ra.range_flag || ra.reused ? 16 : 8, hipMemcpyDeviceToHost, s));
+    uint64_t total_and_flag[3] = {0, 0, 0};       // {record count, range_flag | reused << 32, resume_cnt | drain_queue << 32}: one copy
+    TW_HIP(hipMemcpyAsync(total_and_flag, total_d, ra.drain_live ? 24 : ra.range_flag || ra.reused ? 16 : 8, hipMemcpyDeviceToHost, s));
     TW_HIP(hipStreamSynchronize(s));
+    if (reuse_path) {                             // tw_debug_counters after an f32 PPO collect: [0] episodes handed over, [1] the drain's grid
+        std::lock_guard<std::mutex> dbg(g_dbg_mutex);
+        for (int i = 0; i < 16; ++i) g_dbg_counters[i] = 0;
+        g_dbg_counters[0] = total_and_flag[2] & 0xffffffffull; g_dbg_counters[1] = drain_blocks;
+    }
     const uint64_t total = total_and_flag[0];
     if (total_and_flag[1] & 0xffffffffull) {
         *out_of_range = true;

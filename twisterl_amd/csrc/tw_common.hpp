@@ -113,7 +113,7 @@ int  hip_fail(hipError_t e, const char *what, const char *file, int line);
 hipStream_t current_stream();
 
 // Diagnostic launch overrides (tw_set_launch_option; the tests pin launch shapes with them).  Read once per collect.
-struct LaunchOptions { int force_geom; int no_persist; int az_variant; int az_tree_budget; int az_tree_budget_min; int az_reuse; int env_resident_groups; int rollout_reuse_off; };
+struct LaunchOptions { int force_geom; int no_persist; int az_variant; int az_tree_budget; int az_tree_budget_min; int az_reuse; int env_resident_groups; int rollout_reuse_off; int rollout_drain; };
 LaunchOptions launch_options();
 // Raises a kernel's dynamic-LDS limit above the 64 KiB default; cached per (kernel, device), thread-safe.
 int ensure_dynamic_lds(const void *kernel, size_t bytes);
@@ -539,8 +539,17 @@ struct RolloutArgs {
     // launch; one atomic per wave at the kernel's end); reuse_off != 0 (TW_OPT_ROLLOUT_REUSE = 1): no look-ups at all.
     unsigned int   *reused;
     uint32_t        reuse_off;
+    // 256-episode persistent f32 shape, hand-over: once the queue is dry and at most `drain_live` episodes of a
+    // workgroup are still running, every live writer lane appends {board lo, hi, episode, t} to `resume` (one atomicAdd on
+    // `resume_cnt`, one 16-byte store) and the workgroup ends; a second launch of the 32-episode persistent shape, on the same
+    // stream, takes `resume` as its init_boards and reads its episode count from the device (`num_episodes_dev` = the first
+    // launch's resume_cnt: the host never waits between the two).  drain_live == 0: no hand-over.
+    uint4              *resume;            // [resident lanes of the first launch]
+    unsigned int       *resume_cnt;        // zeroed before the launch
+    unsigned int       *drain_queue;       // the second launch's queue word (starts at that launch's resident lanes)
+    uint32_t            drain_live;
+    const unsigned int *num_episodes_dev;  // second launch only (read by the <NT, NC, -4, true> instantiation): entries of init_boards
 };
-
 // Waves per workgroup of the f32 engine for a batch of n columns (episodes / attempts): 8 (two per SIMD, 256 columns) is
 // the throughput geometry.  Below ~40k columns the small-batch geometries win (measured crossover of the rollout,
 // scripts/geom_sweep.py): 32 columns per workgroup -- shared by four waves that split the hidden units (Engine3S,
@@ -553,7 +562,8 @@ inline int waves_per_group(uint64_t n)
 }
 
 // kernel launchers (each returns a TW_* status)
-int launch_rollout_f32(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads);
+int launch_rollout_f32(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads, uint32_t *drain_blocks = nullptr);   // drain_blocks: grid of the hand-over's second launch (0: none)
+bool rollout_f32_hands_over(const PolicyDev &pol, uint64_t resident, int reserve_cus);   // the launch of more than `resident` episodes is the 256-episode persistent shape and has a drain shape
 uint64_t rollout_generic_resident_episodes(const PolicyDev &pol, int n_cells, int reserve_cus);   // generic stacks: episodes in flight in the persistent launch
 // boards of 17 .. 25 cells (tw_rollout_big.hip): obs ids as uint16 in their own padded array [E][t_pad][n_cells]
 int launch_rollout_big(const RolloutArgs &a, uint16_t *obs16, hipStream_t s, uint32_t *blocks, uint32_t *threads);

@@ -186,9 +186,17 @@ TW_STAMP_ARRAY(g_gen_stamps, 8);   // cycle stamps of the generic engine and the
 // 256-episode shape (`lg` and `value` come out of one of the episode's own records: act-permuted and masked already): reward,
 // Gumbel arg-max, the record, is_final / step, and in persistent mode the next episode off the queue.  `on`: this lane takes the
 // step (the forwarded step: every lane; a round: the lanes that hit).
+// entries of RolloutArgs::init_boards: the drain launch of a hand-over (the <NT, NC, -4, true> shape) reads the count the first launch left
+template <int NW>
+__device__ __forceinline__ uint64_t queue_entries(const RolloutArgs &a)
+{
+    if constexpr (NW == -4) { if (a.num_episodes_dev) return (uint64_t)*a.num_episodes_dev; }
+    return a.num_episodes;
+}
+
 template <int NW, bool PERSIST, bool RAW, class Eng>
 __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleConsts &env, const Eng &eng, bool writer, bool on, int perm, float (&lg)[4], float value,
-                                          uint32_t &e_local, uint64_t &board, int &depth, int &t, bool &alive, bool &more)
+                                          uint32_t &e_local, uint64_t &board, int &depth, int &t, bool &alive, bool &more, unsigned *wg_words = nullptr)
 {
     const int j = eng.j, h = eng.h;
     PuzzleLane st; st.board = board; st.depth = depth;
@@ -229,11 +237,15 @@ __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleCons
             got = bc[j];
         } else got = (unsigned)__shfl((int)got, j, 64);
         if (want) {
-            if ((uint64_t)got < a.num_episodes) {
-                const uint4 ib = a.init_boards[got];
-                e_local = ib.z; board = ((uint64_t)ib.y << 32) | ib.x; depth = env.depth0;
-                alive = true; t = 0;
-            } else more = false;
+            if ((uint64_t)got < queue_entries<NW>(a)) {
+                const uint4 ib = a.init_boards[got];          // (w: the step the episode is at -- 0, or where a hand-over left it)
+                e_local = ib.z; board = ((uint64_t)ib.y << 32) | ib.x; t = (int)ib.w;
+                depth = env.depth0 > t ? env.depth0 - t : 0;
+                alive = true;
+            } else {
+                more = false;
+                if constexpr (NW == 8) { if (writer) wg_words[1] = 1u; }     // the queue never refills: from here on the workgroup only drains
+            }
         }
     }
 }
@@ -247,6 +259,29 @@ __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleCons
 #define TW_REUSE_R 2
 #endif
 constexpr int REUSE_LB = TW_REUSE_LB, REUSE_R = TW_REUSE_R;
+
+// -DTW_DRAIN_ANATOMY (a TW_VARIANT build; TW_STAMPS=1 prints): per workgroup of the persistent 256-episode shape, the iteration at
+// which the queue was dry, at which 128 / 64 / 32 or fewer episodes lived, and the last one (profiles/r14_rollout_drain.txt).
+// Thread 0 alone keeps the iteration count and the events seen in the two spare LDS words behind the reuse counter.
+#ifdef TW_DRAIN_ANATOMY
+__device__ unsigned g_drain_anat[1024 * 8];
+#define TW_DRAIN_ANATOMY_INIT(w) do { (w)[2] = 0u; (w)[3] = 0u; } while (0)
+#define TW_DRAIN_ANATOMY_STEP(w, live, wg)                                                                              \
+    do {                                                                                                                \
+        if (threadIdx.x == 0 && (wg) < 1024u) {                                                                         \
+            const unsigned it_ = (w)[2]++; unsigned seen_ = (w)[3]; unsigned *o_ = g_drain_anat + 8u * (wg);            \
+            if (!(seen_ & 1u) && (w)[1]) { o_[0] = it_; seen_ |= 1u; }                                                  \
+            if (!(seen_ & 2u) && (live) <= 128u) { o_[1] = it_; seen_ |= 2u; }                                          \
+            if (!(seen_ & 4u) && (live) <= 64u) { o_[2] = it_; seen_ |= 4u; }                                           \
+            if (!(seen_ & 8u) && (live) <= 32u) { o_[3] = it_; seen_ |= 8u; }                                           \
+            o_[4] = it_; o_[5] = (live);                                                                                \
+            (w)[3] = seen_;                                                                                             \
+        }                                                                                                               \
+    } while (0)
+#else
+#define TW_DRAIN_ANATOMY_INIT(w) do {} while (0)
+#define TW_DRAIN_ANATOMY_STEP(w, live, wg) do {} while (0)
+#endif
 
 // (the generic engine's workgroups are small -- 256 threads, exact-size activation buffers: two of them share a CU, and while one
 //  gathers its embeddings from L2 the other one keeps the matrix cores busy)
@@ -264,21 +299,22 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
     // global episode index, record address, obs-id constants) is recomputed after the forward -- held across it, those were the
     // registers the 8-wave x 256-accumulator shape spilled to scratch.
     const uint64_t e_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)eng.ep_lane();
-    const bool valid  = e_first < a.num_episodes;
+    const bool valid  = e_first < (PERSIST ? queue_entries<NW>(a) : a.num_episodes);
     const bool writer = h == 0 && eng.primary();          // the lane that stores the episode's records
     uint32_t e_local = (uint32_t)e_first;                 // (launch_geom bounds the episode count of a launch to 2^31)
     uint64_t board = env.ident; int depth = 0;
+    int      t = 0;                                       // (stays at the last record once the episode is over: records = t + 1)
     if (valid) {
         if constexpr (PERSIST) {              // the episode and its start board from the pre-pass (RolloutArgs::init_boards: in the order the lanes take them)
             const uint4 ib = a.init_boards[e_local];
-            e_local = ib.z; board = ((uint64_t)ib.y << 32) | ib.x; depth = env.depth0;
+            e_local = ib.z; board = ((uint64_t)ib.y << 32) | ib.x; t = (int)ib.w;
+            depth = env.depth0 > t ? env.depth0 - t : 0;
         }
         else { PuzzleLane s0; puzzle_reset(s0, env, a.seed, a.episode_offset + e_first); board = s0.board; depth = s0.depth; }
     }
 
     bool     alive = valid;
     bool     more  = PERSIST;                             // the queue may still hold episodes
-    int      t = 0;                                       // (stays at the last record once the episode is over: records = t + 1)
 
     eng.begin2();
     // (the barrier inside __syncthreads_or publishes the first two ring slots and the LDS constants)
@@ -286,10 +322,25 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
     TW_STAMP_VARS(n_fwd = 0);
     // records taken from the trajectory: counted in one LDS word behind the engine's image (launch_geom adds it) -- a counter
     // in a register would be live across the forward, which has none to spare
+    // ([1]: "the queue is dry", set by whichever lane finds it so in step_tail)
     unsigned *reuse_cnt = nullptr;
-    if constexpr (NW == 8) { reuse_cnt = reinterpret_cast<unsigned *>(lds + Eng::lds_floats(a.pol)); if (threadIdx.x == 0) *reuse_cnt = 0u; }
+    if constexpr (NW == 8) { reuse_cnt = reinterpret_cast<unsigned *>(lds + Eng::lds_floats(a.pol)); if (threadIdx.x == 0) { reuse_cnt[0] = 0u; reuse_cnt[1] = 0u; TW_DRAIN_ANATOMY_INIT(reuse_cnt); } }
 
-    while (__syncthreads_or(alive ? 1 : 0)) {
+    // The loop runs while an episode of the workgroup lives.  Persistent 256-episode shape: the same barrier counts them, and once
+    // the queue is dry and no more than drain_live are left the workgroup hands them over instead of running 256-column forwards
+    // for a handful of columns (RolloutArgs::resume; the flag was stored before this barrier, and the next store to it lies behind
+    // the forward's barriers).  Exit plus stream order: nothing waits.
+    auto go_on = [&]() -> bool {
+        if constexpr (NW == 8 && PERSIST) {
+            const unsigned live = (unsigned)__syncthreads_count(alive && writer ? 1 : 0);
+            TW_DRAIN_ANATOMY_STEP(reuse_cnt, live, blockIdx.x);
+            if (live == 0u) return false;
+            if (live > a.drain_live || !*(volatile unsigned *)(reuse_cnt + 1)) return true;
+            if (alive && writer) a.resume[atomicAdd(a.resume_cnt, 1u)] = make_uint4((uint32_t)board, (uint32_t)(board >> 32), e_local, (uint32_t)t);
+            return false;
+        } else return __syncthreads_or(alive ? 1 : 0) != 0;
+    };
+    while (go_on()) {
         TW_STAMP_COUNT(n_fwd, 1);
         // ---- observe (puzzle.rs:183-185) + twist of the obs ids (policy.rs:67-83) -------------
         int perm = -1;
@@ -303,7 +354,7 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
         float lg[4]; float value;
         eng.forward(rowoff, lg, value);
 
-        step_tail<NW, PERSIST, true>(a, env, eng, writer, true, perm, lg, value, e_local, board, depth, t, alive, more);
+        step_tail<NW, PERSIST, true>(a, env, eng, writer, true, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt);
 
         // ---- fast-forward rounds: a step whose (board, perm) the episode recorded 2k steps ago takes that record's output -----
         if constexpr (NW == 8) {
@@ -340,7 +391,7 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
                     lg[0] = __uint_as_float(low(hl.x)); lg[1] = __uint_as_float(low(hl.y));
                     lg[2] = __uint_as_float(low(hl.z)); lg[3] = __uint_as_float(low(hl.w));
                     value = __uint_as_float(low(hv));
-                    step_tail<NW, PERSIST, false>(a, env, eng, writer, on, perm, lg, value, e_local, board, depth, t, alive, more);
+                    step_tail<NW, PERSIST, false>(a, env, eng, writer, on, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt);
                 }
             }
         }
@@ -420,13 +471,35 @@ static int launch_geom(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, ui
                     NW, (double)g[0] / g[5], (double)g[1] / g[5], (double)g[4] / g[5], (double)g[6] / g[5], g[5]);
     });
     TW_HIP(hipGetLastError());
+#ifdef TW_DRAIN_ANATOMY
+    if constexpr (NW == 8 && PERSIST) {
+        if (getenv("TW_STAMPS") && nb <= 1024) {
+            static unsigned h[1024 * 8];
+            TW_HIP(hipStreamSynchronize(s));
+            TW_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_drain_anat), sizeof(h)));
+            static const char *what[6] = {"queue dry", "live <= 128", "live <= 64", "live <= 32", "last", "live at last"};
+            for (int k = 0; k < 6; ++k) {
+                double sum = 0; unsigned lo = ~0u, hi = 0;
+                for (uint64_t b = 0; b < nb; ++b) { const unsigned v = h[8 * b + k]; sum += v; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
+                fprintf(stderr, "[drain anatomy, %llu workgroups, iteration] %-12s mean %.1f min %u max %u\n", (unsigned long long)nb, what[k], sum / (double)nb, lo, hi);
+            }
+        }
+    }
+#endif
     if (blocks) *blocks = (uint32_t)nb;
     if (threads) *threads = THREADS;
     return TW_OK;
 }
 
+// The launch of more than `resident` episodes is the persistent 256-episode shape, and the policy has the 32-episode shape the
+// hand-over drains into (hidden >= 128).
+bool rollout_f32_hands_over(const PolicyDev &pol, uint64_t resident, int reserve_cus)
+{
+    return !pol.generic && pol.hidden >= 128 && resident == rollout_f32_resident_episodes(reserve_cus);
+}
+
 template <int NT, int NC>
-static int launch_one(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads)
+static int launch_one(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads, uint32_t *drain_blocks)
 {
     // small batches: fewer waves per workgroup, so that the episodes spread over more CUs
     const uint64_t resident = f32_resident_episodes(a.num_episodes, a.pol.hidden, false, a.reserve_cus);
@@ -435,7 +508,20 @@ static int launch_one(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uin
             const uint64_t full = rollout_f32_resident_episodes(a.reserve_cus);
             if (resident < full) return launch_geom<NT, NC, -4, true>(a, s, blocks, threads);
         }
-        return launch_geom<NT, NC, 8, true>(a, s, blocks, threads);
+        if (a.drain_live && (NT < 4 || !a.resume || !a.resume_cnt || !a.drain_queue)) { set_error("rollout: hand-over without a drain shape or its workspace"); return TW_ERR_INVALID; }
+        int rc = launch_geom<NT, NC, 8, true>(a, s, blocks, threads);
+        if constexpr (NT >= 4) {
+            // the drain: the 32-episode persistent shape over the episodes the workgroups above left in `resume`, right behind them on
+            // the stream; how many there are it reads on the device (an empty list: every lane leaves at its first barrier)
+            if (rc == TW_OK && a.drain_live) {
+                RolloutArgs d = a;
+                d.init_boards = a.resume; d.queue = a.drain_queue; d.num_episodes_dev = a.resume_cnt;
+                d.num_episodes = rollout_f32_resident_episodes(a.reserve_cus);          // (the list's capacity)
+                d.drain_live = 0; d.resume = nullptr; d.resume_cnt = nullptr; d.drain_queue = nullptr;
+                rc = launch_geom<NT, NC, -4, true>(d, s, drain_blocks, nullptr);
+            }
+        }
+        return rc;
     }
     const int nw = geometry_for<NT>(a.num_episodes);
     if constexpr (NT >= 4) { if (nw == -16) return launch_geom<NT, NC, -16>(a, s, blocks, threads); }
@@ -449,16 +535,17 @@ static int launch_one(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uin
 }
 
 template <int NT>
-static int launch_nt(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads)
+static int launch_nt(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads, uint32_t *drain_blocks)
 {
     const int nc = a.env.n_cells;
-    if (nc <= 4) return launch_one<NT, 4>(a, s, blocks, threads);
-    if (nc <= 9) return launch_one<NT, 9>(a, s, blocks, threads);
-    return launch_one<NT, 16>(a, s, blocks, threads);
+    if (nc <= 4) return launch_one<NT, 4>(a, s, blocks, threads, drain_blocks);
+    if (nc <= 9) return launch_one<NT, 9>(a, s, blocks, threads, drain_blocks);
+    return launch_one<NT, 16>(a, s, blocks, threads, drain_blocks);
 }
 
-int launch_rollout_f32(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads)
+int launch_rollout_f32(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, uint32_t *threads, uint32_t *drain_blocks)
 {
+    if (drain_blocks) *drain_blocks = 0;
     if (a.pol.generic) {          // any Sequential depth: the vector-ALU engine (tw_engine_generic.hpp); shapes validated by tw_policy_create
         if (a.env.n_cells < 1 || a.env.n_cells > 16 || a.pol.obs_size != a.env.n_cells * a.env.n_cells || a.pol.n_actions != 4 ||
             a.out.t_pad < a.env.depth0 + 1 || (a.queue == nullptr) != (a.init_boards == nullptr)) {
@@ -484,10 +571,10 @@ int launch_rollout_f32(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, ui
         return TW_ERR_UNSUPPORTED;
     }
     switch (a.pol.hidden) {
-        case 32:  return launch_nt<1>(a, s, blocks, threads);
-        case 64:  return launch_nt<2>(a, s, blocks, threads);
-        case 128: return launch_nt<4>(a, s, blocks, threads);
-        case 256: return launch_nt<8>(a, s, blocks, threads);
+        case 32:  return launch_nt<1>(a, s, blocks, threads, drain_blocks);
+        case 64:  return launch_nt<2>(a, s, blocks, threads, drain_blocks);
+        case 128: return launch_nt<4>(a, s, blocks, threads, drain_blocks);
+        case 256: return launch_nt<8>(a, s, blocks, threads, drain_blocks);
         default:
             set_error("rollout: hidden size %d not in {32,64,128,256}", a.pol.hidden);
             return TW_ERR_UNSUPPORTED;
