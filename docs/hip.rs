@@ -120,6 +120,9 @@ extern "C" {
     // test hook: a policy's device image (*bytes in all, up to cap copied) and the (offset, length) ranges of it that hold device pointers
     #[allow(dead_code)] fn tw_debug_policy_image(policy: *mut c_void, out: *mut c_void, cap: u64, bytes: *mut u64, ptr_ranges: *mut u64, range_cap: u32,
                                                  n_ranges: *mut u32) -> c_int;
+    // test hooks: the collectors' tail (scan, finalize, movers) on host records the caller wrote; a result's whole arena with its field offsets
+    #[allow(dead_code)] fn tw_debug_collect_tail(args: *const c_void, launched: *mut c_void, out: *mut *mut c_void) -> c_int;
+    #[allow(dead_code)] fn tw_debug_collected_arena(c: *const c_void, out: *mut c_void, cap: u64, bytes: *mut u64, offsets: *mut u64, scratch: *mut u64) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {

@@ -148,6 +148,42 @@ int tw_debug_last_attempts(float *success, float *total, uint32_t *n_steps, uint
  * tw_policy_update_device, tw_policy_update_device_layers). */
 struct tw_policy;
 int tw_debug_policy_image(struct tw_policy *p, void *out, uint64_t cap, uint64_t *bytes, uint64_t *ptr_ranges, uint32_t range_cap, uint32_t *n_ranges);
+/* Test hook: the tail of every device collector -- the episode-length scan, then finalize (GAE or remaining values + compaction), the
+ * obs and logits movers, ep_len / ep_start -- on records the CALLER wrote.  Everything in tw_debug_tail_args is host memory; the hook
+ * uploads it into the trajectory workspace, runs the scan and calls the collectors' own tail with the production kernels and launch
+ * rules.  *out: an ordinary result (tw_collected_free).  *launched (may be NULL): the finalize kernel the tail launched.
+ *   records   [E][t_pad] records of 48 bytes: 16 obs bytes | four float logits (AZ: probabilities) | float value | float reward |
+ *             uint32 action | perm << 8 | 4 bytes unused.  Records at and beyond ep_len[e] are padding: never read, never written out.
+ *   obs16     NULL: the obs ids are the first n_cells (1..16) bytes of the records; else [E][t_pad][n_cells] two-byte ids (n_cells
+ *             1..64), written out at obs_width = 1 or 2 bytes per id
+ *   wide      n_actions 5..31: the logits [E][t_pad][n_actions]; NULL for 1..4 (the records' columns, narrowed below 4)
+ *   arena_fill  not 0: the result's whole arena is set to this byte before anything is written to it (tw_debug_collected_arena)
+ *   scan_only not 0: only the scan runs; ep_start_out[E] and *total_out receive its output, ep_len may hold any value, no result
+ * Refused before anything is launched: E = 0, a length of 0 or above t_pad, n_cells / n_actions / obs_width outside the above
+ * (TW_ERR_INVALID); a t_pad beyond the finalize forms' LDS tiles (TW_ERR_UNSUPPORTED). */
+enum { TW_FIN_NONE = 0, TW_FIN_GROUP16 = 1, TW_FIN_GROUP8 = 2, TW_FIN_WAVE = 3, TW_FIN_AZ = 4 };
+typedef struct {
+    uint32_t form;              /* TW_FIN_*: finalize_ppo_group_kernel<16> / <8>, finalize_ppo_kernel, finalize_az_kernel */
+    uint32_t waves;             /* waves per workgroup                                           */
+    uint32_t blocks, threads;   /* the kernel's grid                                             */
+    uint64_t lds_bytes;         /* dynamic LDS of a workgroup                                    */
+} tw_finalize_launch;
+typedef struct {
+    uint64_t n_episodes;
+    uint32_t t_pad, is_ppo, n_cells, n_actions, obs_width, merge_order, scan_only, arena_fill;
+    float    gamma, lambda;
+    const uint32_t *ep_len;     /* [E]                                                           */
+    const void     *records;
+    const uint16_t *obs16;
+    const float    *wide;
+    uint64_t       *ep_start_out, *total_out;   /* scan_only                                     */
+} tw_debug_tail_args;
+struct tw_collected;
+int tw_debug_collect_tail(const tw_debug_tail_args *args, tw_finalize_launch *launched, struct tw_collected **out);
+/* Test hook: the whole arena of a result (*bytes in all, up to cap copied to out), gaps between and behind the fields included.
+ * offsets[TW_F_COUNT]: where each field starts in it (its length: tw_collected_device_ptr); scratch[2]: offset and length of the
+ * four-column logits the finalize kernel wrote behind the fields when the result has other than four columns (0, 0: none). */
+int tw_debug_collected_arena(const struct tw_collected *c, void *out, uint64_t cap, uint64_t *bytes, uint64_t *offsets, uint64_t *scratch);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Env: host object with the PyBaseEnv / Puzzle surface.  Collectors only read its          */

@@ -33,19 +33,19 @@ TOTAL_KERNELS = 331
 
 # The kernels that are no template family: name (with its integer template arguments, if any) -> (source file, GPU test file, test that launches it)
 OTHER = {
-    "scan_tile_sums": ("tw_finalize", "test_gpu_parity.py", "test_gae_and_compaction_in_each_of_its_forms"),
-    "scan_tile_offsets": ("tw_finalize", "test_gpu_parity.py", "test_gae_and_compaction_in_each_of_its_forms"),
-    "scan_write": ("tw_finalize", "test_gpu_parity.py", "test_gae_and_compaction_in_each_of_its_forms"),
-    "finalize_ppo_kernel": ("tw_finalize", "test_gpu_parity.py", "test_gae_and_compaction_in_each_of_its_forms"),
-    "finalize_ppo_group_kernel<16>": ("tw_finalize", "test_gpu_parity.py", "test_gae_and_compaction_in_each_of_its_forms"),
-    "finalize_ppo_group_kernel<8>": ("tw_finalize", "test_gpu_parity.py", "test_gae_and_compaction_in_each_of_its_forms"),
-    "finalize_az_kernel": ("tw_mcts", "test_gpu_parity.py", "test_az_collect_bit_exact_vs_oracle"),
+    "scan_tile_sums": ("tw_finalize", "test_gpu_finalize.py", "test_scan_offsets_and_total_are_exact"),
+    "scan_tile_offsets": ("tw_finalize", "test_gpu_finalize.py", "test_scan_offsets_and_total_are_exact"),
+    "scan_write": ("tw_finalize", "test_gpu_finalize.py", "test_scan_offsets_and_total_are_exact"),
+    "finalize_ppo_kernel": ("tw_finalize", "test_gpu_finalize.py", "test_every_form_on_both_sides_of_every_switch"),
+    "finalize_ppo_group_kernel<16>": ("tw_finalize", "test_gpu_finalize.py", "test_every_form_on_both_sides_of_every_switch"),
+    "finalize_ppo_group_kernel<8>": ("tw_finalize", "test_gpu_finalize.py", "test_every_form_on_both_sides_of_every_switch"),
+    "finalize_az_kernel": ("tw_mcts", "test_gpu_finalize.py", "test_az_horizons"),
     "split_gate_kernel": ("tw_mcts_deep", "test_gpu_parity.py", "test_split_walker_shape_bit_exact_vs_oracle"),
     "init_boards_kernel": ("tw_rollout", "test_gpu_parity.py", "test_persistent_lane_mode_bit_exact"),
     "episode_order_count_kernel": ("tw_rollout", "test_gpu_parity.py", "test_episode_order_is_a_stable_sort_by_manhattan_distance"),
     "episode_order_prefix_kernel": ("tw_rollout", "test_gpu_parity.py", "test_episode_order_is_a_stable_sort_by_manhattan_distance"),
     "episode_order_scatter_kernel": ("tw_rollout", "test_gpu_parity.py", "test_episode_order_is_a_stable_sort_by_manhattan_distance"),
-    "compact_obs16_kernel": ("tw_rollout_big", "test_gpu_parity.py", "test_boards_of_17_to_64_cells_roll_out_on_the_device"),
+    "compact_obs16_kernel": ("tw_rollout_big", "test_gpu_finalize.py", "test_every_form_on_both_sides_of_every_switch"),
     "policy_eval_kernel": ("tw_eval", "test_gpu_parity.py", "test_policy_evaluate_matches_oracle"),
     "policy_eval_generic_kernel": ("tw_eval", "test_gpu_parity.py", "test_policies_of_any_depth"),
     "policy_sync_kernel": ("tw_sync", "test_gpu_policy_sync.py", "test_synced_image_equals_the_host_built_image"),
@@ -56,8 +56,8 @@ OTHER = {
     "ppo_pack_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),
     "sum_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),
     "sum_partials_kernel": ("tw_trainer", "test_gpu_parity.py", "test_trainer_handoff_matches_reference_formulas"),
-    "compact_env_obs8_kernel": ("tw_device_env", "test_gpu_device_env.py", "test_gridworld_collect_equals_host_path_and_oracle"),
-    "narrow_logits_kernel": ("tw_device_env", "test_gpu_device_env.py", "test_gridworld_collect_equals_host_path_and_oracle"),
+    "compact_env_obs8_kernel": ("tw_device_env", "test_gpu_finalize.py", "test_every_form_on_both_sides_of_every_switch"),
+    "narrow_logits_kernel": ("tw_device_env", "test_gpu_finalize.py", "test_columns_narrowed_kept_and_moved_from_the_wide_array"),
 }
 
 

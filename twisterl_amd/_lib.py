@@ -90,6 +90,20 @@ class LaunchInfo(C.Structure):
  TW_KERNEL_ROLLOUT_BIG, TW_KERNEL_ONEHOT) = range(8)
 
 
+TW_FIN_NONE, TW_FIN_GROUP16, TW_FIN_GROUP8, TW_FIN_WAVE, TW_FIN_AZ = range(5)
+
+
+class FinalizeLaunch(C.Structure):
+    _fields_ = [("form", C.c_uint32), ("waves", C.c_uint32), ("blocks", C.c_uint32), ("threads", C.c_uint32), ("lds_bytes", C.c_uint64)]
+
+
+class DebugTailArgs(C.Structure):
+    _fields_ = [("n_episodes", C.c_uint64), ("t_pad", C.c_uint32), ("is_ppo", C.c_uint32), ("n_cells", C.c_uint32), ("n_actions", C.c_uint32),
+                ("obs_width", C.c_uint32), ("merge_order", C.c_uint32), ("scan_only", C.c_uint32), ("arena_fill", C.c_uint32),
+                ("gamma", C.c_float), ("lambda_", C.c_float), ("ep_len", C.c_void_p), ("records", C.c_void_p), ("obs16", C.c_void_p),
+                ("wide", C.c_void_p), ("ep_start_out", C.c_void_p), ("total_out", C.c_void_p)]
+
+
 class EnvVTable(C.Structure):
     _fields_ = [("prototype", C.c_void_p), ("num_actions", C.c_uint32), ("n_obs", C.c_uint32), ("obs_size", C.c_uint32),
                 ("clone", C.CFUNCTYPE(C.c_void_p, C.c_void_p)), ("destroy", C.CFUNCTYPE(None, C.c_void_p)),
@@ -127,6 +141,8 @@ SYMBOLS = {
     "tw_debug_last_attempts": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]),
     "tw_debug_episode_order": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "tw_debug_policy_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "tw_debug_collect_tail": (C.c_int, [C.POINTER(DebugTailArgs), C.POINTER(FinalizeLaunch), C.POINTER(_VP)]),
+    "tw_debug_collected_arena": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "tw_puzzle_create": (_VP, [C.c_uint32] * 5),
     "tw_puzzle_clone": (_VP, [_VP]),
     "tw_puzzle_destroy": (None, [_VP]),
@@ -322,6 +338,57 @@ def debug_policy_image(policy):
     check(lib().tw_debug_policy_image(h, img.ctypes.data_as(C.c_void_p), size.value, C.byref(size), ranges.ctypes.data_as(C.POINTER(C.c_uint64)),
                                       n.value, C.byref(n)))
     return img, [(int(o), int(b)) for o, b in ranges[:n.value]]
+
+
+def debug_scan(ep_len, merge_order: bool):
+    """(ep_start, total) of the collectors' episode-length scan over any uint32 lengths (tw_debug_collect_tail in scan-only mode; test
+    hook): ep_start[e] = the lengths in front of episode e in the output order, as uint64; total as a Python int."""
+    import numpy as np
+    ep_len = np.ascontiguousarray(ep_len, dtype=np.uint32)
+    ep_start, total = np.zeros(ep_len.size, dtype=np.uint64), C.c_uint64()
+    a = DebugTailArgs(n_episodes=ep_len.size, merge_order=int(bool(merge_order)), scan_only=1, ep_len=ep_len.ctypes.data,
+                      ep_start_out=ep_start.ctypes.data, total_out=C.addressof(total))
+    check(lib().tw_debug_collect_tail(C.byref(a), None, None))
+    return ep_start, int(total.value)
+
+
+def debug_collect_tail(ep_len, records, t_pad: int, *, is_ppo: bool, n_cells: int, n_actions: int, obs16=None, obs_width: int = 1, wide=None,
+                       gamma: float = 0.0, lam: float = 0.0, merge_order: bool = False, arena_fill: int = 0):
+    """The tail of every device collector on records the caller wrote (tw_debug_collect_tail; test hook) -> (handle, launch):
+    a tw_collected handle (debug_collected_fields / debug_collected_arena; free it with lib().tw_collected_free) and the finalize
+    kernel that was launched as a dict of FinalizeLaunch's fields.  records: [E][t_pad] records of 48 bytes (any array of that many
+    bytes); obs16: uint16 [E][t_pad][n_cells] or None; wide: float32 [E][t_pad][n_actions] for more than four actions."""
+    import numpy as np
+    ep_len = np.ascontiguousarray(ep_len, dtype=np.uint32)
+    records = np.ascontiguousarray(records)
+    if records.nbytes != ep_len.size * t_pad * 48:
+        raise ValueError(f"debug_collect_tail: {records.nbytes} bytes of records, {ep_len.size} x {t_pad} x 48 expected")
+    if obs16 is not None:
+        obs16 = np.ascontiguousarray(obs16, dtype=np.uint16)
+        if obs16.size != ep_len.size * t_pad * n_cells:
+            raise ValueError("debug_collect_tail: obs16 is not [E][t_pad][n_cells]")
+    if wide is not None:
+        wide = np.ascontiguousarray(wide, dtype=np.float32)
+        if wide.size != ep_len.size * t_pad * n_actions:
+            raise ValueError("debug_collect_tail: wide is not [E][t_pad][n_actions]")
+    a = DebugTailArgs(n_episodes=ep_len.size, t_pad=t_pad, is_ppo=int(bool(is_ppo)), n_cells=n_cells, n_actions=n_actions, obs_width=obs_width,
+                      merge_order=int(bool(merge_order)), scan_only=0, arena_fill=arena_fill, gamma=gamma, lambda_=lam,
+                      ep_len=ep_len.ctypes.data, records=records.ctypes.data, obs16=None if obs16 is None else obs16.ctypes.data,
+                      wide=None if wide is None else wide.ctypes.data)
+    launch, handle = FinalizeLaunch(), _VP()
+    check(lib().tw_debug_collect_tail(C.byref(a), C.byref(launch), C.byref(handle)))
+    return handle, {name: int(getattr(launch, name)) for name, _ in FinalizeLaunch._fields_}
+
+
+def debug_collected_arena(handle):
+    """(arena, offsets, scratch) of a tw_collected handle (tw_debug_collected_arena; test hook): every byte of its arena as a uint8
+    array, the offset of each field TW_F_* in it, and (offset, bytes) of the four-column logits scratch behind the fields."""
+    import numpy as np
+    size, offs, scratch = C.c_uint64(), (C.c_uint64 * TW_F_COUNT)(), (C.c_uint64 * 2)()
+    check(lib().tw_debug_collected_arena(handle, None, 0, C.byref(size), offs, scratch))
+    arena = np.zeros(size.value, dtype=np.uint8)
+    check(lib().tw_debug_collected_arena(handle, arena.ctypes.data_as(C.c_void_p), size.value, C.byref(size), offs, scratch))
+    return arena, [int(x) for x in offs], (int(scratch[0]), int(scratch[1]))
 
 
 def release_cached_memory() -> None:

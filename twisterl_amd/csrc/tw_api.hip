@@ -1008,6 +1008,7 @@ struct tw_collected {
                                             // what the Puzzle collectors write, and nobody else claims (trainer hand-off, tw_trainer.hip)
     void *field_ptr[TW_F_COUNT] = {};
     size_t field_bytes[TW_F_COUNT] = {};
+    size_t scratch_off = 0, scratch_bytes = 0;   // collect_tail, other than four columns: the finalize kernel's four-column logits behind the fields
     uint64_t n_records = 0, n_episodes = 0;
     uint32_t n_cells = 0, n_actions = 0;
     int is_ppo = 0;
@@ -1192,7 +1193,7 @@ int collect_tail(const CollectTail &d, tw_collected **out)
     else put(TW_F_REMAINING, total * 4);
     put(TW_F_EP_LEN, E * 4); put(TW_F_EP_START, E * 8);
     const size_t o_lg4 = A != 4 ? cur : off[TW_F_LOGITS];
-    if (A != 4) cur += total * 16;
+    if (A != 4) { c->scratch_off = cur; c->scratch_bytes = total * 16; cur += total * 16; }
     int rc = hipGetDevice(&c->device) == hipSuccess ? arena_acquire(cur, &c->arena, &c->arena_cap) : TW_ERR_HIP;
     if (rc) { delete c; return rc; }
     uint8_t *ca = reinterpret_cast<uint8_t *>(c->arena);
@@ -1201,16 +1202,17 @@ int collect_tail(const CollectTail &d, tw_collected **out)
 
     // from here on every failing step frees the result (the arena goes back to the pool) and returns what the step returned
 #define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { tw_collected_free(c); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
+    if (d.arena_fill) TW_HIP_C(hipMemsetAsync(ca, d.arena_fill, c->arena_cap, s));       // (test hook: the gaps become readable)
     TW_HIP_C(hipEventRecord(d.ev->ev[3], s));
     const int rec_cells = d.obs16 ? 0 : (int)d.n_cells;                   // (0 cells: the obs ids come from their own array)
     if (d.is_ppo) {
         CompactTraj ct{};
         ct.obs = ca + off[TW_F_OBS]; ct.logits = reinterpret_cast<float *>(ca + o_lg4); ct.perms = reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]);
         ct.values = at(TW_F_VALUES); ct.rewards = at(TW_F_REWARDS); ct.actions = ca + off[TW_F_ACTIONS]; ct.advs = at(TW_F_ADVS); ct.rets = at(TW_F_RETS);
-        rc = launch_finalize_ppo(d.traj, d.ep_start, E, rec_cells, d.gamma, d.lambda, ct, s);
+        rc = launch_finalize_ppo(d.traj, d.ep_start, E, rec_cells, d.gamma, d.lambda, ct, s, d.launched);
     } else {
         rc = launch_finalize_az(d.traj, d.ep_start, E, rec_cells, ca + off[TW_F_OBS], reinterpret_cast<float *>(ca + o_lg4),
-                                reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]), at(TW_F_REMAINING), s);
+                                reinterpret_cast<int8_t *>(ca + off[TW_F_PERMS]), at(TW_F_REMAINING), s, d.launched);
     }
     if (rc == TW_OK && d.obs16)
         rc = OW == 2 ? launch_compact_obs16(d.obs16, d.traj.ep_len, d.ep_start, E, t_pad, (int)d.n_cells, reinterpret_cast<uint16_t *>(ca + off[TW_F_OBS]), s)
@@ -1241,6 +1243,97 @@ extern "C" void tw_collected_free(tw_collected *c)
     if (!c) return;
     arena_release(c->arena, c->arena_cap, c->device, c->stream);
     delete c;
+}
+
+// tw_debug_collect_tail (test hook): launch_scan + collect_tail over records the caller wrote on the host.  Everything a kernel of the
+// tail indexes with is checked here, before the first launch: a test cannot reach a kernel with a length or a horizon it would fault on.
+extern "C" int tw_debug_collect_tail(const tw_debug_tail_args *a, tw_finalize_launch *launched, tw_collected **out)
+{
+    if (out) *out = nullptr;
+    if (launched) *launched = tw_finalize_launch{};
+    if (!a || !a->ep_len) { set_error("tw_debug_collect_tail: null argument"); return TW_ERR_INVALID; }
+    const uint64_t E = a->n_episodes;
+    if (E == 0 || E > (1ull << 28)) { set_error("tw_debug_collect_tail: %llu episodes (1 .. 2^28)", (unsigned long long)E); return TW_ERR_INVALID; }
+    const bool scan_only = a->scan_only != 0;
+    const uint32_t A = a->n_actions, NC = a->n_cells, OW = a->obs16 ? a->obs_width : 1u;
+    const uint64_t t_pad = a->t_pad;
+    uint64_t sum = 0;
+    if (scan_only) {
+        if (!a->ep_start_out || !a->total_out) { set_error("tw_debug_collect_tail: scan-only mode needs ep_start_out and total_out"); return TW_ERR_INVALID; }
+    } else {
+        if (!out || !a->records) { set_error("tw_debug_collect_tail: null argument"); return TW_ERR_INVALID; }
+        if (NC < 1 || NC > (a->obs16 ? 64u : 16u) || (OW != 1 && OW != 2)) { set_error("tw_debug_collect_tail: %u obs ids of %u bytes", NC, OW); return TW_ERR_INVALID; }
+        if (A < 1 || A > 31 || (A > 4) != (a->wide != nullptr)) { set_error("tw_debug_collect_tail: %u actions %s a wide array", A, a->wide ? "with" : "without"); return TW_ERR_INVALID; }
+        if (a->arena_fill > 255) { set_error("tw_debug_collect_tail: the arena fill is one byte"); return TW_ERR_INVALID; }
+        if (t_pad == 0) { set_error("tw_debug_collect_tail: t_pad 0"); return TW_ERR_INVALID; }
+        const uint64_t max_t = a->is_ppo ? (uint64_t)finalize_ppo_max_t_pad(a->obs16 ? 0 : (int)NC) : 64 * 1024 / (4 * 2 * sizeof(float));
+        if (t_pad > max_t) { set_error("finalize: t_pad %llu too large for the LDS tile (at most %llu)", (unsigned long long)t_pad, (unsigned long long)max_t); return TW_ERR_UNSUPPORTED; }
+        for (uint64_t e = 0; e < E; ++e) {
+            if (a->ep_len[e] == 0 || a->ep_len[e] > t_pad) { set_error("tw_debug_collect_tail: episode %llu has %u records (1 .. %llu)", (unsigned long long)e, a->ep_len[e], (unsigned long long)t_pad); return TW_ERR_INVALID; }
+            sum += a->ep_len[e];
+        }
+    }
+    int rc = require_device(); if (rc) return rc;
+
+    std::lock_guard<std::mutex> lock(g_ws_mutex);
+    hipStream_t s = current_stream();
+    const uint64_t R = scan_only ? 0 : E * t_pad;
+    size_t cur = 0;
+    auto seg = [&](size_t bytes) { size_t o = cur; cur = align_up(cur + bytes, 256); return o; };
+    const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(32), o_scan = seg(scan_scratch_bytes(E)),
+                 o_obs16 = seg(!scan_only && a->obs16 ? R * NC * 2 : 0), o_lgw = seg(!scan_only && a->wide ? R * A * sizeof(float) : 0);
+    rc = check_memory_fit(cur, "tw_debug_collect_tail"); if (rc) return rc;
+    void *wsp = nullptr;
+    rc = ws_reserve(cur, &wsp); if (rc) return rc;
+    uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
+    PaddedTraj traj{};
+    traj.rec = reinterpret_cast<PaddedRec *>(ws + o_rec); traj.ep_len = reinterpret_cast<uint32_t *>(ws + o_len); traj.t_pad = (int32_t)t_pad;
+    uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
+
+    EventSet ev; rc = ev.init(); if (rc) return rc;
+    TW_HIP(hipEventRecord(ev.ev[0], s));
+    TW_HIP(hipMemcpyAsync(traj.ep_len, a->ep_len, E * 4, hipMemcpyHostToDevice, s));
+    if (!scan_only) {
+        TW_HIP(hipMemcpyAsync(traj.rec, a->records, R * sizeof(PaddedRec), hipMemcpyHostToDevice, s));
+        if (a->obs16) TW_HIP(hipMemcpyAsync(ws + o_obs16, a->obs16, R * NC * 2, hipMemcpyHostToDevice, s));
+        if (a->wide) TW_HIP(hipMemcpyAsync(ws + o_lgw, a->wide, R * A * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    TW_HIP(hipEventRecord(ev.ev[1], s));
+    rc = launch_scan(traj.ep_len, E, a->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
+    if (rc) return rc;
+    TW_HIP(hipEventRecord(ev.ev[2], s));
+    uint64_t total = 0;
+    TW_HIP(hipMemcpyAsync(&total, total_d, 8, hipMemcpyDeviceToHost, s));
+    if (scan_only) TW_HIP(hipMemcpyAsync(a->ep_start_out, ep_start_ws, E * 8, hipMemcpyDeviceToHost, s));
+    TW_HIP(hipStreamSynchronize(s));
+    if (scan_only) { *a->total_out = total; return TW_OK; }
+    // the finalize kernels place every episode by the scan's offsets: a scan that disagrees with the lengths ends the call here
+    if (total != sum) { set_error("tw_debug_collect_tail: the scan counts %llu records, the lengths add up to %llu", (unsigned long long)total, (unsigned long long)sum); return TW_ERR_HIP; }
+
+    CollectTail tail{};
+    tail.is_ppo = a->is_ppo != 0; tail.traj = traj; tail.ep_start = ep_start_ws; tail.E = E; tail.total = total;
+    tail.n_cells = NC; tail.n_actions = A; tail.obs_size = OW == 2 ? 65535u : 256u;
+    if (a->obs16) { tail.obs16 = reinterpret_cast<const uint16_t *>(ws + o_obs16); tail.obs_width = OW; }
+    if (a->wide) tail.wide = reinterpret_cast<const float *>(ws + o_lgw);
+    tail.gamma = a->gamma; tail.lambda = a->lambda; tail.ev = &ev; tail.stream = s;
+    tail.stats.padded_bytes = cur;
+    tail.arena_fill = (uint8_t)a->arena_fill; tail.launched = launched;
+    return collect_tail(tail, out);
+}
+
+// tw_debug_collected_arena (test hook): every byte of a result's arena, with where the fields lie in it
+extern "C" int tw_debug_collected_arena(const tw_collected *c, void *out, uint64_t cap, uint64_t *bytes, uint64_t *offsets, uint64_t *scratch)
+{
+    if (!c || !bytes || !offsets || !scratch || (cap && !out)) { set_error("tw_debug_collected_arena: null argument"); return TW_ERR_INVALID; }
+    if (!c->arena) { set_error("tw_debug_collected_arena: the result has no arena"); return TW_ERR_INVALID; }
+    TW_HIP(hipStreamSynchronize(current_stream()));
+    *bytes = (uint64_t)c->arena_cap;
+    for (int f = 0; f < TW_F_COUNT; ++f)
+        offsets[f] = c->field_ptr[f] ? (uint64_t)(reinterpret_cast<const uint8_t *>(c->field_ptr[f]) - reinterpret_cast<const uint8_t *>(c->arena)) : 0;
+    scratch[0] = c->scratch_off; scratch[1] = c->scratch_bytes;
+    const size_t take = cap < (uint64_t)c->arena_cap ? (size_t)cap : c->arena_cap;
+    if (take) TW_HIP(hipMemcpy(out, c->arena, take, hipMemcpyDeviceToHost));
+    return TW_OK;
 }
 
 // ====================================================================================== PPO collect

@@ -589,8 +589,10 @@ int launch_scan(const uint32_t *ep_len, uint64_t n_episodes, int merge_order, ui
                 uint64_t *total /*device*/, void *scratch, size_t scratch_bytes, hipStream_t s);
 size_t scan_scratch_bytes(uint64_t n_episodes);
 int finalize_ppo_max_t_pad(int n_cells);            // the longest horizon (t_pad) launch_finalize_ppo takes
+// (launched, optional: the form, grid and LDS of the kernel that was launched -- tw_debug_collect_tail; not tw_debug_last_launch, which a
+//  finalize after every rollout would overwrite)
 int launch_finalize_ppo(const PaddedTraj &in, const uint64_t *ep_start, uint64_t n_episodes, int n_cells,
-                        float gamma, float lambda, const CompactTraj &out, hipStream_t s);
+                        float gamma, float lambda, const CompactTraj &out, hipStream_t s, tw_finalize_launch *launched = nullptr);
 struct SolveArgs {
     PuzzleConsts env;
     PolicyDev    pol;
@@ -669,7 +671,8 @@ int launch_mcts_f32(const MctsArgs &a, hipStream_t s, uint32_t *blocks, uint32_t
 size_t mcts_big_node_bytes();
 int launch_mcts_big(const MctsArgs &a, uint16_t *obs16, hipStream_t s, uint32_t *blocks, uint32_t *threads);
 int launch_finalize_az(const PaddedTraj &in, const uint64_t *ep_start, uint64_t n_episodes, int n_cells,
-                       uint8_t *obs_out, float *probs_out, int8_t *perms_out, float *remaining_out, hipStream_t s);
+                       uint8_t *obs_out, float *probs_out, int8_t *perms_out, float *remaining_out, hipStream_t s,
+                       tw_finalize_launch *launched = nullptr);
 int launch_onehot(const uint8_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, bool cell_major, float *out, hipStream_t s);
 int launch_onehot16(const uint16_t *obs, uint64_t row0, uint64_t rows, int n_cells, int obs_size, float *out, hipStream_t s);   // two-byte ids, 0xFFFF = none
 int launch_ppo_pack(const float *logits, const uint8_t *actions, const int8_t *perms, const float *advs, uint64_t row0, uint64_t rows,
@@ -747,6 +750,8 @@ struct CollectTail {
     float gamma, lambda;                              // PPO only
     const EventSet *ev; hipStream_t stream;           // events 0..2 are the caller's
     tw_collect_stats stats;                           // the caller's: rollout_blocks / _threads, padded_bytes, *_evals; the tail's: ms_*, records, episodes
+    uint8_t arena_fill;                               // not 0 (tw_debug_collect_tail only): the acquired arena is set to this byte before finalize
+    tw_finalize_launch *launched;                     // not null (tw_debug_collect_tail only): what the finalize launcher reports
 };
 // The one ending of the device collectors: the fields in a pooled arena, finalize (GAE or remaining values + compaction), the obs and
 // logits steps the descriptor asks for, ep_len / ep_start, the timings.  On failure nothing is left behind.

@@ -299,7 +299,7 @@ static size_t fin_group_bytes(int g, int t_pad, int n_cells)
 
 template <int G>
 static int launch_fin_group(const PaddedTraj &in, const uint64_t *ep_start, uint64_t E, int n_cells, float gamma, float lambda,
-                            const CompactTraj &out, hipStream_t s)
+                            const CompactTraj &out, hipStream_t s, tw_finalize_launch *launched)
 {
     const size_t lds_bytes = fin_group_bytes(G, in.t_pad, n_cells);
     uint64_t blocks = (E + G - 1) / G;
@@ -308,6 +308,7 @@ static int launch_fin_group(const PaddedTraj &in, const uint64_t *ep_start, uint
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&finalize_ppo_group_kernel<G>), lds_bytes)) return rc;
     hipLaunchKernelGGL(finalize_ppo_group_kernel<G>, dim3((unsigned)blocks), dim3(256), lds_bytes, s, in, ep_start, E, n_cells, gamma, lambda, out);
     TW_HIP(hipGetLastError());
+    if (launched) *launched = tw_finalize_launch{G == 16 ? TW_FIN_GROUP16 : TW_FIN_GROUP8, 4, (uint32_t)blocks, 256, lds_bytes};
     return TW_OK;
 }
 
@@ -320,14 +321,14 @@ int finalize_ppo_max_t_pad(int n_cells)
 }
 
 int launch_finalize_ppo(const PaddedTraj &in, const uint64_t *ep_start, uint64_t E, int n_cells, float gamma,
-                        float lambda, const CompactTraj &out, hipStream_t s)
+                        float lambda, const CompactTraj &out, hipStream_t s, tw_finalize_launch *launched)
 {
     if (E == 0) return TW_OK;
     // horizons whose tile of 16 (8) episodes fits 64 KiB of LDS -- 511 (1,023: every horizon the Puzzle takes) records with 16-cell or
     // id-array observations, 170 (341) with staged ones: the grouped form (headline size, 262,144 x 257: 1.21 ms with 16, 1.25 with 8 or 32, against 1.82 per wave;
     // scripts/bench_finalize.py); longer ones: a wave per episode
-    if (fin_group_bytes(16, in.t_pad, n_cells) <= 64 * 1024) return launch_fin_group<16>(in, ep_start, E, n_cells, gamma, lambda, out, s);
-    if (fin_group_bytes(8, in.t_pad, n_cells) <= 64 * 1024) return launch_fin_group<8>(in, ep_start, E, n_cells, gamma, lambda, out, s);
+    if (fin_group_bytes(16, in.t_pad, n_cells) <= 64 * 1024) return launch_fin_group<16>(in, ep_start, E, n_cells, gamma, lambda, out, s, launched);
+    if (fin_group_bytes(8, in.t_pad, n_cells) <= 64 * 1024) return launch_fin_group<8>(in, ep_start, E, n_cells, gamma, lambda, out, s, launched);
     const size_t per_wave = fin_wave_bytes(in.t_pad, n_cells);
     int waves = FIN_WAVES;
     while (waves > 1 && waves * per_wave > 64 * 1024) waves >>= 1;           // long horizons: fewer episodes per workgroup
@@ -338,6 +339,7 @@ int launch_finalize_ppo(const PaddedTraj &in, const uint64_t *ep_start, uint64_t
     hipLaunchKernelGGL(finalize_ppo_kernel, dim3((unsigned)blocks), dim3(waves * 64), lds_bytes, s, in, ep_start, E,
                        n_cells, gamma, lambda, out);
     TW_HIP(hipGetLastError());
+    if (launched) *launched = tw_finalize_launch{TW_FIN_WAVE, (uint32_t)waves, (uint32_t)blocks, (uint32_t)waves * 64, lds_bytes};
     return TW_OK;
 }
 

@@ -611,7 +611,7 @@ __global__ void __launch_bounds__(AZF_WAVES * 64) finalize_az_kernel(const Padde
 }
 
 int launch_finalize_az(const PaddedTraj &in, const uint64_t *ep_start, uint64_t E, int n_cells, uint8_t *obs_out,
-                       float *probs_out, int8_t *perms_out, float *remaining_out, hipStream_t s)
+                       float *probs_out, int8_t *perms_out, float *remaining_out, hipStream_t s, tw_finalize_launch *launched)
 {
     if (E == 0) return TW_OK;
     const size_t lds_bytes = (size_t)AZF_WAVES * 2 * in.t_pad * sizeof(float);
@@ -621,6 +621,7 @@ int launch_finalize_az(const PaddedTraj &in, const uint64_t *ep_start, uint64_t 
     hipLaunchKernelGGL(finalize_az_kernel, dim3((unsigned)blocks), dim3(AZF_WAVES * 64), lds_bytes, s, in, ep_start, E, n_cells,
                        obs_out, probs_out, perms_out, remaining_out);
     TW_HIP(hipGetLastError());
+    if (launched) *launched = tw_finalize_launch{TW_FIN_AZ, AZF_WAVES, (uint32_t)blocks, AZF_WAVES * 64, lds_bytes};
     return TW_OK;
 }
 
