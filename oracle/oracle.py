@@ -281,7 +281,9 @@ class Policy:
         pol.n_common = fill(pol.common, common)
         pol.n_action = fill(pol.action, action)
         pol.n_value = fill(pol.value, value)
-        pol.n_actions = int(np.asarray(action[-1][1]).size if len(action) else (len(act_perms[0]) if len(act_perms) else 0))
+        # an empty action Sequential hands its input on (modules.rs:28-34): the logits are the common output, or the embedding
+        pol.n_actions = int(np.asarray(action[-1][1]).size if len(action) else len(act_perms[0]) if len(act_perms)
+                            else np.asarray(common[-1][1]).size if len(common) else bias.size)
         pol.obs_size = int(vec.shape[0]) if len(shape) == 1 else int(np.prod(shape))
         pol.n_perms = len(obs_perms)
         if pol.n_perms:
@@ -349,6 +351,28 @@ class Policy:
         lib().two_policy_predict(C.byref(self.pol), o, C.c_int(n), self._masks(masks), C.c_int(perm),
                                  C.c_int(arith), pr, C.byref(v))
         return [float(x) for x in pr][: self.n_actions], float(v.value)
+
+    def evaluate_batch(self, mode, obs, masks, perms=None, arith=ARITH_CHAIN):
+        """forward (mode 0), predict (1) or full_predict (2) record by record: obs [n, n_obs] ids, masks [n, n_actions], perms [n]
+        or None (-1 = None; full_predict takes none) -> (logits or probs [n, n_actions] f32, values [n] f32).  An id of -1 is a
+        free slot of a shorter observation: the reference's Policy is handed the list without it."""
+        obs = np.asarray(obs, dtype=np.int64)
+        n = obs.shape[0]
+        obs = obs.reshape(n, -1)
+        masks = np.asarray(masks).reshape(n, self.n_actions)
+        out, val = np.empty((n, self.n_actions), np.float32), np.empty(n, np.float32)
+        for i in range(n):
+            ids = [int(x) for x in obs[i] if x >= 0]
+            perm = -1 if perms is None else int(perms[i])
+            if mode == 0:
+                out[i], val[i] = self.forward(ids, masks[i], perm=perm, arith=arith)
+            elif mode == 1:
+                out[i], val[i] = self.predict(ids, masks[i], perm=perm, arith=arith)
+            elif mode == 2:
+                out[i], val[i] = self.full_predict(ids, masks[i], arith=arith)
+            else:
+                raise ValueError(f"mode {mode}")
+        return out, val
 
     def full_predict(self, obs, masks, arith=ARITH_REF):
         o, n = self._obs(obs)

@@ -8,6 +8,9 @@ f32 orders against an arithmetic neither of them uses:
 * Policy::_raw_predict (policy.rs:79-100): embedding, common layers, value layers summed, action layers; a twist maps the obs ids
   through obs_perms[perm] (policy.rs:81-83) and gathers the logits by act_perms[perm] (policy.rs:95-97).
 * Policy::forward_with_perm (policy.rs:56-65): masked logits are exactly -1e10.
+* Policy::predict_with_perm (policy.rs:39-49): exp(l) for a legal action, 0 for a masked one, divided by their sum + 1e-6.
+* Policy::full_predict (policy.rs:102-126): logits / n and value / n summed over all n twists in twist order, then that soft-max;
+  without twists it is predict.
 * GAE (ppo.rs:82-92): ret[t] = r[t] + gamma (v[t+1] + lambda adv[t+1]), adv[t] = ret[t] - v[t]; at the last record adv = r - v,
   ret = r.
 """
@@ -25,13 +28,27 @@ def linear_f64(w, b, relu, x):
 
 
 def embedding_bag_f64(vectors, bias, relu, ids):
-    """EmbeddingBag on a batch of obs ids [n, cells] -> [n, vec_len] in float64: bias plus the rows in cell order."""
+    """EmbeddingBag on a batch of obs ids [n, cells] -> [n, vec_len] in float64: bias plus the rows in cell order.  An id of -1
+    is a free slot of a shorter observation: the reference is handed the shorter list, so the slot adds nothing."""
     V = np.asarray(vectors, np.float64)
     ids = np.asarray(ids, np.int64)
     h = np.broadcast_to(np.asarray(bias, np.float64), (ids.shape[0], V.shape[1])).copy()
     for c in range(ids.shape[1]):
-        h += V[ids[:, c]]
+        h += np.where(ids[:, c, None] >= 0, V[ids[:, c]], 0.0)         # a free slot (-1) adds nothing
     return np.maximum(h, 0.0) if relu else h
+
+
+def twist_ids(OP, perms, ids):
+    """obs_perms[perm][id] per record (policy.rs:81-83); a free slot (-1) stays free."""
+    return np.where(ids >= 0, np.take_along_axis(OP[perms], np.maximum(ids, 0), axis=1), -1)
+
+
+def _n_actions(emb, common, action):
+    """Width of the action stack's output: an empty Sequential hands its input on (modules.rs:28-34)."""
+    for stack in (action, common):
+        if len(stack):
+            return int(np.asarray(stack[-1][1]).size)
+    return int(np.asarray(emb).shape[1])
 
 
 def forward_f64(arrs, obs_perms, act_perms, obs, masks, perms, emb_relu=True, chunk=8192):
@@ -45,7 +62,6 @@ def forward_f64(arrs, obs_perms, act_perms, obs, masks, perms, emb_relu=True, ch
     obs = obs.reshape(n, -1)
     masks = np.asarray(masks, bool).reshape(n, -1)
     perms = np.asarray(perms, np.int64).reshape(n)
-    A = np.asarray(action[-1][1]).size
     OP = np.asarray(obs_perms, np.int64) if len(obs_perms) else None
     AP = np.asarray(act_perms, np.int64) if len(act_perms) else None
     if (perms >= 0).any() and (OP is None or AP is None or perms.max() >= len(OP)):
@@ -61,6 +77,7 @@ def forward_f64(arrs, obs_perms, act_perms, obs, masks, perms, emb_relu=True, ch
                 x = np.maximum(x, 0.0)
         return x
 
+    A = _n_actions(emb, common, action)
     logits = np.empty((n, A), np.float64)
     values = np.empty(n, np.float64)
     for s in range(0, n, chunk):
@@ -69,7 +86,7 @@ def forward_f64(arrs, obs_perms, act_perms, obs, masks, perms, emb_relu=True, ch
         tw = p >= 0
         if tw.any():
             ids = ids.copy()
-            ids[tw] = np.take_along_axis(OP[p[tw]], ids[tw], axis=1)
+            ids[tw] = twist_ids(OP, p[tw], ids[tw])
         h = embedding_bag_f64(V, eb, emb_relu, ids)
         h = seq(common, h)
         values[s:e] = seq(value, h).sum(axis=1)
@@ -222,7 +239,7 @@ def forward_f64_bound(arrs, obs_perms, act_perms, obs, masks, perms, mode, emb_r
     common, action, value = lay(common), lay(action), lay(value)
     ebias = np.asarray(eb, np.float64)
     rel, eta, _ = MODES[mode]
-    A = action[-1][1].size
+    A = _n_actions(emb, common, action)
     logits, values = np.empty((n, A)), np.empty(n)
     el, ev = np.zeros((n, A)), np.empty(n)
 
@@ -239,8 +256,8 @@ def forward_f64_bound(arrs, obs_perms, act_perms, obs, masks, perms, mode, emb_r
         tw = p >= 0
         if tw.any():
             ids = ids.copy()
-            ids[tw] = np.take_along_axis(OP[p[tw]], ids[tw], axis=1)
-        rows = V[ids]                                                    # [m, cells, emb]
+            ids[tw] = twist_ids(OP, p[tw], ids[tw])
+        rows = V[ids] * (ids >= 0)[:, :, None]                           # [m, cells, emb]; a free slot (-1) adds nothing
         h = ebias + rows.sum(axis=1)
         # EmbeddingBag: the table entries are the rounded operands (one-hot x table), the bias an f32 addend
         e = _gamma(mode, ids.shape[1] + 1) * (np.abs(rows).sum(axis=1) + np.abs(ebias)) + eta * ids.shape[1]
@@ -291,7 +308,7 @@ def max_activations(arrs, obs_perms, act_perms, obs, perms, emb_relu=True):
     if (p >= 0).any():
         OP = np.asarray(obs_perms, np.int64)
         obs = obs.copy()
-        obs[p >= 0] = np.take_along_axis(OP[p[p >= 0]], obs[p >= 0], axis=1)
+        obs[p >= 0] = twist_ids(OP, p[p >= 0], obs[p >= 0])
     h = embedding_bag_f64(emb, eb, emb_relu, obs)
     m0, m1 = float(np.abs(h).max()), 0.0
     for w, b, r in common:
@@ -303,3 +320,106 @@ def max_activations(arrs, obs_perms, act_perms, obs, perms, emb_relu=True):
             x = linear_f64(w, b, r, x)
             m1 = max(m1, float(np.abs(x).max()))
     return m0, m1
+
+
+# ---------------------------------------------------------------------------------------------- predict / full_predict
+SOFTMAX_EPS = 0.000001            # policy.rs:47,124
+# Relative error of an f32 exp against the exact exponential of its f32 argument, MEASURED on the CPU against float64 (never on
+# a GPU): the oracle's two_expf_det (the operation sequence the kernels' tw_expf repeats) and libm's expf over 2,000,001 evenly
+# spaced f32 arguments of [-87, 88].  Measured maxima: 1.392 x 2^-24 (two_expf_det, at x = -59.956) and 0.999 x 2^-24 (glibc's
+# expf).  Margin 4 x the larger, one rounding model for both implementations; tests/test_eval_matrix.py repeats the measurement
+# on a coarser grid and on every in-range logit of tests/eval_matrix.py and holds it under a quarter of this constant.
+EXP_REL = 4 * 1.392 * 2.0 ** -24
+EXP_RANGE = 40.0                  # |logit| + its error below this: exp, the sum of 31 of them and every quotient are normal f32 numbers
+
+
+def masked_softmax_f64(logits, masks):
+    """policy.rs:43-47 / 118-124 in float64: exp(l) where the mask is set and 0 where it is not, over their sum + 1e-6.  No
+    maximum is subtracted; a row without a legal action is 0 / 1e-6 = 0 everywhere."""
+    l = np.asarray(logits, np.float64)
+    m = np.asarray(masks, bool).reshape(l.shape)
+    with np.errstate(over="ignore"):
+        e = np.where(m, np.exp(np.where(m, l, 0.0)), 0.0)
+        return e / (e.sum(axis=1, keepdims=True) + SOFTMAX_EPS)
+
+
+def predict_f64(arrs, obs_perms, act_perms, obs, masks, perms, emb_relu=True):
+    """Policy::predict_with_perm (policy.rs:39-49) on a batch -> (probs [n, A], values [n]) in float64; perms [n], -1 = no twist."""
+    logits, values = forward_f64(arrs, obs_perms, act_perms, obs, masks, perms, emb_relu=emb_relu)
+    return masked_softmax_f64(logits, masks), values
+
+
+def _twist_average(per_twist):
+    """policy.rs:109-115: acc += x_pi / n for pi = 0 .. n - 1, from 0."""
+    acc = np.zeros_like(per_twist[0])
+    for x in per_twist:
+        acc = acc + x / float(len(per_twist))
+    return acc
+
+
+def full_predict_logits_f64(arrs, obs_perms, act_perms, obs, emb_relu=True):
+    """The logits [n, A] and values [n] that Policy::full_predict (policy.rs:102-116) hands its soft-max, before any mask:
+    the average over all twists, or the one un-twisted pass of a policy without twists (policy.rs:103)."""
+    n = len(obs)
+    legal = np.ones((n, _n_actions(arrs[0], arrs[2], arrs[3])), bool)
+    if len(obs_perms) == 0:
+        return forward_f64(arrs, (), (), obs, legal, np.full(n, -1), emb_relu=emb_relu)
+    per = [forward_f64(arrs, obs_perms, act_perms, obs, legal, np.full(n, pi), emb_relu=emb_relu) for pi in range(len(obs_perms))]
+    return _twist_average([l for l, _ in per]), _twist_average([v for _, v in per])
+
+
+def full_predict_f64(arrs, obs_perms, act_perms, obs, masks, emb_relu=True):
+    """Policy::full_predict (policy.rs:102-126) on a batch -> (probs [n, A], values [n]) in float64."""
+    logits, values = full_predict_logits_f64(arrs, obs_perms, act_perms, obs, emb_relu=emb_relu)
+    return masked_softmax_f64(logits, masks), values
+
+
+def full_predict_f64_bound(arrs, obs_perms, act_perms, obs, mode="f32", emb_relu=True):
+    """full_predict_logits_f64 plus an a-priori bound of |mode's f32 twist average - float64| -> logits, values, err_logits,
+    err_values (all unmasked).  Twist pi contributes t = fl(x^ / n) with |x^ - x| <= e (forward_f64_bound): |t - x / n| <=
+    (e + u (|x| + e)) / n; the n terms are added from 0 with n - 1 rounded additions: gamma(n - 1) sum |t| more."""
+    n = len(obs)
+    T = len(obs_perms)
+    legal = np.ones((n, _n_actions(arrs[0], arrs[2], arrs[3])), bool)
+    if T == 0:
+        return forward_f64_bound(arrs, (), (), obs, legal, np.full(n, -1), mode, emb_relu=emb_relu)
+    per = [forward_f64_bound(arrs, obs_perms, act_perms, obs, legal, np.full(n, pi), mode, emb_relu=emb_relu) for pi in range(T)]
+    g = _gamma("f32", T - 1)
+
+    def avg(xs, es):
+        term_err = sum((e + U32 * (np.abs(x) + e)) / T for x, e in zip(xs, es))
+        term_abs = sum((np.abs(x) + e) * (1 + U32) / T for x, e in zip(xs, es))
+        return _twist_average(xs), term_err + g * term_abs
+
+    logits, el = avg([p[0] for p in per], [p[2] for p in per])
+    values, ev = avg([p[1] for p in per], [p[3] for p in per])
+    return logits, values, el, ev
+
+
+def prob_bound(logits, err_logits, masks, exp_rel=EXP_REL):
+    """|f32 masked soft-max of logits l^ - masked_softmax_f64(l)| per entry, for |l^ - l| <= err_logits and a kernel that computes
+    e_i = exp(l^_i) (0 where masked), S = e_0 + .. + e_{A-1} in index order, p_i = e_i / (S + 1e-6f), every operation rounded to f32
+    (u = 2^-24):
+
+      e^_i = exp(l_i) (1 + a_i),   |a_i| <= rho_i = expm1(err_i) + exp_rel exp(err_i)     (the shifted argument, then the exp itself);
+      |S^ - sum e^_i| <= gamma(A - 1) sum e^_i                                              (A - 1 rounded additions of terms >= 0);
+      D^ = fl(S^ + fl(1e-6)):  |D^ - D| <= dD = sum rho_i e_i + gamma(A - 1) sum (1 + rho_i) e_i + 1e-6 u + u (D + the three before);
+      p^_i = fl(e^_i / D^)  =>  |p^_i - p_i| <= p_i ((1 + rho_i) (1 + u) / (1 - dD / D) - 1).
+
+    A masked entry is exactly 0 on both sides.  Holds while every number is a normal f32: raises outside |l| + err < EXP_RANGE."""
+    l = np.asarray(logits, np.float64)
+    m = np.asarray(masks, bool).reshape(l.shape)
+    el = np.where(m, np.asarray(err_logits, np.float64), 0.0)
+    if m.any() and float((np.abs(l) + el)[m].max()) >= EXP_RANGE:
+        raise ValueError("prob_bound: a legal logit outside the range the bound is derived for")
+    e = np.where(m, np.exp(np.where(m, l, 0.0)), 0.0)
+    rho = np.where(m, np.expm1(el) + exp_rel * np.exp(el), 0.0)
+    g = _gamma("f32", l.shape[1] - 1)
+    D = e.sum(axis=1) + SOFTMAX_EPS
+    dD = (rho * e).sum(axis=1) + g * ((1 + rho) * e).sum(axis=1) + SOFTMAX_EPS * U32
+    dD = dD + U32 * (D + dD)
+    rD = dD / D
+    if float(rD.max(initial=0.0)) >= 0.5:
+        raise ValueError("prob_bound: the logit errors are too large for a bound of the quotient")
+    want = e / D[:, None]
+    return want * ((1 + rho) * (1 + U32) / (1 - rD[:, None]) - 1)

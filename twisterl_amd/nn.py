@@ -107,7 +107,9 @@ class Policy:
         if len(self.obs_perms) != len(self.act_perms):
             raise ValueError("obs_perms and act_perms must have the same length.")
         self._h = None
-        self._n_actions = action_net.layers[-1].out_features if action_net.layers else 0
+        # an empty action Sequential hands its input on (modules.rs:28-34): the logits are the common output, or the embedding
+        self._n_actions = (action_net.layers[-1].out_features if action_net.layers else
+                           common.layers[-1].out_features if common.layers else int(embeddings.bias.size))
         self._rng = np.random.default_rng(int.from_bytes(os.urandom(8), "little"))
 
     def __del__(self):
