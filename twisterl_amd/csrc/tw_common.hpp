@@ -479,14 +479,6 @@ __device__ inline void store_rec(PaddedRec *dst, const uint32_t (&obs4)[4], cons
                       (uint32_t)(action & 0xff) | ((uint32_t)(perm & 0xff) << 8), 0u);
 }
 
-// the three 16-byte words of a stored record: obs bytes | logits | {value, reward, action | perm << 8, 0} (the rollout's
-// fast-forward rounds read the episode's own records back, tw_rollout.hip)
-__device__ inline void load_rec(const PaddedRec *src, uint4 &obs4, uint4 &lg4, uint4 &tail4)
-{
-    const uint4 *d = reinterpret_cast<const uint4 *>(src);
-    obs4 = d[0]; lg4 = d[1]; tail4 = d[2];
-}
-
 // four nibbles (16 bits) -> four bytes
 __host__ __device__ inline uint32_t spread_nibbles4(uint32_t t16)
 {
@@ -534,8 +526,8 @@ struct RolloutArgs {
     // split-f16 mode: starts as the policy's split_range word; the kernel ORs in 1 when an activation leaves the range of the
     // split (EngineS::out_of_range) -- the host then runs the collect again in f32 (tw_ppo_collect)
     uint32_t       *range_flag;
-    // 256-episode f32 shape: a step whose (board, twist) the episode recorded 2 or 4 steps ago takes that record's logits and
-    // value instead of a forward (tw_rollout.hip: fast-forward rounds).  `reused` counts those records (zeroed before the
+    // 256-episode f32 shape: a step whose (board, twist) the episode stood on 2 or 4 steps ago takes that step's logits and
+    // value instead of a forward (tw_rollout.hip: fast-forward rounds, look-back ring in LDS).  `reused` counts those records (zeroed before the
     // launch; one atomic per wave at the kernel's end); reuse_off != 0 (TW_OPT_ROLLOUT_REUSE = 1): no look-ups at all.
     unsigned int   *reused;
     uint32_t        reuse_off;

@@ -60,9 +60,9 @@ __device__ __forceinline__ float relu_lim_v(float x, float lim)
 // gumbel_argmax4 for a wave whose lanes l and l^32 carry the same episode (the same logits and draw): the lower half transforms
 // uniforms 0 and 1, the upper half 2 and 3 -- the same operations on other lanes, so the same bits -- and two v_permlane32_swap
 // give every lane all four perturbed logits; the argmax is gumbel_argmax4's (strict '>', first max wins, NaN never wins).
-__device__ __forceinline__ int gumbel_argmax4_halves(const float l[4], const u32x4 w, bool upper)
+// w0, w1: the two words this lane transforms (the draw's x, y on the lower half, z, w on the upper).
+__device__ __forceinline__ int gumbel_argmax4_words(const float l[4], uint32_t w0, uint32_t w1, bool upper)
 {
-    const uint32_t w0 = upper ? w.z : w.x, w1 = upper ? w.w : w.y;
     const float l0 = upper ? l[2] : l[0], l1 = upper ? l[3] : l[1];
     const float g0 = l0 - tw_logf(__builtin_fabsf(tw_logf(u32_to_unit(w0))));
     const float g1 = l1 - tw_logf(__builtin_fabsf(tw_logf(u32_to_unit(w1))));
@@ -99,7 +99,7 @@ constexpr int R3_LSTR  = R3_KC + 4;         // 20 floats per row
 constexpr int R3_TSLOT = 21 * 256;          // floats per table slot (21 KiB = 21 DMA pieces)
 
 template <int NT>
-__host__ __device__ inline size_t engine3_lds_floats(int obs_size)
+__host__ __device__ constexpr size_t engine3_lds_floats(int obs_size)
 {
     return (size_t)3 * R3_KC * Tiles<NT>::NQ * 128 + (size_t)3 * R3_TSLOT + (size_t)NT * 32 * 10 + 8 +
            (size_t)MAX_LDS_PERMS * ((obs_size + 3) / 4 + 1) + (size_t)NT * 32 * 5;

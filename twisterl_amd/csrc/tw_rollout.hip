@@ -183,10 +183,49 @@ int launch_episode_order(const PuzzleConsts &env, const uint64_t *boards, uint64
 TW_STAMP_ARRAY(g_gen_stamps, 8);   // cycle stamps of the generic engine and the 32- and 16-episode shapes (tw_common.hpp)
 
 // The tail of one step, shared by the forwarded step (RAW: `lg` comes out of the forward) and the fast-forward rounds of the
-// 256-episode shape (`lg` and `value` come out of one of the episode's own records: act-permuted and masked already): reward,
+// 256-episode shape (`lg` and `value` come out of the episode's look-back ring: act-permuted and masked already): reward,
 // Gumbel arg-max, the record, is_final / step, and in persistent mode the next episode off the queue.  `on`: this lane takes the
 // step (the forwarded step: every lane; a round: the lanes that hit).
 // entries of RolloutArgs::init_boards: the drain launch of a hand-over (the <NT, NC, -4, true> shape) reads the count the first launch left
+// Policy::get_perm_id of step t of an episode (policy.rs:67-77); n_perms > 0
+__device__ __forceinline__ int draw_twist(const RolloutArgs &a, int n_perms, uint32_t e_local, int t)
+{
+    const u32x4 w = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_PERM);
+    return (int)u32_below(w.x, (uint32_t)n_perms);
+}
+
+// Look-back ring of the 256-episode shape: the last RING_SLOTS steps of every episode of the workgroup, in LDS behind
+// the engine's image and the four counter words -- [slot][dword][episode] with the dwords board lo, hi | masked, act-permuted
+// logits | value, then one dword per episode with the slots' four twist bytes (perm & 0xff: 0xff without twists).  Step t sits in
+// slot t & 3.  Only the episode's writer lane stores; both lanes of the episode (j and j + 32 of one wave, whose LDS operations
+// execute in program order) read, so no barrier is involved.
+// Why a slot never answers for another step than the one asked for: a lane clears its episode's four twist bytes to RING_EMPTY
+// (byte 0xfd, which is no key: a twist index is below 128, "no twist" is 0xff, "twist not drawn yet" is 0xfe) before the kernel's
+// first step and whenever it takes a new episode off the queue, and it stores step t of an episode before it looks anything up at
+// a later step.  So the slots of t-2 and t-4 hold those very steps once this lane has run them, and RING_EMPTY before (t < 2,
+// t < 4, the steps a previous episode left there): the twist byte of such a slot equals no key, whatever its board words are
+// (unwritten LDS included).  A step whose twist is not drawn yet (the first one of an episode taken inside the rounds, key byte
+// 0xfe) equals no stored byte either.
+constexpr int      RING_SLOTS = 4, RING_DW = 7, RING_EPS = 8 * EPW;
+constexpr int      RING_AT    = 4;                                           // in dwords behind the engine's image: the counter words first
+constexpr size_t   RING_BYTES = (size_t)(RING_SLOTS * RING_DW + 1) * RING_EPS * 4;
+constexpr unsigned RING_EMPTY = 0xfdfdfdfdu;
+constexpr int      PERM_UNDRAWN = -2;                                        // (key byte 0xfe: no stored byte, so such a step never hits)
+static_assert(RING_BYTES == 116 * 256, "look-back ring: 116 bytes per episode");
+static_assert((engine3_lds_floats<8>(256) + RING_AT) * 4 + RING_BYTES <= 159 * 1024, "the look-back ring must fit behind the largest engine image (launch_geom checks every launch)");
+
+// (`ring`: the lane's own view, the ring's first dword + the episode's index inside the workgroup)
+__device__ __forceinline__ void ring_clear(unsigned *ring) { ring[RING_SLOTS * RING_DW * RING_EPS] = RING_EMPTY; }
+__device__ __forceinline__ void ring_put(unsigned *ring, int t, uint64_t board, int perm, const float (&lg)[4], float value)
+{
+    unsigned *e = ring + (t & (RING_SLOTS - 1)) * (RING_DW * RING_EPS);
+    e[0] = (uint32_t)board; e[RING_EPS] = (uint32_t)(board >> 32);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e[(2 + i) * RING_EPS] = __float_as_uint(lg[i]);
+    e[6 * RING_EPS] = __float_as_uint(value);
+    reinterpret_cast<uint8_t *>(ring + RING_SLOTS * RING_DW * RING_EPS)[t & (RING_SLOTS - 1)] = (uint8_t)(perm & 0xff);
+}
+
 template <int NW>
 __device__ __forceinline__ uint64_t queue_entries(const RolloutArgs &a)
 {
@@ -194,9 +233,12 @@ __device__ __forceinline__ uint64_t queue_entries(const RolloutArgs &a)
     return a.num_episodes;
 }
 
+// 256-episode shape (NW == 8): `perm` comes in as the twist of this step and goes out as the twist of the lane's pending step
+// (PERM_UNDRAWN where that is the first step of a new episode), and
+// the step's (board, twist) -> (logits, value) goes into the look-back ring (`ring`: the lane's view of it, below).
 template <int NW, bool PERSIST, bool RAW, class Eng>
-__device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleConsts &env, const Eng &eng, bool writer, bool on, int perm, float (&lg)[4], float value,
-                                          uint32_t &e_local, uint64_t &board, int &depth, int &t, bool &alive, bool &more, unsigned *wg_words = nullptr)
+__device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleConsts &env, const Eng &eng, bool writer, bool on, int &perm, float (&lg)[4], float value,
+                                          uint32_t &e_local, uint64_t &board, int &depth, int &t, bool &alive, bool &more, unsigned *wg_words = nullptr, unsigned *ring = nullptr)
 {
     const int j = eng.j, h = eng.h;
     PuzzleLane st; st.board = board; st.depth = depth;
@@ -208,10 +250,22 @@ __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleCons
         for (int i = 0; i < 4; ++i) lg[i] = ((mb >> i) & 1u) ? lg[i] : -1e10f;   // policy.rs:62
     }
     const float rew = puzzle_reward(st, env);
-    const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
-    int action;
-    if constexpr (NW == 8) action = gumbel_argmax4_halves(lg, gw, h != 0);   // (lanes j and j+32: one episode)
-    else action = gumbel_argmax4(lg, gw);
+    int action, perm_next = perm;
+    if constexpr (NW == 8) {
+        // Lanes j and j+32 carry one episode, so ONE Philox pass serves both draws the step needs: the lower half runs it for
+        // (episode, t, Gumbel), the upper half the same instructions for (episode, t + 1, twist) -- integer arithmetic, the same
+        // bits whichever lane computes a word.  swap(x, z): the first result holds the lower half's x (lower lanes) and z (upper
+        // lanes), the uniforms gumbel_argmax4_words transforms there; the second one hands the upper half's x, the twist word,
+        // to the lower lanes.
+        const u32x4 w = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)(t + h), h ? STREAM_PERM : STREAM_GUMBEL);
+        const auto s0 = __builtin_amdgcn_permlane32_swap(w.x, w.z, false, false);
+        const auto s1 = __builtin_amdgcn_permlane32_swap(w.y, w.w, false, false);
+        action = gumbel_argmax4_words(lg, s0[0], s1[0], h != 0);
+        if (eng.pol.n_perms > 0) perm_next = (int)u32_below(h ? w.x : s0[1], (uint32_t)eng.pol.n_perms);
+    } else {
+        const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
+        action = gumbel_argmax4(lg, gw);
+    }
     // ---- push the record (ppo.rs:71-76), then is_final / step (ppo.rs:78-79) --------------
     if (alive && on) {
         if (writer) {
@@ -220,11 +274,12 @@ __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleCons
             obs_base_words(env.n_cells, obs_base);
             obs_bytes(board, obs_base, pk);
             store_rec(a.out.rec + rec, pk, lg, value, rew, action, perm);
+            if constexpr (NW == 8) ring_put(ring, t, board, perm, lg, value);
         }
         if (puzzle_final(st, env)) {
             alive = false;
             if constexpr (PERSIST) { if (writer) a.out.ep_len[e_local] = (uint32_t)t + 1u; }
-        } else { puzzle_step(st, env, action); board = st.board; depth = st.depth; ++t; }
+        } else { puzzle_step(st, env, action); board = st.board; depth = st.depth; ++t; perm = perm_next; }
     }
     if constexpr (PERSIST) {
         const bool want = on && !alive && more;       // take the next episode off the queue (every lane of the episode the same one)
@@ -242,16 +297,19 @@ __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleCons
                 e_local = ib.z; board = ((uint64_t)ib.y << 32) | ib.x; t = (int)ib.w;
                 depth = env.depth0 > t ? env.depth0 - t : 0;
                 alive = true;
+                if constexpr (NW == 8) { if (writer) ring_clear(ring); }
             } else {
                 more = false;
                 if constexpr (NW == 8) { if (writer) wg_words[1] = 1u; }     // the queue never refills: from here on the workgroup only drains
             }
         }
+        // a lane that took a new episode: its pending step is not (episode, t + 1) -- the loop top draws that twist
+        if constexpr (NW == 8) perm = want && alive && eng.pol.n_perms > 0 ? PERM_UNDRAWN : perm;
     }
 }
 
 // Fast-forward rounds of the 256-episode shape: after a forwarded step every wave on its own takes up to REUSE_R
-// further steps whose output one of the episode's records of 2, 4, .. 2 * REUSE_LB steps ago holds (same obs bytes, same twist).
+// further steps whose output the episode's look-back ring holds from 2, 4, .. 2 * REUSE_LB steps ago (same board, same twist).
 #ifndef TW_REUSE_LB        // (-DTW_REUSE_LB / -DTW_REUSE_R with TW_VARIANT: the pairs measured in profiles/r10_rollout_reuse.txt)
 #define TW_REUSE_LB 2
 #endif
@@ -281,6 +339,24 @@ __device__ unsigned g_drain_anat[1024 * 8];
 #else
 #define TW_DRAIN_ANATOMY_INIT(w) do {} while (0)
 #define TW_DRAIN_ANATOMY_STEP(w, live, wg) do {} while (0)
+#endif
+
+// -DTW_STEP_ANATOMY (with -DTW_ABLATE, a TW_VARIANT build; TW_STAMPS=1 prints): where wave 0 of every workgroup of the 256-episode
+// shape spends an iteration of the step loop -- observe + forward | forwarded tail | rounds, of which the wait for the look-back
+// entries | the rest: the loop-top barrier (profiles/r15_rollout_lookback.txt).  No other build holds any of it.
+#if defined(TW_STEP_ANATOMY) && defined(TW_ABLATE)
+TW_STAMP_ARRAY(g_step_stamps, 8);
+#define TW_STEP_VARS(...)          unsigned long long __VA_ARGS__
+#define TW_STEP_STAMP(t)           TW_RESTAMP(t)
+#define TW_STEP_ADD(acc, t0, t1)   TW_STAMP_ADD(acc, t0, t1)
+#define TW_STEP_USE(x)             TW_STAMP_USE(x)
+constexpr bool STEP_ANATOMY = true;
+#else
+#define TW_STEP_VARS(...)          static_assert(true, "")
+#define TW_STEP_STAMP(t)           do {} while (0)
+#define TW_STEP_ADD(acc, t0, t1)   do {} while (0)
+#define TW_STEP_USE(x)             do {} while (0)
+constexpr bool STEP_ANATOMY = false;
 #endif
 
 // (the generic engine's workgroups are small -- 256 threads, exact-size activation buffers: two of them share a CU, and while one
@@ -324,7 +400,14 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
     // in a register would be live across the forward, which has none to spare
     // ([1]: "the queue is dry", set by whichever lane finds it so in step_tail)
     unsigned *reuse_cnt = nullptr;
-    if constexpr (NW == 8) { reuse_cnt = reinterpret_cast<unsigned *>(lds + Eng::lds_floats(a.pol)); if (threadIdx.x == 0) { reuse_cnt[0] = 0u; reuse_cnt[1] = 0u; TW_DRAIN_ANATOMY_INIT(reuse_cnt); } }
+    // (behind the four words: the look-back ring, every writer lane its own episode's part)
+    int perm = -1;                                        // 256-episode shape: the twist of the lane's pending step, handed on by step_tail
+    if constexpr (NW == 8) {
+        reuse_cnt = reinterpret_cast<unsigned *>(lds + Eng::lds_floats(a.pol));
+        if (threadIdx.x == 0) { reuse_cnt[0] = 0u; reuse_cnt[1] = 0u; TW_DRAIN_ANATOMY_INIT(reuse_cnt); }
+        if (writer) ring_clear(reuse_cnt + RING_AT + eng.ep_lane());
+        if (eng.pol.n_perms > 0) perm = PERSIST ? PERM_UNDRAWN : draw_twist(a, eng.pol.n_perms, e_local, t);
+    }
 
     // The loop runs while an episode of the workgroup lives.  Persistent 256-episode shape: the same barrier counts them, and once
     // the queue is dry and no more than drain_live are left the workgroup hands them over instead of running 256-column forwards
@@ -340,59 +423,70 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
             return false;
         } else return __syncthreads_or(alive ? 1 : 0) != 0;
     };
+    TW_STEP_VARS(sq0 = 0, sq1 = 0, sq2 = 0, s_fwd = 0, s_tail = 0, s_rounds = 0, s_wait = 0, s_iter = 0);
     while (go_on()) {
         TW_STAMP_COUNT(n_fwd, 1);
+        TW_STEP_STAMP(sq0);
         // ---- observe (puzzle.rs:183-185) + twist of the obs ids (policy.rs:67-83) -------------
-        int perm = -1;
-        if (eng.pol.n_perms > 0) {
-            const u32x4 w = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_PERM);
-            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
+        if constexpr (NW == 8) {
+            // step_tail left the twist of the pending step with the step before it; only a lane whose pending step is an episode's
+            // first one has none yet (persistent lanes: the first iteration, a lane that took an episode off the queue; the plain
+            // launch drew it in front of the loop): one more pass, wave-uniform
+            if constexpr (PERSIST) {
+                if (__builtin_amdgcn_ballot_w64(perm == PERM_UNDRAWN) != 0ull) {
+                    const int p = draw_twist(a, eng.pol.n_perms, e_local, t);
+                    perm = perm == PERM_UNDRAWN ? p : perm;
+                }
+            }
+        } else {
+            perm = -1;
+            if (eng.pol.n_perms > 0) perm = draw_twist(a, eng.pol.n_perms, e_local, t);
         }
         int rowoff[NC];
         eng.rows_of(board, env.n_cells, perm, rowoff);
 
         float lg[4]; float value;
         eng.forward(rowoff, lg, value);
+        TW_STEP_USE(value); TW_STEP_STAMP(sq1); TW_STEP_ADD(s_fwd, sq0, sq1);
 
-        step_tail<NW, PERSIST, true>(a, env, eng, writer, true, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt);
+        // the lane's view of the look-back ring, computed behind the forward (through an opaque copy of the lane's column: an address
+        // hoisted out of the loop would be one more register live across the forward)
+        unsigned *ring = nullptr;
+        if constexpr (NW == 8) { int jj = eng.j; asm volatile("" : "+v"(jj)); ring = reuse_cnt + RING_AT + eng.wave * EPW + jj; }
+        step_tail<NW, PERSIST, true>(a, env, eng, writer, true, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt, ring);
+        TW_STEP_USE(t); TW_STEP_USE(perm); TW_STEP_STAMP(sq2); TW_STEP_ADD(s_tail, sq1, sq2); TW_STEP_ADD(s_iter, 0, 1);
 
         // ---- fast-forward rounds: a step whose (board, perm) the episode recorded 2k steps ago takes that record's output -----
         if constexpr (NW == 8) {
             if (!a.reuse_off) {
-                bool cand = writer;                       // a lane that missed stays where it is: it would miss again
+                static_assert(2 * REUSE_LB <= RING_SLOTS, "the look-back ring holds the last RING_SLOTS steps");
+                bool cand = true;                         // a lane that missed stays where it is: it would miss again
 #pragma unroll 1
                 for (int r = 0; r < REUSE_R; ++r) {
-                    perm = -1;
-                    if (eng.pol.n_perms > 0) {
-                        const u32x4 w = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_PERM);
-                        perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
-                    }
-                    uint32_t obs_base[4], pk[4];
-                    obs_base_words(env.n_cells, obs_base);
-                    obs_bytes(board, obs_base, pk);
-                    const PaddedRec *cur = a.out.rec + (uint64_t)e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
-                    bool hit = false;
-                    uint4 hl = make_uint4(0u, 0u, 0u, 0u); uint32_t hv = 0u;
+                    TW_STEP_STAMP(sq0);
+                    // the pending step's key against the ring's entries of t-2 and t-4 (both lanes of the episode the same reads)
+                    const uint32_t tws = ring[RING_SLOTS * RING_DW * RING_EPS];
+                    bool hit = false; int hs = 0;
 #pragma unroll
-                    for (int k = REUSE_LB; k >= 1; --k) {             // (the nearer record last: it wins, though any match holds the same bits)
-                        if (cand && alive && t >= 2 * k) {            // the lane that stored the record reads it: program order
-                            uint4 ko, kl, kt;
-                            load_rec(cur - 2 * k, ko, kl, kt);
-                            if (ko.x == pk[0] && ko.y == pk[1] && ko.z == pk[2] && ko.w == pk[3] && (kt.z >> 8) == (uint32_t)(perm & 0xff)) { hit = true; hl = kl; hv = kt.x; }
-                        }
+                    for (int k = REUSE_LB; k >= 1; --k) {             // (the nearer step last: it wins, though any match holds the same bits)
+                        const int sl = (t - 2 * k) & (RING_SLOTS - 1);
+                        const unsigned *e = ring + sl * (RING_DW * RING_EPS);
+                        const uint32_t blo = e[0], bhi = e[RING_EPS];
+                        if (blo == (uint32_t)board && bhi == (uint32_t)(board >> 32) && ((tws >> (8 * sl)) & 0xffu) == (uint32_t)(perm & 0xff)) { hit = true; hs = sl; }
                     }
+                    hit = hit && cand && alive;
+                    TW_STEP_USE(hit ? 1 : 0); TW_STEP_STAMP(sq1); TW_STEP_ADD(s_wait, sq0, sq1);
                     const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
                     if (hm == 0ull) break;
-                    if (hit) atomicAdd(reuse_cnt, 1u);
+                    if (hit && writer) atomicAdd(reuse_cnt, 1u);
                     cand = hit;
-                    // lane j -> lane j + 32 (swap(x, x)[0]: the lower half's x in every lane), as the Gumbel halves cross
-                    auto low = [](uint32_t x) { return __builtin_amdgcn_permlane32_swap(x, x, false, false)[0]; };
-                    const bool on = low(hit ? 1u : 0u) != 0u;
-                    lg[0] = __uint_as_float(low(hl.x)); lg[1] = __uint_as_float(low(hl.y));
-                    lg[2] = __uint_as_float(low(hl.z)); lg[3] = __uint_as_float(low(hl.w));
-                    value = __uint_as_float(low(hv));
-                    step_tail<NW, PERSIST, false>(a, env, eng, writer, on, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt);
+                    const unsigned *e = ring + hs * (RING_DW * RING_EPS);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) lg[i] = __uint_as_float(e[(2 + i) * RING_EPS]);
+                    value = __uint_as_float(e[6 * RING_EPS]);
+                    step_tail<NW, PERSIST, false>(a, env, eng, writer, hit, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt, ring);
                 }
+                TW_STEP_USE(t); TW_STEP_STAMP(sq1); TW_STEP_ADD(s_rounds, sq2, sq1);
             }
         }
     }
@@ -404,6 +498,10 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
     }
     if constexpr (!PERSIST) { if (valid && writer) a.out.ep_len[e_local] = (uint32_t)t + 1u; }
     eng.end();
+    if constexpr (NW == 8 && STEP_ANATOMY) {              // wave 0: forward | tail | rounds | of those the look-back wait; iterations; cycles in the step loop
+        TW_STEP_STAMP(sq1);
+        TW_STAMP_FLUSH(eng.lane == 0 && eng.wave == 0, g_step_stamps, s_fwd, s_tail, s_rounds, s_wait, s_iter, sq1 - q_loop);
+    }
     if constexpr (NW == -65)                              // waves 0 and 3: embed | common | value | action
         TW_STAMP_FLUSH(eng.lane == 0 && (eng.wave == 0 || eng.wave == 3), g_gen_stamps + (eng.wave ? 4 : 0), eng.stq[0], eng.stq[1], eng.stq[2], eng.stq[3]);
     if constexpr (NW == -16 || NW == -4) {                // wave 0: prologue | chunk loop | - | - | heads; forwards; cycles in the step loop
@@ -455,12 +553,13 @@ static int launch_geom(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, ui
     constexpr int EPB = G::Eng::EPB, THREADS = 64 * G::WAVES;
     const uint64_t nb = PERSIST ? persist_blocks(a.reserve_cus) * (NW == -65 ? generic_groups_per_cu(a.pol, a.env.n_cells) : 1) : (a.num_episodes + EPB - 1) / EPB;
     if (nb == 0 || nb > 0x7fffffffull) { set_error("rollout: bad episode count %llu", (unsigned long long)a.num_episodes); return TW_ERR_INVALID; }
-    const size_t lds_bytes = G::Eng::lds_floats(a.pol) * sizeof(float) + (NW == 8 ? 16 : 0);    // (+ the 256-episode shape's reuse counter)
+    const size_t lds_bytes = G::Eng::lds_floats(a.pol) * sizeof(float) + (NW == 8 ? RING_AT * 4 + RING_BYTES : 0);    // (+ the 256-episode shape's counter words and look-back ring)
     if (lds_bytes > 159 * 1024) { set_error("rollout: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
     if (NW == 8 && !a.reused && !a.reuse_off) { set_error("rollout: the 256-episode shape needs RolloutArgs::reused (or reuse_off)"); return TW_ERR_INVALID; }
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&rollout_f32_kernel<NT, NC, NW, PERSIST>), lds_bytes)) return rc;
     constexpr bool STAMPED = NW == -65 || NW == -16 || NW == -4;      // the shapes that take cycle stamps
     if constexpr (STAMPED) TW_STAMPS_CLEAR(g_gen_stamps);
+    if constexpr (NW == 8 && STEP_ANATOMY) TW_STAMPS_CLEAR(g_step_stamps);
     hipLaunchKernelGGL((rollout_f32_kernel<NT, NC, NW, PERSIST>), dim3((unsigned)nb), dim3(THREADS), lds_bytes, s, a);
     if constexpr (STAMPED) TW_STAMPS_REPORT(g_gen_stamps, s, g, {
         if (NW == -65)
@@ -469,6 +568,12 @@ static int launch_geom(const RolloutArgs &a, hipStream_t s, uint32_t *blocks, ui
         else
             fprintf(stderr, "[geometry %d, wave 0, cycles per forward] prologue %.0f chunk loop %.0f heads %.0f | whole step %.0f (%llu forwards)\n",
                     NW, (double)g[0] / g[5], (double)g[1] / g[5], (double)g[4] / g[5], (double)g[6] / g[5], g[5]);
+    });
+    if constexpr (NW == 8 && STEP_ANATOMY) TW_STAMPS_REPORT(g_step_stamps, s, g, {
+        const double n = (double)g[4];
+        fprintf(stderr, "[step anatomy, wave 0 of %llu workgroups, cycles per iteration] observe + forward %.0f | forwarded tail %.0f | rounds %.0f (look-back wait %.0f) | "
+                        "barrier %.0f | whole %.0f (%.1f iterations per workgroup)\n", (unsigned long long)nb, g[0] / n, g[1] / n, g[2] / n, g[3] / n,
+                ((double)g[5] - g[0] - g[1] - g[2]) / n, g[5] / n, n / (double)nb);
     });
     TW_HIP(hipGetLastError());
 #ifdef TW_DRAIN_ANATOMY
