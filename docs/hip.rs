@@ -123,6 +123,9 @@ extern "C" {
     // test hooks: the collectors' tail (scan, finalize, movers) on host records the caller wrote; a result's whole arena with its field offsets
     #[allow(dead_code)] fn tw_debug_collect_tail(args: *const c_void, launched: *mut c_void, out: *mut *mut c_void) -> c_int;
     #[allow(dead_code)] fn tw_debug_collected_arena(c: *const c_void, out: *mut c_void, cap: u64, bytes: *mut u64, offsets: *mut u64, scratch: *mut u64) -> c_int;
+    // test hook: on != 0, every device buffer the library hands to a call (workspace, result arena, call-local scratch) is set to `pattern`
+    // before its first use; process-wide, off by default (TW_DEBUG_FILL=<hex word> in the environment: the initial value)
+    #[allow(dead_code)] fn tw_debug_fill_memory(on: c_int, pattern: u32) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {

@@ -184,6 +184,13 @@ int tw_debug_collect_tail(const tw_debug_tail_args *args, tw_finalize_launch *la
  * offsets[TW_F_COUNT]: where each field starts in it (its length: tw_collected_device_ptr); scratch[2]: offset and length of the
  * four-column logits the finalize kernel wrote behind the fields when the result has other than four columns (0, 0: none). */
 int tw_debug_collected_arena(const struct tw_collected *c, void *out, uint64_t cap, uint64_t *bytes, uint64_t *offsets, uint64_t *scratch);
+/* Test hook: on != 0 -- from now on every device buffer the library hands to a call is set to the 32-bit `pattern` over its whole
+ * capacity, on the call's stream, before the call's first use of it: the cached trajectory workspace (on a cache hit as on a fresh
+ * allocation), a result arena (pooled or fresh), every call-local scratch allocation, the gather arena.  Policy images are not
+ * touched.  on == 0 (the default): nothing is filled.  The state is process-wide; the environment variable TW_DEBUG_FILL=<hex word>,
+ * read once when the library is loaded, gives its initial value.  No result may depend on what device memory held before a call:
+ * with any pattern every entry point returns the bytes it returns with the hook off. */
+int tw_debug_fill_memory(int on, uint32_t pattern);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Env: host object with the PyBaseEnv / Puzzle surface.  Collectors only read its          */

@@ -135,6 +135,11 @@ def _collect(tw, r, env, gp, E):
 @pytest.mark.parametrize("E", EPISODES)
 @pytest.mark.parametrize("module", IDS)
 def test_ppo_collect(tw, module, E):
+    check_ppo_collect(tw, module, E)
+
+
+def check_ppo_collect(tw, module, E):
+    """-> the device collect that was checked"""
     from twisterl_amd import _lib
     r, env, gp, _ = _setup(module)
     g = _collect(tw, r, env, gp, E)
@@ -144,12 +149,18 @@ def test_ppo_collect(tw, module, E):
     assert h.stats["rollout_threads"] == 0
     _same_bytes(g, h)
     _ppo_same_as_oracle(g, shared_collect(module, E), r)
+    return g
 
 
 # ---- 2. PPO collect on a persistent grid of one and two workgroups: 100 episodes on 16 (32) columns, every column takes several -------------------
 @pytest.mark.parametrize("groups", [1, 2])
 @pytest.mark.parametrize("module", IDS)
 def test_ppo_collect_queued(tw, module, groups):
+    check_ppo_collect_queued(tw, module, groups)
+
+
+def check_ppo_collect_queued(tw, module, groups):
+    """-> the collect on the persistent grid that was checked"""
     from twisterl_amd import _lib
     r, env, gp, _ = _setup(module)
     E = 100
@@ -161,6 +172,7 @@ def test_ppo_collect_queued(tw, module, groups):
     _assert_launch(_lib.TW_KERNEL_ROLLOUT_BIG, r, 0, (E + 15) // 16)
     _same_bytes(g, p)
     _ppo_same_as_oracle(g, shared_collect(module, E), r)
+    return g
 
 
 # ---- 3. evaluate without MCTS: deterministic (100 attempts) and sampled with 2 searches (80 attempts); plain and queued ---------------------------
@@ -214,6 +226,11 @@ class _Counted:
 @pytest.mark.parametrize("E,S,med", AZ_CASES)
 @pytest.mark.parametrize("module", SEARCH_IDS)
 def test_self_play(tw, det_exp, module, E, S, med):
+    check_self_play(tw, det_exp, module, E, S, med)
+
+
+def check_self_play(tw, det_exp, module, E, S, med):
+    """-> the device self-play that was checked"""
     r, env, gp, op = _setup(module)
     g = tw.collector.AZCollector(E, S, 1.41, med, 4, episode_offset=r.offset).collect(env, gp, seed=r.seed)
     _assert_search_launch(r, E, False)
@@ -233,6 +250,7 @@ def test_self_play(tw, det_exp, module, E, S, med):
         assert g.obs == o.obs_lists
     assert 1 in o.ep_len.tolist() and len(set(o.ep_len.tolist())) >= 3                 # episodes final at reset are searched and recorded too
     assert g.stats["forward_evals"] == cop.n * max(r.twists, 1), (g.stats["forward_evals"], cop.n, r.twists)
+    return g
 
 
 # ---- 5. search rows: MCTS-guided evaluate ---------------------------------------------------------------------------------------------------------------

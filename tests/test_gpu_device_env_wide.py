@@ -137,6 +137,11 @@ def _collect(tw, r, env, gp):
 # ---- 1. PPO collect, one column per episode ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("module", IDS)
 def test_ppo_collect(tw, module):
+    check_ppo_collect(tw, module)
+
+
+def check_ppo_collect(tw, module):
+    """-> the device collect that was checked"""
     from twisterl_amd import _lib
     r, env, gp, _ = _setup(module)
     g = _collect(tw, r, env, gp)
@@ -146,11 +151,17 @@ def test_ppo_collect(tw, module):
     assert h.stats["rollout_threads"] == 0
     _ppo_same_as_oracle(g, shared_collect(module), r)
     _same_bytes(g, h)
+    return g
 
 
 # ---- 2. PPO collect on a persistent grid of ONE workgroup: 40 episodes on 16 columns -----------------------------------------------------------
 @pytest.mark.parametrize("module", IDS)
 def test_ppo_collect_queued(tw, module):
+    check_ppo_collect_queued(tw, module)
+
+
+def check_ppo_collect_queued(tw, module):
+    """-> the collect on the persistent grid that was checked"""
     from twisterl_amd import _lib
     r, env, gp, _ = _setup(module)
     with _hook(1):
@@ -159,6 +170,7 @@ def test_ppo_collect_queued(tw, module):
         assert g.stats["rollout_blocks"] == 1 and g.stats["rollout_threads"] == 256
     _ppo_same_as_oracle(g, shared_collect(module), r)
     _same_bytes(g, _host_collect(env, gp, r.seed))
+    return g
 
 
 # ---- 3. evaluate: deterministic and sampled, 2 attempts per episode; plain and queued ------------------------------------------------------------

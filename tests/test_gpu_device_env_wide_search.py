@@ -94,6 +94,11 @@ def _message(fn):
 # ---- 1. self-play: the host-stepped path's bytes, the oracle's fields ------------------------------------------------------------------------------
 @pytest.mark.parametrize("module", IDS)
 def test_self_play_equals_host_path_and_oracle(tw, det_exp, module):
+    check_self_play(tw, det_exp, module)
+
+
+def check_self_play(tw, det_exp, module):
+    """-> the device self-play that was checked"""
     r, env, gp, _ = _setup(module, det_exp)
     assert env.search is True
     g = tw.collector.AZCollector(E, r.S, C_UCB, r.med, 4).collect(env, gp, seed=r.seed)
@@ -112,6 +117,7 @@ def test_self_play_equals_host_path_and_oracle(tw, det_exp, module):
     assert np.array_equal(f32_bits(a["remaining_values"]), f32_bits(o.remaining_values))
     n_tw = max(r.twists, 1)
     assert g.stats["forward_evals"] == o.evals * n_tw and g.stats["forward_evals"] % n_tw == 0      # full_predict averages ALL twists
+    return g
 
 
 # ---- 2. MCTS-guided evaluate: deterministic with 1 attempt, sampled with 2 -------------------------------------------------------------------------

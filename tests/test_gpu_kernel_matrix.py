@@ -87,10 +87,11 @@ def _check_bounds(a, arrs, op, ap, mode, label, emb_relu=True, also_1e5=False):
     return float(np.max(dl[masks])), float(np.max(dv))
 
 
-def _row_policy(oracle, row):
+def _row_policy(oracle, row, seed=None):
+    """The row's policy arrays and twists; `seed`: other weights of the same shapes (default: the row's index in the table)."""
     n2 = row.w * row.h
     op, ap = puzzle_transpose_twist(row.w) if row.twists else ([], [])
-    seed = km.TABLE.index(row)
+    seed = km.TABLE.index(row) if seed is None else seed
     if row.common is not None:
         arrs = make_deep_policy_arrays(n2, seed=seed, emb=row.emb, common=row.common, scale=2.0)
     else:
@@ -98,8 +99,8 @@ def _row_policy(oracle, row):
     return arrs, op, ap
 
 
-@pytest.mark.parametrize("row", km.TABLE, ids=[km.row_id(r) for r in km.TABLE])
-def test_every_rollout_kernel_against_the_oracle_and_the_f64_bound(tw, oracle, cus, row):
+def check_row(tw, oracle, cus, row):
+    """One row of the table: the launch shape, then the oracle and the float64 bound.  -> the collect that was checked."""
     arrs, op, ap = _row_policy(oracle, row)
     gp, opol = _policy(tw, arrs, op, ap), oracle.Policy(*arrs, op, ap)
     seed = 100 + km.TABLE.index(row)
@@ -112,7 +113,7 @@ def test_every_rollout_kernel_against_the_oracle_and_the_f64_bound(tw, oracle, c
                                det_log=True, merge_order=False, num_threads=_threads())
         _assert_same_collect(g, o, row.w * row.h)
         _check_bounds(g.to_numpy(), arrs, op, ap, "f32", label)
-        return
+        return g
     a = g.to_numpy()
     n_perms = len(op)
     if row.prec == "fp16":
@@ -122,6 +123,12 @@ def test_every_rollout_kernel_against_the_oracle_and_the_f64_bound(tw, oracle, c
         worst = _check_f16_collect(oracle, a, opol, row.w, row.h, row.diff, seed, n_perms, range(row.E), arith=oracle.ARITH_REF, atol=1e-5)
         assert worst < 1e-5, (label, worst)
         _check_bounds(a, arrs, op, ap, "fp16x2", label, also_1e5=True)
+    return g
+
+
+@pytest.mark.parametrize("row", km.TABLE, ids=[km.row_id(r) for r in km.TABLE])
+def test_every_rollout_kernel_against_the_oracle_and_the_f64_bound(tw, oracle, cus, row):
+    check_row(tw, oracle, cus, row)
 
 
 # ------------------------------------------------------------------------------ operand range of the f16 modes
@@ -156,9 +163,8 @@ def _range_case(n2, case):
 RANGE_CASES = ["h1_250", "h1_300", "h0_4000", "h0_5000", "head_5000", "tiny", "no_relu_neg"]
 
 
-@pytest.mark.parametrize("w", [3, 4])
-@pytest.mark.parametrize("case", RANGE_CASES)
-def test_f16_modes_at_the_edges_of_their_operand_range(tw, oracle, cus, w, case):
+def check_range_case(tw, oracle, cus, w, case):
+    """One operand-range case of the f16 modes.  -> (the fp16x2 collect, inside the split's range?)"""
     n2, E, diff, seed = w * w, 300, 4, 7
     arrs, relu, inside = _range_case(n2, case)
     gp, opol = _policy(tw, arrs, [], [], emb_relu=relu), oracle.Policy(*arrs, emb_relu=relu)
@@ -186,3 +192,10 @@ def test_f16_modes_at_the_edges_of_their_operand_range(tw, oracle, cus, w, case)
         assert shape(g2) == shape(g32), (case, g2.stats)
         for k in a32:
             assert np.array_equal(a2[k], a32[k]), (case, k)
+    return g2, inside
+
+
+@pytest.mark.parametrize("w", [3, 4])
+@pytest.mark.parametrize("case", RANGE_CASES)
+def test_f16_modes_at_the_edges_of_their_operand_range(tw, oracle, cus, w, case):
+    check_range_case(tw, oracle, cus, w, case)

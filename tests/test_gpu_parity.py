@@ -504,16 +504,10 @@ def test_generic_policy_with_more_episodes_than_lanes_uses_the_queue(tw, oracle)
 
 
 # ------------------------------------------------------------------------------ any environment
-@pytest.mark.parametrize("w,h,steps,emb,common,E", [(3, 3, 8, 64, (64,), 120), (5, 5, 12, 64, (128, 32), 60)])
-def test_ppo_collect_of_a_python_environment(tw, oracle, w, h, steps, emb, common, E):
-    """PPOCollector.collect on an environment the library does not implement (the reference collects any Box<dyn Env>;
-    its example is examples/grid_world): a GridWorld written in Python behind twisterl.env.PyEnv.  The env's code runs on the
-    host, the policy forward of every time step is one batched launch; the whole CollectedData is bit-equal to the oracle's
-    generic restatement of ppo.rs:41-126 running the same env class.  5 x 5: 625 obs ids (two-byte ids in the result)."""
-    from tests.gridworld_env import GridWorld
-    from tests.util import make_deep_policy_arrays
+def python_env_policy_arrays(w, h, emb, common, seed=13):
+    """The weights of the Python GridWorld's policy (seed 13: the test's; another seed: other weights of the same shapes)."""
     n = w * h
-    rng = np.random.default_rng(13)
+    rng = np.random.default_rng(seed)
     lin = lambda i, o, relu: (np.ascontiguousarray(rng.uniform(-2 / np.sqrt(i), 2 / np.sqrt(i), size=(o, i)).astype(np.float32).T).reshape(-1),
                               rng.uniform(-1 / np.sqrt(i), 1 / np.sqrt(i), size=o).astype(np.float32), relu)
     we = rng.uniform(-0.3, 0.3, size=(n * n, emb)).astype(np.float32)
@@ -521,16 +515,60 @@ def test_ppo_collect_of_a_python_environment(tw, oracle, w, h, steps, emb, commo
     cs, width = [], emb
     for hdim in common:
         cs.append(lin(width, hdim, True)); width = hdim
-    arrs = (we, be, cs, [lin(width, 4, False)], [lin(width, 1, False)])
-    gp, op = amd_policy(arrs), oracle_policy(oracle, arrs)
+    return (we, be, cs, [lin(width, 4, False)], [lin(width, 1, False)])
+
+
+def python_env(tw, w, h, steps):
+    """-> (the GridWorld written in Python, twisterl.env.PyEnv over it at difficulty 3)"""
+    from tests.gridworld_env import GridWorld
     proto = GridWorld(w, h, steps)
     env = tw.env.PyEnv(proto)
     env.difficulty = 3
+    return proto, env
+
+
+def check_python_env_ppo(tw, oracle, proto, env, gp, op, n, E, merge_order):
+    g = tw.collector.PPOCollector(E, 0.99, 0.95, 4, merge_order=merge_order).collect(env, gp, seed=77)
+    o = oracle.ppo_collect_env(proto, op, E, 0.99, 0.95, seed=77, difficulty=3, merge_order=merge_order)
+    _assert_same_collect(g, o, n)
+    return g
+
+
+def check_python_env_self_play(tw, oracle, proto, env, gp, op, n, E, S, med):
+    """(under oracle.set_det_exp(True))"""
+    z = tw.collector.AZCollector(min(E, 16), S, 1.41, med, 4).collect(env, gp, seed=79)
+    zo = oracle.az_collect_env(proto, op, min(E, 16), S, 1.41, med, seed=79, difficulty=3)
+    _assert_same_az(z, zo, n)
+    return z
+
+
+def check_python_env_evaluate_and_solve(tw, oracle, proto, env, gp, op, det, ns, S):
+    """(under oracle.set_det_exp(True)) -> (evaluate's result, solve's result)"""
+    ge = tw.collector.evaluate(env, gp, num_episodes=12, deterministic=det, num_searches=ns, num_mcts_searches=S, seed=5, C=1.41,
+                               max_expand_depth=1, num_cores=4)
+    oe = oracle.evaluate_env(proto, op, 12, det, ns, S, 1.41, 1, seed=5, difficulty=3)
+    assert f32_bits(ge[0]) == f32_bits(oe[0]) and f32_bits(ge[1]) == f32_bits(oe[1]), (det, ns, S, ge, oe)
+    cur = proto.copy(); cur.seed_episode(3, 1); cur.reset(3)
+    (gs, gr), gact = tw.collector.solve(tw.env.PyEnv(cur), gp, det, ns, S, 1.41, 1, seed=9)
+    (os_, or_), oact = oracle.solve_env(cur, op, det, ns, S, 1.41, 1, seed=9)
+    assert (gs, f32_bits(gr)) == (os_, f32_bits(or_)) and gact == list(oact), (det, ns, S)
+    return ge, ((gs, gr), gact)
+
+
+@pytest.mark.parametrize("w,h,steps,emb,common,E", [(3, 3, 8, 64, (64,), 120), (5, 5, 12, 64, (128, 32), 60)])
+def test_ppo_collect_of_a_python_environment(tw, oracle, w, h, steps, emb, common, E):
+    """PPOCollector.collect on an environment the library does not implement (the reference collects any Box<dyn Env>;
+    its example is examples/grid_world): a GridWorld written in Python behind twisterl.env.PyEnv.  The env's code runs on the
+    host, the policy forward of every time step is one batched launch; the whole CollectedData is bit-equal to the oracle's
+    generic restatement of ppo.rs:41-126 running the same env class.  5 x 5: 625 obs ids (two-byte ids in the result)."""
+    from tests.gridworld_env import GridWorld
+    n = w * h
+    arrs = python_env_policy_arrays(w, h, emb, common)
+    gp, op = amd_policy(arrs), oracle_policy(oracle, arrs)
+    proto, env = python_env(tw, w, h, steps)
     assert env.num_actions() == 4 and env.obs_shape() == [n, n]
     for merge_order in (True, False):
-        g = tw.collector.PPOCollector(E, 0.99, 0.95, 4, merge_order=merge_order).collect(env, gp, seed=77)
-        o = oracle.ppo_collect_env(proto, op, E, 0.99, 0.95, seed=77, difficulty=3, merge_order=merge_order)
-        _assert_same_collect(g, o, n)
+        g = check_python_env_ppo(tw, oracle, proto, env, gp, op, n, E, merge_order)
     a = g.to_numpy()
     assert a["obs"].dtype == (np.uint16 if n * n > 256 else np.uint8)
     assert (a["ep_len"] <= steps + 1).all() and a["ep_len"].min() >= 1
@@ -540,19 +578,10 @@ def test_ppo_collect_of_a_python_environment(tw, oracle, w, h, steps, emb, commo
     oracle.set_det_exp(True)
     try:
         for S, med in ((8, 1), (5, 2)):
-            z = tw.collector.AZCollector(min(E, 16), S, 1.41, med, 4).collect(env, gp, seed=79)
-            zo = oracle.az_collect_env(proto, op, min(E, 16), S, 1.41, med, seed=79, difficulty=3)
-            _assert_same_az(z, zo, n)
+            check_python_env_self_play(tw, oracle, proto, env, gp, op, n, E, S, med)
         # evaluate / solve of the same environment (tw_evaluate_env / tw_solve_env), plain and MCTS-guided
         for det, ns, S in ((True, 1, 0), (False, 3, 0), (False, 2, 4)):
-            ge = tw.collector.evaluate(env, gp, num_episodes=12, deterministic=det, num_searches=ns, num_mcts_searches=S, seed=5, C=1.41,
-                                       max_expand_depth=1, num_cores=4)
-            oe = oracle.evaluate_env(proto, op, 12, det, ns, S, 1.41, 1, seed=5, difficulty=3)
-            assert f32_bits(ge[0]) == f32_bits(oe[0]) and f32_bits(ge[1]) == f32_bits(oe[1]), (det, ns, S, ge, oe)
-            cur = proto.copy(); cur.seed_episode(3, 1); cur.reset(3)
-            (gs, gr), gact = tw.collector.solve(tw.env.PyEnv(cur), gp, det, ns, S, 1.41, 1, seed=9)
-            (os_, or_), oact = oracle.solve_env(cur, op, det, ns, S, 1.41, 1, seed=9)
-            assert (gs, f32_bits(gr)) == (os_, f32_bits(or_)) and gact == list(oact), (det, ns, S)
+            check_python_env_evaluate_and_solve(tw, oracle, proto, env, gp, op, det, ns, S)
     finally:
         oracle.set_det_exp(False)
 

@@ -90,8 +90,20 @@ def same_bytes(a, o, n_cells):
         assert np.array_equal(f32_bits(a[f]), f32_bits(ref)), f
 
 
+def collect_shape(tw, name, gp, off=0):
+    """One collect of a shape with the fast-forward rounds on (off = 0) or off (1)."""
+    _, side, diff, twists, E, geom = next(s for s in SHAPES if s[0] == name)
+    with _lib.launch_option(_lib.TW_OPT_FORCE_GEOM, geom), _lib.launch_option(_lib.TW_OPT_ROLLOUT_REUSE, off):
+        return tw.collector.PPOCollector(E, 0.995, 0.995, 32, merge_order=False).collect(tw.env.Puzzle(side, side, diff, 2, 256), gp, seed=SEED)
+
+
 @pytest.mark.parametrize("name", [s[0] for s in SHAPES])
 def test_reused_records_keep_the_oracles_bytes(tw, oracle, name):
+    check_shape(tw, oracle, name)
+
+
+def check_shape(tw, oracle, name):
+    """-> the collect with the rounds on that was checked."""
     _, side, diff, twists, E, geom = next(s for s in SHAPES if s[0] == name)
     arrs, op, ap, o, lo, hi, lo_ends = reference(oracle, name)
     print(f"[{name}] records {len(o.values)} lo {lo} hi {hi} hits at t-2 that end an episode {lo_ends}")
@@ -99,15 +111,8 @@ def test_reused_records_keep_the_oracles_bytes(tw, oracle, name):
     if twists:
         assert lo_ends > 0                                # ... and an episode that ends on a hit (depth out / queue refill inside a round)
     gp = amd_policy(arrs, op, ap)
-    env = tw.env.Puzzle(side, side, diff, 2, 256)
-
-    def collect(off):
-        with _lib.launch_option(_lib.TW_OPT_FORCE_GEOM, geom), _lib.launch_option(_lib.TW_OPT_ROLLOUT_REUSE, off):
-            g = tw.collector.PPOCollector(E, 0.995, 0.995, 32, merge_order=False).collect(env, gp, seed=SEED)
-        return g.to_numpy(), g.stats
-
-    a_on, st_on = collect(0)
-    a_off, st_off = collect(1)
+    g_on, g_off = collect_shape(tw, name, gp, 0), collect_shape(tw, name, gp, 1)
+    (a_on, st_on), (a_off, st_off) = (g_on.to_numpy(), g_on.stats), (g_off.to_numpy(), g_off.stats)
     if geom == 0:
         assert st_on["rollout_blocks"] * 256 < E          # persistent lanes: fewer lanes than episodes, the queue refills them
     print(f"[{name}] reused_evals on {st_on['reused_evals']} off {st_off['reused_evals']} launch {st_on['rollout_blocks']} x {st_on['rollout_threads']}")
@@ -118,3 +123,4 @@ def test_reused_records_keep_the_oracles_bytes(tw, oracle, name):
     assert st_off["reused_evals"] == 0
     assert st_on["forward_evals"] == st_off["forward_evals"] == len(o.values)
     assert lo <= st_on["reused_evals"] <= hi, (lo, st_on["reused_evals"], hi)
+    return g_on

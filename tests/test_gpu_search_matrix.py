@@ -87,8 +87,9 @@ def options(row):
         yield
 
 
-def policies(oracle, row):
-    n2, idx = row.w * row.h, sm.TABLE.index(row)
+def policies(oracle, row, seed=None):
+    """(the library's policy, the oracle's) of a row; `seed`: other weights of the same shapes (default: the row's index in the table)."""
+    n2, idx = row.w * row.h, sm.TABLE.index(row) if seed is None else seed
     op, ap = puzzle_transpose_twist(row.w) if row.twists else ((), ())
     if row.common is not None:
         arrs = make_deep_policy_arrays(n2, seed=idx, emb=row.emb, common=row.common, scale=2.0)
@@ -99,19 +100,24 @@ def policies(oracle, row):
 
 def merged_too(row):
     """The rows that are also collected in the merged order: every eighth one, and the first row of every family."""
+    if row not in sm.TABLE:                                           # (a further case of a kernel that has its row: tests/memory_matrix.py)
+        return False
     idx = sm.TABLE.index(row)
     fam = lambda r: sm.dispatch(r, 256)[0][0]
     return idx % 8 == 0 or all(fam(r) != fam(row) for r in sm.TABLE[:idx])
 
 
-def run_self_play(tw, oracle, cus, row, gp, opol, seed):
-    n2 = row.w * row.h
-    genv, oenv = tw.env.Puzzle(row.w, row.h, row.diff, 2, 256), oracle.Puzzle(row.w, row.h, row.diff, 2, 256)
+def collect_self_play(tw, cus, row, gp, seed, merge_order=False):
+    coll = tw.collector.AZCollector(row.E, row.S, 1.41, row.med, 32, merge_order=merge_order, reserve_cus=sm.reserve_cus(row, cus))
+    with options(row):
+        return coll.collect(tw.env.Puzzle(row.w, row.h, row.diff, 2, 256), gp, seed=seed)
 
-    def collect(merge_order):
-        coll = tw.collector.AZCollector(row.E, row.S, 1.41, row.med, 32, merge_order=merge_order, reserve_cus=sm.reserve_cus(row, cus))
-        with options(row):
-            return coll.collect(genv, gp, seed=seed)
+
+def run_self_play(tw, oracle, cus, row, gp, opol, seed):
+    """-> the collect (records in episode order) that was checked."""
+    n2 = row.w * row.h
+    oenv = oracle.Puzzle(row.w, row.h, row.diff, 2, 256)
+    collect = lambda merge_order: collect_self_play(tw, cus, row, gp, seed, merge_order)
 
     g = collect(False)
     kernel = assert_launch(row, cus, g.stats)
@@ -133,24 +139,37 @@ def run_self_play(tw, oracle, cus, row, gp, opol, seed):
         assert_launch(row, cus, m.stats)
         _assert_same_az(m, oracle.az_collect(oenv, opol, row.E, row.S, 1.41, row.med, seed=seed, arith=oracle.ARITH_CHAIN, num_threads=_threads(),
                                              merge_order=True, det_math=True), n2)
+    return g
 
 
-def run_evaluate(tw, oracle, cus, row, gp, opol, seed):
+def call_evaluate(tw, oracle, row, gp, seed):
+    """The row's evaluate or solve (from episode 3's start board) -> (genv, start state or None, (success, reward), actions or None)."""
     solve = row.entry == "solve"
     max_depth = SOLVE_MAX_DEPTH if solve else 256
-    genv, oenv = tw.env.Puzzle(row.w, row.h, row.diff, 2, max_depth), oracle.Puzzle(row.w, row.h, row.diff, 2, max_depth)
-    kw = dict(num_mcts_searches=row.S, seed=seed, Cc=1.41, max_expand_depth=row.med, arith=oracle.ARITH_CHAIN, det_math=True)
+    genv = tw.env.Puzzle(row.w, row.h, row.diff, 2, max_depth)
     if solve:
         start = oracle.Puzzle(row.w, row.h, row.diff, 2, max_depth)
         start.reset(seed=seed, episode=3)
         state = start.get_state()
-        genv.set_state(state); oenv.set_state(state)
+        genv.set_state(state)
         with options(row):
             (gs, gr), gact = tw.collector.solve(genv, gp, row.det, row.ns, row.S, 1.41, row.med, seed=seed)
-    else:
-        with options(row):
-            gs, gr = tw.collector.evaluate(genv, gp, num_episodes=row.E, deterministic=row.det, num_searches=row.ns, num_mcts_searches=row.S, seed=seed,
-                                           C=1.41, max_expand_depth=row.med, num_cores=32)
+        return genv, state, (gs, gr), gact
+    with options(row):
+        gs, gr = tw.collector.evaluate(genv, gp, num_episodes=row.E, deterministic=row.det, num_searches=row.ns, num_mcts_searches=row.S, seed=seed,
+                                       C=1.41, max_expand_depth=row.med, num_cores=32)
+    return genv, None, (gs, gr), None
+
+
+def run_evaluate(tw, oracle, cus, row, gp, opol, seed):
+    """-> ((success, reward), the solve's actions or None, the attempts) of the call that was checked."""
+    solve = row.entry == "solve"
+    max_depth = SOLVE_MAX_DEPTH if solve else 256
+    oenv = oracle.Puzzle(row.w, row.h, row.diff, 2, max_depth)
+    kw = dict(num_mcts_searches=row.S, seed=seed, Cc=1.41, max_expand_depth=row.med, arith=oracle.ARITH_CHAIN, det_math=True)
+    genv, state, (gs, gr), gact = call_evaluate(tw, oracle, row, gp, seed)
+    if solve:
+        oenv.set_state(state)
     assert_launch(row, cus)
     # every attempt
     a_s, a_t, a_n = _lib.debug_last_attempts()
@@ -173,20 +192,29 @@ def run_evaluate(tw, oracle, cus, row, gp, opol, seed):
         assert fin[-1] and not fin[:-1].any()
         assert gs == float(boards[-1].tolist() == list(range(row.w * row.h))) and f32_bits(gr) == f32_bits(total)
         assert genv.get_state() == state
-        return
+        return (gs, gr), gact, (a_s, a_t, a_n)
     if sm.attempts(row) <= 8192:                                      # the reduction of the attempts is the reference's (serial: only up to here)
         ref = oracle.evaluate(oenv, opol, row.E, row.det, row.ns, **kw)
         assert f32_bits(ref[0]) == f32_bits(rate) and f32_bits(ref[1]) == f32_bits(mean), (ref, rate, mean)
     assert f32_bits(gs) == f32_bits(rate) and f32_bits(gr) == f32_bits(mean), (gs, gr, rate, mean)
+    return (gs, gr), None, (a_s, a_t, a_n)
+
+
+def collect_ppo(tw, row, gp, seed, merge_order=False):
+    return tw.collector.PPOCollector(row.E, G, G, 32, merge_order=merge_order).collect(tw.env.Puzzle(row.w, row.h, row.diff, 2, 256), gp, seed=seed)
 
 
 def run_ppo(tw, oracle, cus, row, gp, opol, seed):
-    genv, oenv = tw.env.Puzzle(row.w, row.h, row.diff, 2, 256), oracle.Puzzle(row.w, row.h, row.diff, 2, 256)
+    """-> the collect in episode order that was checked."""
+    oenv = oracle.Puzzle(row.w, row.h, row.diff, 2, 256)
+    first = None
     for merge_order in (False, True):
-        g = tw.collector.PPOCollector(row.E, G, G, 32, merge_order=merge_order).collect(genv, gp, seed=seed)
+        g = collect_ppo(tw, row, gp, seed, merge_order)
         assert_launch(row, cus, g.stats)
         o = oracle.ppo_collect(oenv, opol, row.E, G, G, seed=seed, arith=oracle.ARITH_CHAIN, det_log=True, num_threads=_threads(), merge_order=merge_order)
         _assert_same_collect(g, o, row.w * row.h)
+        first = g if first is None else first
+    return first
 
 
 @pytest.mark.parametrize("row", sm.TABLE, ids=[sm.row_id(r) for r in sm.TABLE])

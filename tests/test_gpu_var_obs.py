@@ -103,6 +103,11 @@ def _same_as_loop(g, o, n):
 @pytest.mark.parametrize("num_episodes", [E, 1])
 @pytest.mark.parametrize("n", SIZES)
 def test_device_collect_equals_the_host_stepped_collect_and_the_oracle(tw, oracle, n, num_episodes):
+    check_device_collect(tw, oracle, n, num_episodes)
+
+
+def check_device_collect(tw, oracle, n, num_episodes):
+    """-> the device collect of Lamps<n> that was checked"""
     from twisterl_amd import _lib
     env = lamps(n)
     gp, _ = _policies(oracle, n)
@@ -113,6 +118,7 @@ def test_device_collect_equals_the_host_stepped_collect_and_the_oracle(tw, oracl
     assert h.ragged and h.stats["rollout_threads"] == 0
     _same_bytes(g, h)
     _same_as_loop(g, shared_collect(n, False, num_episodes), n)
+    return g
 
 
 @pytest.mark.parametrize("n", SIZES)

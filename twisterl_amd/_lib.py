@@ -143,6 +143,7 @@ SYMBOLS = {
     "tw_debug_policy_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     "tw_debug_collect_tail": (C.c_int, [C.POINTER(DebugTailArgs), C.POINTER(FinalizeLaunch), C.POINTER(_VP)]),
     "tw_debug_collected_arena": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "tw_debug_fill_memory": (C.c_int, [C.c_int, C.c_uint32]),
     "tw_puzzle_create": (_VP, [C.c_uint32] * 5),
     "tw_puzzle_clone": (_VP, [_VP]),
     "tw_puzzle_destroy": (None, [_VP]),
@@ -283,6 +284,45 @@ class launch_option:
 
     def __exit__(self, *exc):
         check(lib().tw_set_launch_option(self.option, 0))
+        return False
+
+
+class debug_fill_memory:
+    """`with debug_fill_memory(0xFFFFFFFF): ...` -- while the block runs, every device buffer the library hands to a call (the cached
+    workspace, a result arena, a call-local scratch allocation) is set to the 32-bit pattern before its first use
+    (tw_debug_fill_memory; test hook).  Leaving the block turns the hook off, whatever happened inside: no result may depend on what
+    device memory held before a call, and tests/test_gpu_memory_matrix.py shows it pattern by pattern."""
+
+    _state = None          # (on, pattern) as the library holds it; None: not asked yet (TW_DEBUG_FILL gives the initial value)
+
+    def __init__(self, pattern: int):
+        if not 0 <= pattern <= 0xFFFFFFFF:
+            raise ValueError(f"debug_fill_memory: pattern {pattern:#x} is not a 32-bit word")
+        self.pattern = pattern
+
+    @classmethod
+    def _current(cls):
+        if cls._state is None:
+            try:
+                cls._state = (1, int(os.environ["TW_DEBUG_FILL"], 16))
+            except (KeyError, ValueError):
+                cls._state = (0, 0)
+            if not 0 <= cls._state[1] <= 0xFFFFFFFF:
+                cls._state = (0, 0)
+        return cls._state
+
+    @classmethod
+    def _set(cls, state):
+        check(lib().tw_debug_fill_memory(*state))
+        cls._state = state
+
+    def __enter__(self):
+        self.before = self._current()
+        self._set((1, self.pattern))
+        return self
+
+    def __exit__(self, *exc):
+        self._set(self.before)          # (off, unless TW_DEBUG_FILL or an enclosing block had it on)
         return False
 
 

@@ -96,6 +96,44 @@ int require_device()
     return TW_OK;
 }
 
+// ---------------------------------------------------------------------------------- tw_debug_fill_memory (test hook)
+// Off (the product): nothing is filled, a reservation pays one relaxed load.  On: every device buffer the library hands to a call --
+// the cached workspace, a result arena, a call-local scratch allocation -- is set to a 32-bit pattern over its whole capacity, on the
+// call's stream, before the call's first use of it.  A kernel that reads what neither it nor a predecessor in the same call wrote then
+// reads the pattern instead of zeros or a previous call's leftovers.  (bit 32: on; the low word: the pattern)
+static uint64_t fill_from_env()
+{
+    const char *v = getenv("TW_DEBUG_FILL");
+    if (!v || !*v) return 0;
+    char *end = nullptr;
+    const unsigned long long x = strtoull(v, &end, 16);
+    if (*end || x > 0xffffffffull) { fprintf(stderr, "twisterl_hip: TW_DEBUG_FILL=%s is not a 32-bit hex word; ignored\n", v); return 0; }
+    return (1ull << 32) | x;
+}
+static std::atomic<uint64_t> g_fill{fill_from_env()};
+
+int debug_fill(void *ptr, size_t bytes, hipStream_t s)
+{
+    const uint64_t f = g_fill.load(std::memory_order_relaxed);
+    if (!(f >> 32) || !ptr || !bytes) return TW_OK;
+    const uint32_t pattern = (uint32_t)f;
+    uint8_t *p = reinterpret_cast<uint8_t *>(ptr);
+    if (bytes / 4) TW_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)pattern, bytes / 4, s));
+    for (size_t i = bytes / 4 * 4; i < bytes; ++i) TW_HIP(hipMemsetAsync(p + i, (int)((pattern >> (8 * (i & 3))) & 0xffu), 1, s));
+    return TW_OK;
+}
+
+// every call-local device allocation of the library: one hipMalloc, filled while the hook is on (the caller hipFrees it)
+int scratch_alloc(void **out, size_t bytes, hipStream_t s, const char *what)
+{
+    *out = nullptr;
+    const hipError_t e = hipMalloc(out, bytes);
+    if (e != hipSuccess) { *out = nullptr; return hip_fail(e, what, __FILE__, __LINE__); }
+    const int rc = debug_fill(*out, bytes, s);
+    if (rc) { (void)hipFree(*out); *out = nullptr; }
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------- workspace
 // Padded trajectory buffers are large (E * t_pad * 48 B) and have the same size every
 // iteration of the trainer, so they are cached per device instead of hipMalloc'ed per call.
@@ -119,7 +157,7 @@ static int ws_reserve(size_t bytes, void **out)
         g_ws.cap = bytes; g_ws.device = dev;
     }
     *out = g_ws.ptr;
-    return TW_OK;
+    return debug_fill(g_ws.ptr, g_ws.cap, current_stream());      // (test hook; a cache hit is filled like a fresh allocation)
 }
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -165,7 +203,9 @@ static int arena_acquire(size_t bytes, void **out, size_t *cap)
                 (void)hipEventDestroy(a.released);
                 if (e != hipSuccess) { (void)hipFree(a.ptr); return hip_fail(e, "hipStreamWaitEvent(pooled arena)", __FILE__, __LINE__); }
             }
-            return TW_OK;
+            const int rc = debug_fill(a.ptr, a.cap, current_stream());      // (test hook)
+            if (rc) { (void)hipFree(a.ptr); *out = nullptr; }
+            return rc;
         }
     }
     // a new arena gets 1/16 of headroom: the record count of a collect varies with the seed by a fraction of a percent, and an
@@ -180,7 +220,9 @@ static int arena_acquire(size_t bytes, void **out, size_t *cap)
     }
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(compact result)", __FILE__, __LINE__);
     *cap = want;
-    return TW_OK;
+    const int rc = debug_fill(*out, want, current_stream());      // (test hook)
+    if (rc) { (void)hipFree(*out); *out = nullptr; }
+    return rc;
 }
 
 // `producer`: the stream the result was produced on.  tw_set_stream is thread-local, and a result may be freed by another thread
@@ -268,6 +310,12 @@ extern "C" int tw_set_launch_option(int option, int value)
             g_env_resident_groups.store(value); return TW_OK;
         default: set_error("tw_set_launch_option: unknown option %d", option); return TW_ERR_INVALID;
     }
+}
+
+extern "C" int tw_debug_fill_memory(int on, uint32_t pattern)
+{
+    g_fill.store(on ? (1ull << 32) | pattern : 0ull, std::memory_order_relaxed);
+    return TW_OK;
 }
 
 extern "C" int tw_debug_counters(uint64_t *out, int n)
@@ -977,7 +1025,7 @@ extern "C" int tw_policy_evaluate(const tw_policy *p, int mode, uint32_t precisi
     const size_t o_obs = 0, o_m = align_up(o_obs + b_obs, 256), o_p = align_up(o_m + b_m, 256),
                  o_oa = align_up(o_p + b_p, 256), o_ov = align_up(o_oa + b_oa, 256), tot = align_up(o_ov + b_ov, 256);
     uint8_t *buf = nullptr;
-    TW_HIP(hipMalloc((void **)&buf, tot));
+    rc = scratch_alloc((void **)&buf, tot, s, "device scratch (policy evaluate staging)"); if (rc) return rc;
     auto cleanup = [&]() { (void)hipFree(buf); };
 #define TW_HIP_C(call) do { hipError_t _e = (call); if (_e != hipSuccess) { cleanup(); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
     TW_HIP_C(hipMemcpyAsync(buf + o_obs, obs, b_obs, hipMemcpyHostToDevice, s));
@@ -1055,11 +1103,11 @@ extern "C" int tw_collected_adv_stats(const tw_collected *c, double *mean, doubl
     if (!c->is_ppo || !c->field_ptr[TW_F_ADVS]) { set_error("tw_collected_adv_stats: no advantages in this result (AlphaZero data?)"); return TW_ERR_INVALID; }
     hipStream_t s = current_stream();
     double *acc = nullptr;
-    TW_HIP(hipMalloc((void **)&acc, sum_scratch_doubles() * sizeof(double)));
+    int rc = scratch_alloc((void **)&acc, sum_scratch_doubles() * sizeof(double), s, "device scratch (sum scratch)"); if (rc) return rc;
     const float *adv = reinterpret_cast<const float *>(c->field_ptr[TW_F_ADVS]);
     const uint64_t n = c->n_records;
     double sum = 0.0, ss = 0.0;
-    int rc = launch_sum(adv, n, 0.0, 0, acc, s);
+    rc = launch_sum(adv, n, 0.0, 0, acc, s);
     hipError_t e = hipSuccess;
     if (rc == TW_OK) { e = hipMemcpyAsync(&sum, acc, 8, hipMemcpyDeviceToHost, s); if (e == hipSuccess) e = hipStreamSynchronize(s); }
     const double m = n ? sum / (double)n : 0.0;
@@ -1372,7 +1420,7 @@ extern "C" int tw_debug_episode_order(const tw_puzzle_desc *env, uint64_t seed, 
     PuzzleConsts envc; rc = make_env_consts(env, &envc, 16); if (rc) return rc;
     hipStream_t s = current_stream();
     void *buf = nullptr;
-    TW_HIP(hipMalloc(&buf, n * 12 + 256 + episode_order_scratch_bytes(n)));
+    rc = scratch_alloc(&buf, n * 12 + 256 + episode_order_scratch_bytes(n), s, "device scratch (episode order)"); if (rc) return rc;
     uint64_t *b = reinterpret_cast<uint64_t *>(buf); uint32_t *o = reinterpret_cast<uint32_t *>(b + n);
     void *scr = reinterpret_cast<uint8_t *>(buf) + align_up(n * 12, 256);
     rc = launch_init_boards(envc, seed, episode_offset, n, b, s);
@@ -1837,7 +1885,7 @@ int run_solve(const PuzzleConsts &envc, const tw_policy *policy, const tw_solve_
                  o_tbl = seg(deep ? (size_t)walkers * tbl_entries * 32 : 0), o_init = seg(deep && !from_state ? n_episodes * 8 : 0), o_queue = seg(deep ? 4 : 0),
                  o_sv = seg(deep ? sizeof(MctsSolve) : 0);
     uint8_t *buf = nullptr;
-    TW_HIP(hipMalloc((void **)&buf, cur ? cur : 256));
+    int rc = scratch_alloc((void **)&buf, cur ? cur : 256, s, "device scratch (solve workspace)"); if (rc) return rc;
     sa.success = reinterpret_cast<float *>(buf + o_s); sa.total = reinterpret_cast<float *>(buf + o_r);
     sa.n_steps = reinterpret_cast<uint32_t *>(buf + o_n); sa.actions = want_actions ? buf + o_a : nullptr;
     if (from_state && envc.n_cells > 16) {
@@ -1846,7 +1894,6 @@ int run_solve(const PuzzleConsts &envc, const tw_policy *policy, const tw_solve_
         if (ce != hipSuccess) { (void)hipFree(buf); return hip_fail(ce, "hipMemcpyAsync(start state)", __FILE__, __LINE__); }
         sa.start_cells = buf + o_cells;
     }
-    int rc;
     if (mcts) {
         ma.arena = reinterpret_cast<MctsNode *>(buf + o_arena);
         ma.eval_count = reinterpret_cast<unsigned long long *>(buf + o_cnt);

@@ -298,7 +298,7 @@ static int gather_alloc(tw_gather *g)
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
     for (int f = 0; f < TW_F_COUNT; ++f) if (g->width[f]) off[f] = seg((size_t)g->st.cap * g->width[f] + 16);
     const size_t o_len = seg(E * 4), o_start = seg(E * 8), o_tot = seg(8), o_scan = seg(scan_scratch_bytes(E));
-    TW_HIP(hipMalloc(&g->arena, cur));
+    { const int rc = scratch_alloc(&g->arena, cur, g->c->stream, "device scratch (gather arena)"); if (rc) return rc; }
     g->arena_bytes = cur;
     uint8_t *a = reinterpret_cast<uint8_t *>(g->arena);
     for (int f = 0; f < TW_F_COUNT; ++f) g->base[f] = g->width[f] ? a + off[f] : nullptr;

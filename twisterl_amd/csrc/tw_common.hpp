@@ -721,6 +721,10 @@ int collected_adopt(void *arena, size_t arena_bytes, int device, int is_ppo, uin
 // the cached trajectory workspace (held under workspace_mutex() while in use) and the pooled result arenas (tw_api.hip)
 std::mutex &workspace_mutex();
 int workspace_reserve(size_t bytes, void **out);
+// Test hook (tw_debug_fill_memory): while it is on, sets `bytes` at `ptr` to its 32-bit pattern on `s`; off (the product): one relaxed load.
+// The workspace and the result arenas are filled where they are reserved; a call-local allocation comes from scratch_alloc, which fills it.
+int debug_fill(void *ptr, size_t bytes, hipStream_t s);
+int scratch_alloc(void **out, size_t bytes, hipStream_t s, const char *what);
 // refuses `need` bytes of workspace that neither the cached workspace nor 95 % of (free memory + that workspace) holds
 int check_memory_fit(size_t need, const char *who);
 // the five events of a device collect: 0 | rollout | 1 | scan | 2 ... 3 | finalize | 4

@@ -48,7 +48,7 @@ int upload_collected(const void *const (&src)[TW_F_COUNT], const size_t (&bytes)
     size_t cur = 0, off[TW_F_COUNT] = {};
     for (int f = 0; f < TW_F_COUNT; ++f) { off[f] = cur; cur = (cur + bytes[f] + 255) / 256 * 256; }
     void *arena = nullptr;
-    TW_HIP(hipMalloc(&arena, cur ? cur : 256));
+    { const int rc = scratch_alloc(&arena, cur ? cur : 256, s, "device scratch (collected fields)"); if (rc) return rc; }
     void *fp[TW_F_COUNT] = {};
     hipError_t he = hipSuccess;
     for (int f = 0; f < TW_F_COUNT; ++f) if (bytes[f]) {
@@ -107,8 +107,8 @@ extern "C" int tw_ppo_collect_env(const tw_env_vtable *env, const tw_policy *pol
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t o_obs = 0, o_m = up(b_obs), o_p = o_m + up(b_m), o_la = o_p + up(b_p), o_v = o_la + up(b_la), tot = o_v + up(b_v);
     uint8_t *dev = nullptr;
-    hipError_t he = hipMalloc((void **)&dev, tot);
-    if (he != hipSuccess) { cleanup(); return hip_fail(he, "hipMalloc(step staging)", __FILE__, __LINE__); }
+    rc = scratch_alloc((void **)&dev, tot, s, "device scratch (step staging)");
+    if (rc) { cleanup(); return rc; }
     std::vector<int32_t> h_obs((size_t)E * NO), h_perm(E); std::vector<uint8_t> h_m((size_t)E * A); std::vector<float> h_la((size_t)E * A), h_v(E);
     std::vector<uint64_t> live; live.reserve(E);
 #define TW_HIP_E(call) do { hipError_t _e = (call); if (_e != hipSuccess) { cleanup(); (void)hipFree(dev); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
@@ -343,7 +343,7 @@ struct HostEvalBatch {
     {
         auto up = [](size_t x) { return (x + 255) / 256 * 256; };
         o_obs = 0; o_m = up(cap * NO * 4); o_p = o_m + up(cap * A); o_la = o_p + up(cap * 4); o_v = o_la + up(cap * A * 4);
-        TW_HIP(hipMalloc((void **)&dev, o_v + up(cap * 4)));
+        const int rc = scratch_alloc((void **)&dev, o_v + up(cap * 4), s, "device scratch (evaluation staging)"); if (rc) return rc;
         h_obs.resize(cap * NO); h_perm.resize(cap); h_m.resize(cap * A); h_la.resize(cap * A); h_v.resize(cap);
         return TW_OK;
     }
