@@ -65,6 +65,14 @@
 // self-play and MCTS-guided evaluate of 5..31 actions then run in the same mcts_env_kernel, which loops over a node's children and keeps
 // a column's probabilities in LDS, byte-equal to the host-stepped path.  A module built with the define alone (wide=True) has no search
 // kernel: its AZCollector.collect and evaluate with MCTS run host-stepped over the module's vtable.
+// Reduced precision: `#define TW_DEVICE_ENV_FP16` before this header (build_device_env(..., fp16=True) emits it) adds
+// rollout_env16_kernel -- the same step loop over EngineV16 (twisterl_amd/csrc/tw_engine_generic16.hpp: every Linear on
+// v_mfma_f32_16x16x32_f16, DESIGN.md §2 "Forward, f16-input mode") -- and the kernel that packs its binary16 weight image at the start
+// of every collect; the descriptor's launch_rollout16 / groups_per_cu16 are then set and PPOCollector(precision="fp16").collect runs
+// on the device for any generic policy.  Everything outside the forward is the f32 kernel's instruction sequence: given the same
+// actions, states, ids, masks, rewards and draws are bit-equal to it.  Nothing is asked of the struct for it.  The define composes
+// with every form above and below; without it both members are null and the module holds exactly the other kernels.  Evaluate, solve
+// and the search kernel stay f32.
 #pragma once
 
 #include "twisterl_hip.h"
@@ -157,6 +165,10 @@ struct DeviceEnvModule {
             x.fill_vtable = fill_vtable;
             x.launch_search = search;                                     // (TW_DEVICE_ENV: null, and no third kernel in the module)
             x.groups_per_cu = groups;                                     // (occupancy of the kernels THIS module holds)
+#ifdef TW_DEVICE_ENV_FP16
+            x.launch_rollout16 = launch_rollout_env16<T>;                 // (else null, and the module holds neither f16 kernel)
+            x.groups_per_cu16 = groups_per_cu_env16<T>;
+#endif
             return x;
         }();
         return &d;

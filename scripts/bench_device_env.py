@@ -32,6 +32,14 @@ profiles/r13_device_env_solve.jsonl.
 grid with its episode queue that a collect of more episodes than the chip holds columns gets by itself.  Every device row says which
 of the two ran ("persist") and the grid ("blocks").  --skip-host leaves the host-stepped rows (and the byte comparison with them) out:
 the A/B of two trees or two launch forms needs only the device rows.  profiles/r09_device_env_persist.jsonl.
+
+--precision fp32,fp16 (--env gridworld or perm8): the device collect in each of the listed precisions FROM THE SAME MODULE, built with
+fp16=True (rollout_env_kernel and rollout_env16_kernel side by side; fp16 has no host-stepped counterpart, so these runs are device
+rows only).  --policy small: embedding 128, common [64] (perm8: [64, 64] -- with one common layer of 64 units and 64 obs ids the
+policy has the MFMA shape, which device environments hand to the host-stepped path); --policy deep: embedding 256, common [512, 256].
+Every row carries the rollout's milliseconds (the events around the launch: in fp16 the pack of the weight image and the rollout)
+as median / min / max of --reps, and records per second of rollout time.  Rows are APPENDED to --out.
+profiles/r16_device_env_fp16.jsonl.
 """
 import argparse
 import ctypes as C
@@ -200,6 +208,65 @@ def solve(args):
                         f.write(json.dumps(row) + "\n")
 
 
+def precisions(args):
+    """PPO collect on the device in fp32 and fp16 from ONE module built with fp16=True: rollout milliseconds, their spread, records/s."""
+    import numpy as np
+    import twisterl_amd
+    from twisterl_amd import _lib, twisterl
+    from twisterl_amd.build import build_device_env
+    from twisterl_amd.env import DeviceEnv
+    from tests.util import amd_policy, make_deep_policy_arrays_obs
+    if twisterl_amd.device_count() < 1:
+        raise SystemExit("no GPU")
+    if args.no_persist:
+        _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
+    # (--tree of a checkout from before the fp16 form: the plain module, fp32 rows only -- the parent's figure of the same run)
+    import inspect
+    fp16 = {"fp16": True} if "fp16" in inspect.signature(build_device_env).parameters else {}
+    if args.env == "perm8":
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", "perm8_fp16", wide=True, **fp16)
+        env = DeviceEnv(so, "perm8_fp16", [8, 32, 4], max_records=33)
+        env_name, obs_size, A = "Permutation8 (28 actions)", 64, 28
+        emb, common = {"default": (512, (128, 64)), "small": (128, (64, 64)), "deep": (256, (512, 256))}[args.policy]
+    elif args.env == "gridworld":
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "gridworld.hpp"), "tw_examples::GridWorld5x5", "gridworld5x5_fp16", **fp16)
+        env = DeviceEnv(so, "gridworld5x5_fp16", [5, 5, 64, 1], max_records=65)
+        env_name, obs_size, A = "GridWorld5x5", 625, 4
+        emb, common = {"default": (512, (128,)), "small": (128, (64,)), "deep": (256, (512, 256))}[args.policy]
+    else:
+        raise SystemExit("--precision: --env gridworld or perm8")
+    pol = amd_policy(make_deep_policy_arrays_obs(obs_size, seed=0, emb=emb, common=common, n_actions=A))
+    pol_name = "-".join(str(x) for x in (obs_size, emb) + tuple(common)) + "+heads (generic)"
+    info = twisterl_amd.device_info()
+    for E in [int(x) for x in args.episodes.split(",")]:
+        for prec in args.precision.split(","):
+            if prec != "fp32" and not fp16:
+                continue
+            fn = lambda seed: twisterl.collector.PPOCollector(E, 0.995, 0.995, 32, precision=prec).collect(env, pol, seed=seed)
+            for i in range(args.warmup):
+                fn(100 + i)
+            ts, recs, roll = [], [], []
+            for i in range(args.reps):
+                t0 = time.perf_counter()
+                c = fn(1000 + i)
+                n = len(c)
+                ts.append(time.perf_counter() - t0)
+                recs.append(n)
+                roll.append(float(c.stats.get("ms_rollout", 0.0)))
+            last = _lib.debug_last_launch()
+            assert (last["family"], last["nw"]) == (_lib.TW_KERNEL_ROLLOUT_BIG, 16 if prec == "fp16" else 0), last
+            k = int(np.argsort(roll)[len(roll) // 2])
+            row = {"bench": "precision", "env": env_name, "policy": pol_name, "precision": prec, "path": "device", "episodes": E, "records": recs[k],
+                   "ms_rollout": round(roll[k], 3), "ms_rollout_min": round(min(roll), 3), "ms_rollout_max": round(max(roll), 3),
+                   "records_per_s_rollout": round(recs[k] / (roll[k] * 1e-3), 1), "wall_ms": round(float(np.median(ts)) * 1e3, 3),
+                   "ms_rollout_all": [round(x, 3) for x in roll], "persist": last["persist"], "blocks": last["blocks"],
+                   "reps": args.reps, "warmup": args.warmup, "tree": os.path.basename(ROOT) if args.tree else "this", "device": info["name"]}
+            print(json.dumps(row), flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--solve", action="store_true", help="collector.solve from the current state against the host-stepped path; appends rows to --out")
@@ -215,11 +282,15 @@ def main():
     ap.add_argument("--tree", default=None, help="the checkout to measure (default: this one)")
     ap.add_argument("--no-persist", action="store_true", help="TW_OPT_NO_PERSIST = 1: never the persistent grid + episode queue")
     ap.add_argument("--skip-host", action="store_true", help="device rows only (no host-stepped rows, no byte comparison with them)")
+    ap.add_argument("--precision", default=None, help="fp32,fp16: device rows in these precisions from one module built with fp16=True; appends to --out")
+    ap.add_argument("--policy", default="default", choices=["default", "small", "deep"], help="with --precision: the policy's widths")
     args = ap.parse_args()
     if args.az:
         return az(args)
     if args.solve:
         return solve(args)
+    if args.precision:
+        return precisions(args)
     import numpy as np
     import twisterl_amd
     from twisterl_amd import _lib, twisterl

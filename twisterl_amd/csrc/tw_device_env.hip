@@ -7,7 +7,9 @@
 // id), and an environment with other than four actions has its logits narrowed (A < 4) or moved from a wide array (A > 4).  The two
 // small kernels that serves, compact_env_obs8_kernel and narrow_logits_kernel, live here behind launch_compact_obs8 / launch_narrow_logits.
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
-// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error), and -- for
+// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error; but a PPO
+// collect with precision fp16 of a module built with TW_DEVICE_ENV_FP16 runs in rollout_env16_kernel over EngineV16, its binary16
+// weight image packed into the collect's workspace by the module's launcher in front of every rollout), and -- for
 // a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has no search launcher -- self-play,
 // evaluate and solve with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
 // 1..4 actions and (TW_DEVICE_ENV_WIDE_SEARCH) for 5..31, which lives in the module
@@ -102,6 +104,19 @@ size_t engine_lds_bytes(uint32_t nc, const PolicyDev &p)
     }
 }
 
+// EngineV16 (tw_engine_generic16.hpp): the f16 rollout kernel of a module built with TW_DEVICE_ENV_FP16
+size_t engine16_lds_bytes(uint32_t nc, const PolicyDev &p)
+{
+    switch (nc) {
+        case 4:  return EngineV16<4>::lds_bytes(p);
+        case 9:  return EngineV16<9>::lds_bytes(p);
+        case 16: return EngineV16<16>::lds_bytes(p);
+        case 25: return EngineV16<25>::lds_bytes(p);
+        case 36: return EngineV16<36>::lds_bytes(p);
+        default: return EngineV16<64>::lds_bytes(p);
+    }
+}
+
 // the checks of the host path (tw_env_generic.hip), with its messages
 int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
 {
@@ -110,20 +125,22 @@ int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
     return TW_OK;
 }
 
-// The grid of a module's rollout (0) or solve (1) kernel over `columns` episodes or attempts.  (The search kernel, 2, has no persistent
+// The grid of a module's rollout (0), solve (1) or f16 rollout (ENV_KERNEL_ROLLOUT16: tw_device_env::groups_per_cu16) kernel over
+// `columns` episodes or attempts.  (The search kernel, 2, has no persistent
 // form: a first one faulted on the device and was taken out again -- DESIGN.md §8.)  As many workgroups
 // as the kernel's own occupancy puts on the CUs that reserve_cus leaves are resident at once (TW_OPT_ENV_RESIDENT_GROUPS > 0 caps
 // their total: the test hook); more columns than those hold run on a PERSISTENT grid of that size whose columns take the next
 // episode from a 32-bit counter (EnvRolloutArgs::queue), which starts at the number of slots and is taken once more by every slot that
 // finds it empty: columns + slots must fit 32 bits.  Otherwise -- and with TW_OPT_NO_PERSIST -- one workgroup per 16 columns, as ever.
 struct EnvGrid { uint64_t blocks; bool persist; };
+constexpr int ENV_KERNEL_ROLLOUT16 = 16;
 int env_grid(const tw_device_env *d, int kernel, size_t lds_bytes, uint64_t columns, uint32_t reserve_cus, EnvGrid *g)
 {
     g->blocks = (columns + GEN_COLS - 1) / GEN_COLS; g->persist = false;
     const LaunchOptions o = launch_options();
     if (o.no_persist) return TW_OK;
     int per_cu = 0;
-    const int e = d->groups_per_cu(kernel, lds_bytes, &per_cu);
+    const int e = kernel == ENV_KERNEL_ROLLOUT16 ? d->groups_per_cu16(lds_bytes, &per_cu) : d->groups_per_cu(kernel, lds_bytes, &per_cu);
     if (e != (int)hipSuccess) return hip_fail((hipError_t)e, "device environment occupancy query", __FILE__, __LINE__);
     if (per_cu < 1) { set_error("device environment: the kernel does not fit a compute unit with %zu bytes of LDS", lds_bytes); return TW_ERR_UNSUPPORTED; }
     const uint64_t cus = (uint64_t)device_cus(), keep = reserve_cus < cus - 1 ? reserve_cus : cus - 1;   // reserve_cus CUs stay free (RCCL beside the grid)
@@ -206,9 +223,13 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);      // (tw_debug_last_launch: nothing yet; the host-stepped path reports nothing)
     const tw_env_vtable vt = host_table(env, proto);
     const PolicyDev *pd = policy_dev(policy);
-    // what the kernel does not take: the host-stepped path over the module's own vtable (same bytes; its messages).  Episodes
+    // precision="fp16": rollout_env16_kernel over EngineV16, when the module holds it (built with TW_DEVICE_ENV_FP16) and the policy
+    // is a generic stack with both heads (at most GEN16_MAX_LAYERS layers: tw_policy_create's own limit)
+    const bool f16 = prm->precision == TW_PREC_F16 && env->launch_rollout16 && env->groups_per_cu16 && pd->generic && pd->n_action >= 1 &&
+                     pd->n_value >= 1 && pd->n_common + pd->n_action + pd->n_value <= GEN16_MAX_LAYERS;
+    // what the kernels do not take: the host-stepped path over the module's own vtable (same bytes; its messages).  Episodes
     // longer than the finalize step's LDS tile holds (finalize_ppo_max_t_pad: 1,820 records) go there too.
-    if (!pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > (uint32_t)finalize_ppo_max_t_pad(0))
+    if (!pd->generic || (prm->precision != TW_PREC_F32_EXACT && !f16) || max_records_per_episode > (uint32_t)finalize_ppo_max_t_pad(0))
         return tw_ppo_collect_env(&vt, policy, prm, max_records_per_episode, out);
     if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
     rc = check_env_policy(vt, pd); if (rc) return rc;
@@ -220,12 +241,21 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     const bool ragged = vt.observe_n != nullptr;                          // observations of variable length: two-byte ids, 0xFFFF = no id
     const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
-    const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
+    const size_t lds_bytes = f16 ? engine16_lds_bytes(env->engine_nc, *pd) : engine_lds_bytes(env->engine_nc, *pd);
     if (lds_bytes > 159 * 1024) { set_error("rollout: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
     EnvGrid grid;
-    rc = env_grid(env, 0, lds_bytes, E, prm->reserve_cus, &grid); if (rc) return rc;
+    rc = env_grid(env, f16 ? ENV_KERNEL_ROLLOUT16 : 0, lds_bytes, E, prm->reserve_cus, &grid); if (rc) return rc;
     const uint64_t blocks = grid.blocks;
     if (blocks > 0x7fffffffull || t_pad > 0x7fffffffull) { set_error("tw_ppo_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
+    // the f16 image's size, from the layout function the pack kernel and the engine index with (tw_engine_generic16.hpp), over the
+    // layer table's widths -- which live on the device (they never change after tw_policy_create)
+    size_t image_halves = 0;
+    if (f16) {
+        const int n_layers = pd->n_common + pd->n_action + pd->n_value;
+        std::vector<LayerDev> layers((size_t)n_layers);
+        TW_HIP(hipMemcpy(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost));
+        image_halves = gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
+    }
 
     std::lock_guard<std::mutex> lock(workspace_mutex());
     hipStream_t s = current_stream();
@@ -234,6 +264,12 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(32), o_scan = seg(scan_scratch_bytes(E)),
                  o_obs16 = seg(R * NO * 2),                                // (o_total: record total | err | the episode queue's counter)
                  o_lgw = seg(A > 4 ? R * A * sizeof(float) : 0);           // more than four actions: the masked logits, [E][t_pad][A]
+    // fp16: the binary16 weight image behind the f32 carve, which does not move (f32: no bytes).  Every half of it -- table padding,
+    // weight padding and read slack included -- is written by pack_generic16_kernel before the rollout reads it; the table of
+    // tests/memory_matrix.py lists the f32 carve's segments, and tests/test_gpu_device_env_fp16.py runs the fp16 collect on pre-filled
+    // workspace memory (tw_debug_fill_memory) for this one
+    const size_t o_img = cur;
+    cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
     uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
@@ -254,9 +290,17 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
         TW_HIP(hipMemcpyAsync(ra.queue, &first, 4, hipMemcpyHostToDevice, s));
     }
     TW_HIP(hipEventRecord(ev.ev[0], s));
-    const int lr = env->launch_rollout(&ra, proto, (unsigned)blocks, lds_bytes, s);
+    int lr;
+    if (f16) {                                                            // the pack of the image, then the rollout (the module's launcher)
+        EnvRollout16Args ra16{};
+        ra16.r = ra;
+        ra16.image.img = reinterpret_cast<_Float16 *>(ws + o_img); ra16.image.halves = image_halves;
+        lr = env->launch_rollout16(&ra16, proto, (unsigned)blocks, lds_bytes, s);
+    } else
+        lr = env->launch_rollout(&ra, proto, (unsigned)blocks, lds_bytes, s);
     if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment rollout launch", __FILE__, __LINE__);
-    note_launch(TW_KERNEL_ROLLOUT_BIG, 1, (int)env->engine_nc, 0, 0, grid.persist, false, false, false, (uint32_t)blocks, 256);
+    // (tw_debug_last_launch: nw = 16 marks the f16 kernel, 0 the f32 one -- include/twisterl_hip.h)
+    note_launch(TW_KERNEL_ROLLOUT_BIG, 1, (int)env->engine_nc, f16 ? 16 : 0, 0, grid.persist, false, false, false, (uint32_t)blocks, 256);
     TW_HIP(hipEventRecord(ev.ev[1], s));
     rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;

@@ -9,8 +9,11 @@
 // the same arithmetic as tw_ppo_collect_env / tw_evaluate_env over the environment's host vtable: bit-equal to them.  Both kernels have a
 // persistent form behind a run-time branch on their argument struct's `queue` (fewer columns than episodes; a column whose episode is
 // over takes the next one from a counter), which the library chooses from the kernel's own occupancy (tw_device_env::groups_per_cu).
+// A module built with TW_DEVICE_ENV_FP16 also holds rollout_env16_kernel<Env, NC>: the rollout's loop over EngineV16
+// (tw_engine_generic16.hpp), PPOCollector(precision="fp16"), within the a-priori bound of the f16-input spec instead of bit-equal.
 #pragma once
 #include "tw_engine_generic.hpp"
+#include "tw_engine_generic16.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -33,6 +36,12 @@ struct EnvRolloutArgs {
                                      // index from this counter (which starts at the number of columns) until it passes num_episodes
     float     *lgw;                  // an environment of more than four actions: [E][t_pad][A] masked logits of the records, addressed by
                                      // episode like obs16 (the record's four logit slots are then zero and nobody reads them); else null
+};
+
+// ... and what rollout_env16_kernel (precision="fp16": the same loop over EngineV16, tw_engine_generic16.hpp) needs on top
+struct EnvRollout16Args {
+    EnvRolloutArgs r;
+    Gen16Image     image;            // carved from the collect's workspace, packed by the launcher before the rollout
 };
 
 // evaluate(): one column = one attempt (episode, search), as solve_big_kernel
@@ -121,6 +130,12 @@ struct tw_device_env {
     // dynamic LDS (what the launcher of that kernel is given): the kernel's own answer, hipOccupancyMaxActiveBlocksPerMultiprocessor,
     // from which the library sizes a persistent grid.  A hipError_t; kernel 2 of a module without the search kernel: hipErrorInvalidValue
     int (*groups_per_cu)(int kernel, size_t lds_bytes, int *out);
+    // null unless the module was built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)): pack_generic16_kernel (the policy's
+    // f32 device copies -> the binary16 image a->image, on stream s) and then rollout_env16_kernel, with launch_rollout's return
+    // convention (hipErrorInvalidValue: no image, or a policy EngineV16 does not take); and that kernel's occupancy, as
+    // groups_per_cu gives the others'.  lds_bytes = EngineV16<engine_nc>::lds_bytes(pol).
+    int (*launch_rollout16)(const tw::EnvRollout16Args *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s);
+    int (*groups_per_cu16)(size_t lds_bytes, int *out);
 };
 
 inline void tw_device_env_layout(uint32_t (&out)[TW_DEVICE_ENV_LAYOUT_WORDS])
@@ -446,6 +461,146 @@ __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArg
     eng.end();
 }
 
+// The same loop over EngineV16 (tw_engine_generic16.hpp): precision="fp16" of PPOCollector.collect.  A module holds it when it was
+// built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)); pack_generic16_kernel runs in front of it, on the same stream.
+// It carries its OWN COPY of rollout_env_kernel's step loop, line for line but for the engine and the argument struct: with the loop
+// in one function template that both kernels inline, this compiler allocated the f32 kernels differently (ProbeO64A4S: 1,032 instead
+// of 1,040 bytes of scratch memory, GridWorld 5 x 5: 160 instead of 164 spilled SGPRs), and the f32 kernels are to stay what they
+// are.  A change to one loop belongs in the other: tests/test_gpu_device_env_fp16.py holds this kernel's environment side, record
+// by record, to the same host code the f32 kernel is held to.
+template <class Env, int NC>
+__global__ void __launch_bounds__(256, 1) rollout_env16_kernel(const EnvRollout16Args a16, const Env proto)
+{
+    using Eng = EngineV16<NC>;
+    const EnvRolloutArgs &a = a16.r;
+    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
+    // EngineV<64> alone takes some 450 registers: a fixed-length observation of 37 .. 64 ids kept alive across the forward on top of
+    // them spilled to scratch memory.  There the ids are stored BEFORE the forward, as env_rows_n stores a variable-length record's
+    // (of an observation with a bad id the row is written all the same; the collect fails and nobody reads it)
+    constexpr bool EARLY_IDS = NC > 36 && !EnvHasObserveN<Env>::value;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    Eng eng;
+    eng.img = a16.image.img;
+    eng.begin1(a.pol, lds);
+    const int j = eng.j;
+    // every lane group of every wave carries the state of column j (the engine's mapping); lanes 0-15 of wave 0 store
+    const uint64_t e_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+    const bool valid  = e_first < a.num_episodes;
+    const bool writer = eng.h == 0 && eng.primary();
+    uint32_t e_taken = 0xffffffffu;                                                   // the episode taken from the queue; none: e_first
+    Env st = proto;
+    bool alive = valid;
+    bool fresh = valid;                                                               // the column's episode is still to be reset
+    bool more  = valid && a.queue != nullptr;                                         // the queue may still hold episodes
+    int  t = 0;
+    eng.begin2();
+    while (__syncthreads_or(alive ? 1 : 0)) {
+        const uint64_t e_local  = e_taken != 0xffffffffu ? (uint64_t)e_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+        const uint64_t e_global = a.episode_offset + e_local;
+        // the ONE place the struct's reset() is called from, the column's first episode and every one it takes from the queue alike
+        // (with a second call site the compiler stopped inlining it, and the state went to scratch memory)
+        if (fresh) {
+            st = proto;                                                               // clone of the prototype (ppo.rs:59)
+            st.reset(a.seed, e_global);                                               // ppo.rs:60
+            fresh = false;
+        }
+        int perm = -1;
+        if (eng.pol.n_perms > 0) {                                                    // get_perm_id (policy.rs:67-77)
+            const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_PERM);
+            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
+        }
+        int ids[NO], rowoff[NC];
+        bool bad = false; int bad_id = 0;
+        [[maybe_unused]] bool bad_count = false;                                      // (a struct with observe_n: a count outside 0 .. n_obs)
+        if (alive) {
+            if constexpr (EnvHasObserveN<Env>::value)
+                (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count,
+                                          writer ? a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)env_n_obs(st) : nullptr);
+            else {
+                env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+                if constexpr (EARLY_IDS) {
+                    if (writer) {
+                        const int n = env_n_obs(st);
+                        uint16_t *o = a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)n;
+#pragma unroll
+                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
+        }
+        float lg[4]; float value, rew; int action;
+        if constexpr (A > 4) {
+            // the masked logits go to their own array (the record's four slots stay zero); a record that is not pushed stores none
+            const float *head = eng.forward_head(rowoff, value);
+            const uint32_t mb = alive ? st.masks() : 0u;
+            rew = alive ? st.reward() : 0.0f;
+            float *row = alive && !bad ? a.lgw + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)A : nullptr;
+            action = env_gumbel_stream<A>(eng.pol, head, j, eng.g, perm, mb, a.seed, e_global, (uint32_t)t, row);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lg[i] = 0.0f;
+        } else {
+        eng.forward(rowoff, lg, value);
+        env_act_perm<A>(eng.pol, perm, lg);
+        const uint32_t mb = alive ? st.masks() : 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lg[i] = (i < A && ((mb >> i) & 1u)) ? lg[i] : -1e10f;    // policy.rs:62
+        rew = alive ? st.reward() : 0.0f;
+        const u32x4 gw = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_GUMBEL);
+        action = gumbel_argmax_n<A>(lg, gw);
+        }
+        if (alive) {
+            bool failed = false;
+            if (bad) {                                                                // (the host path fails the collect here)
+                if (writer) {                                                         // the library names the first one (t, episode)
+                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
+                    store_rec(a.out.rec + e_local * (uint64_t)a.out.t_pad + (uint64_t)t, zero4, lg, __builtin_bit_cast(float, bad_id), bad_count ? 1.0f : 0.0f, 0, -1);
+                    atomicOr(a.err, bad_count ? 8u : 1u);
+                }
+                failed = true;
+                alive = false;
+            } else {
+                if (writer) {                                                         // push the record (ppo.rs:71-76)
+                    const uint64_t rec = e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
+                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
+                    store_rec(a.out.rec + rec, zero4, lg, value, rew, action, perm);
+                    if constexpr (!EnvHasObserveN<Env>::value && !EARLY_IDS) {        // (observe_n: env_rows_n has stored them)
+                        const int n = env_n_obs(st);
+                        uint16_t *o = a.obs16 + rec * (uint64_t)n;
+#pragma unroll
+                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
+                    }
+                }
+                if (st.is_final()) alive = false;                                     // ppo.rs:78
+                else if (t + 1 >= a.out.t_pad) {                                      // the host path's max_records_per_episode
+                    if (writer) atomicOr(a.err, 2u);
+                    alive = false;
+                } else { st.step(action); ++t; }                                      // ppo.rs:79
+            }
+            // the episode is over: its length at once (the column may go on with another one)
+            if (!alive && writer) a.out.ep_len[e_local] = ((uint32_t)t + 1u) | (failed ? 0x80000000u : 0u);
+        }
+        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
+            const bool want = !alive && more;
+            unsigned got = 0xffffffffu;
+            if (want && writer) got = atomicAdd(a.queue, 1u);
+            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
+            if (writer) bc[j] = got;
+            __syncthreads();
+            got = bc[j];
+            if (want) {
+                if ((uint64_t)got < a.num_episodes) {
+                    e_taken = got;
+                    t = 0; alive = true; fresh = true;                                // (reset at the top of the next step)
+                } else more = false;
+            }
+        }
+    }
+    eng.end();
+}
+
 // evaluate() (rust/src/rl/evaluate.rs:22-89 over single_solve, rl/solve.rs:17-71), as solve_big_kernel: one column = one attempt
 // (episode e, search a): reset, then while !is_final { total += reward; probs = Policy::predict (masked softmax, random twist);
 // action = argmax | weighted sample; step }.  Best-of-N and the means are reduced on the host.  An attempt's three results are
@@ -579,6 +734,40 @@ int launch_rollout_env(const EnvRolloutArgs *a, const void *proto, unsigned bloc
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((rollout_env_kernel<Env, NC>), dim3(blocks), dim3(EngineV<NC>::THREADS), lds_bytes, s, *a, p);
     return (int)hipGetLastError();
+}
+
+// tw_device_env::launch_rollout16 / groups_per_cu16.  The pack runs in front of EVERY rollout: the image is never older than the
+// policy's f32 copies.  Its grid: one thread per eight halves, at most 1,024 workgroups (grid-stride beyond).
+template <class Env>
+int launch_rollout_env16(const EnvRollout16Args *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
+{
+    constexpr int NC = env_engine_nc(Env::N_OBS);
+    Env p;
+    __builtin_memcpy(&p, proto, sizeof(Env));
+    const PolicyDev &pol = a->r.pol;
+    const int n_layers = pol.n_common + pol.n_action + pol.n_value;
+    if (!a->image.img || !pol.generic || n_layers > GEN16_MAX_LAYERS) return (int)hipErrorInvalidValue;
+    const void *k = reinterpret_cast<const void *>(&rollout_env16_kernel<Env, NC>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    uint64_t pb = (a->image.halves / 8 + 255) / 256;
+    if (pb > 1024) pb = 1024;
+    hipLaunchKernelGGL((pack_generic16_kernel<256>), dim3((unsigned)(pb ? pb : 1)), dim3(256), 0, s, pol, a->image);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((rollout_env16_kernel<Env, NC>), dim3(blocks), dim3(EngineV16<NC>::THREADS), lds_bytes, s, *a, p);
+    return (int)hipGetLastError();
+}
+
+template <class Env>
+int groups_per_cu_env16(size_t lds_bytes, int *out)
+{
+    constexpr int NC = env_engine_nc(Env::N_OBS);
+    if (!out) return (int)hipErrorInvalidValue;
+    const void *k = reinterpret_cast<const void *>(&rollout_env16_kernel<Env, NC>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, EngineV16<NC>::THREADS, lds_bytes);
 }
 
 // tw_device_env::groups_per_cu of a module without the search kernel (with it: groups_per_cu_search_env, tw_mcts_env.hpp)

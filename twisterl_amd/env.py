@@ -229,7 +229,8 @@ class DeviceEnvDesc(C.Structure):
                 ("get_difficulty", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("set_difficulty", C.CFUNCTYPE(None, C.c_void_p, C.c_int)),
                 ("obs_size", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("n_obs_of", C.CFUNCTYPE(C.c_int, C.c_void_p)), ("fill_vtable", C.c_void_p),
                 ("launch_search", C.c_void_p),
-                ("groups_per_cu", C.CFUNCTYPE(C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int)))]
+                ("groups_per_cu", C.CFUNCTYPE(C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int))),
+                ("launch_rollout16", C.c_void_p), ("groups_per_cu16", C.CFUNCTYPE(C.c_int, C.c_size_t, C.POINTER(C.c_int)))]
 
 
 class DeviceEnv:
@@ -238,6 +239,8 @@ class DeviceEnv:
     tw_device_env_<name>.  `params` go to the struct's init() (the environment's constructor arguments).
 
     PPOCollector.collect and evaluate run its episodes inside one kernel each (tw_ppo_collect_device_env / tw_evaluate_device_env);
+    a module built with build_device_env(..., fp16=True) also runs PPOCollector(precision="fp16").collect in one kernel, every Linear
+    of any generic policy on the f16 matrix core (`fp16` says whether the module has that kernel; without it: "f32 only");
     a module built with build_device_env(..., search=True) (1..4 actions; wide_search=True: 1..31) runs AZCollector.collect and evaluate with MCTS inside one kernel too
     (tw_az_collect_device_env; `search` says whether the module has that kernel), any other module steps the same struct's host
     code for those (tw_az_collect_env / tw_evaluate_env).  solve runs from the object's CURRENT state in one kernel as evaluate does
@@ -313,6 +316,11 @@ class DeviceEnv:
     def search(self) -> bool:
         """The module holds the search kernel (built with search=True or wide_search=True): self-play and MCTS-guided evaluate run on the device."""
         return bool(self._desc.launch_search)
+
+    @property
+    def fp16(self) -> bool:
+        """The module holds the f16 rollout kernel (built with fp16=True): PPOCollector(precision="fp16").collect runs on the device."""
+        return bool(self._desc.launch_rollout16)
 
     @property
     def variable_obs(self) -> bool:
