@@ -71,9 +71,19 @@
 // of every collect; the descriptor's launch_rollout16 / groups_per_cu16 are then set and PPOCollector(precision="fp16").collect runs
 // on the device for any generic policy.  Everything outside the forward is the f32 kernel's instruction sequence: given the same
 // actions, states, ids, masks, rewards and draws are bit-equal to it.  Nothing is asked of the struct for it.  The define composes
-// with every form above and below; without it both members are null and the module holds exactly the other kernels.  Evaluate, solve
-// and the search kernel stay f32.
+// with every form above and below; without it both members are null and the module holds exactly the other kernels.
+// `#define TW_DEVICE_ENV_FP16_SOLVE` (build_device_env(..., fp16_solve=True); it implies TW_DEVICE_ENV_FP16) adds solve_env16_kernel,
+// the evaluate loop over the same EngineV16 and the same image: collector.evaluate / collector.solve with precision="fp16" and
+// num_mcts_searches == 0 then run on the device for any generic policy, launched by the descriptor's launch_solve when its arguments
+// carry an image (EnvSolveArgs::image), its occupancy behind groups_per_cu(3, ...) -- the descriptor itself does not grow.  Again
+// everything outside the forward is the f32 kernel's sequence, and nothing is asked of the struct.  A module built with
+// TW_DEVICE_ENV_FP16 alone holds exactly the kernels it held.  The search kernel stays f32: MCTS-guided evaluate and solve in
+// another precision answer "f32 only", as every module without the define does.
 #pragma once
+
+#if defined(TW_DEVICE_ENV_FP16_SOLVE) && !defined(TW_DEVICE_ENV_FP16)
+#define TW_DEVICE_ENV_FP16
+#endif
 
 #include "twisterl_hip.h"
 #include "tw_rollout_env.hpp"

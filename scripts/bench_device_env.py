@@ -40,6 +40,13 @@ policy has the MFMA shape, which device environments hand to the host-stepped pa
 Every row carries the rollout's milliseconds (the events around the launch: in fp16 the pack of the weight image and the rollout)
 as median / min / max of --reps, and records per second of rollout time.  Rows are APPENDED to --out.
 profiles/r16_device_env_fp16.jsonl.
+
+--evaluate (with --precision, --policy, --env gridworld or perm8 as above): collector.evaluate of --episodes episodes x 1 search,
+deterministic and sampled, in each listed precision from ONE module built with fp16_solve=True (solve_env_kernel and solve_env16_kernel
+side by side).  evaluate returns two means and no statistics, so a row carries the WHOLE CALL (checks, the image's pack in fp16, the
+kernel, the copies back, the reduction on the host) as median / min / max of --reps after --warmup, and the two means.  A --tree from
+before the keyword builds the plain module and gives the fp32 rows only: the parent's figures of the same session.
+profiles/r17_device_env_fp16_solve.jsonl.
 """
 import argparse
 import ctypes as C
@@ -267,6 +274,64 @@ def precisions(args):
                     f.write(json.dumps(row) + "\n")
 
 
+def evaluate_bench(args):
+    """collector.evaluate on the device in fp32 and fp16 from ONE module built with fp16_solve=True: whole-call milliseconds, their spread."""
+    import inspect
+    import numpy as np
+    import twisterl_amd
+    from twisterl_amd import _lib, twisterl
+    from twisterl_amd.build import build_device_env
+    from twisterl_amd.env import DeviceEnv
+    from tests.util import amd_policy, make_deep_policy_arrays_obs
+    if twisterl_amd.device_count() < 1:
+        raise SystemExit("no GPU")
+    if args.no_persist:
+        _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
+    # (--tree of a checkout from before the fp16_solve form: the plain module, fp32 rows only)
+    has16 = "fp16_solve" in inspect.signature(build_device_env).parameters
+    kw, suffix = ({"fp16_solve": True}, "_fp16s") if has16 else ({}, "")
+    if args.env == "perm8":
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", "perm8" + suffix, wide=True, **kw)
+        env = DeviceEnv(so, "perm8" + suffix, [8, 32, 4], max_records=33)
+        env_name, obs_size, A = "Permutation8 (28 actions)", 64, 28
+        emb, common = {"default": (512, (128, 64)), "small": (128, (64, 64)), "deep": (256, (512, 256))}[args.policy]
+    elif args.env == "gridworld":
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "gridworld.hpp"), "tw_examples::GridWorld5x5", "gridworld5x5" + suffix, **kw)
+        env = DeviceEnv(so, "gridworld5x5" + suffix, [5, 5, 64, 1], max_records=65)
+        env_name, obs_size, A = "GridWorld5x5", 625, 4
+        emb, common = {"default": (512, (128,)), "small": (128, (64,)), "deep": (256, (512, 256))}[args.policy]
+    else:
+        raise SystemExit("--evaluate: --env gridworld or perm8")
+    pol = amd_policy(make_deep_policy_arrays_obs(obs_size, seed=0, emb=emb, common=common, n_actions=A))
+    pol_name = "-".join(str(x) for x in (obs_size, emb) + tuple(common)) + "+heads (generic)"
+    info = twisterl_amd.device_info()
+    for E in [int(x) for x in args.episodes.split(",")]:
+        for prec in (args.precision or "fp32").split(","):
+            if prec != "fp32" and not has16:
+                continue
+            for det in (True, False):
+                pkw = {"precision": prec} if has16 else {}
+                fn = lambda seed: twisterl.collector.evaluate(env, pol, E, det, 1, 0, seed, 1.41, 1, 1, **pkw)
+                for i in range(args.warmup):
+                    fn(100 + i)
+                ts, res = [], None
+                for i in range(args.reps):
+                    t0 = time.perf_counter()
+                    res = fn(1000 + i)
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                last = _lib.debug_last_launch()
+                assert (last["family"], last["nw"]) == (_lib.TW_KERNEL_SOLVE_BIG, 16 if prec == "fp16" else 0), last
+                row = {"bench": "evaluate", "env": env_name, "policy": pol_name, "precision": prec, "deterministic": det, "path": "device",
+                       "episodes": E, "searches": 1, "wall_ms": round(float(np.median(ts)), 3), "wall_ms_min": round(min(ts), 3),
+                       "wall_ms_max": round(max(ts), 3), "wall_ms_all": [round(t, 3) for t in ts], "success_rate": res[0], "mean_reward": res[1],
+                       "persist": last["persist"], "blocks": last["blocks"], "reps": args.reps, "warmup": args.warmup,
+                       "tree": os.path.basename(ROOT) if args.tree else "this", "device": info["name"]}
+                print(json.dumps(row), flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--solve", action="store_true", help="collector.solve from the current state against the host-stepped path; appends rows to --out")
@@ -284,7 +349,10 @@ def main():
     ap.add_argument("--skip-host", action="store_true", help="device rows only (no host-stepped rows, no byte comparison with them)")
     ap.add_argument("--precision", default=None, help="fp32,fp16: device rows in these precisions from one module built with fp16=True; appends to --out")
     ap.add_argument("--policy", default="default", choices=["default", "small", "deep"], help="with --precision: the policy's widths")
+    ap.add_argument("--evaluate", action="store_true", help="collector.evaluate (episodes x 1 search) instead of the PPO collect, in the precisions of --precision; appends to --out")
     args = ap.parse_args()
+    if args.evaluate:
+        return evaluate_bench(args)
     if args.az:
         return az(args)
     if args.solve:

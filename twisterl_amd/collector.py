@@ -586,13 +586,22 @@ def _solve_params(deterministic, num_searches, num_mcts_searches, C_, max_expand
                             int(seed) & (2**64 - 1), _lib.PRECISIONS[precision])
 
 
-def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches, C, max_expand_depth, *, seed=None):
+def _check_precision(precision):
+    if precision not in _lib.PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
+
+
+def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches, C, max_expand_depth, *, seed=None, precision="fp32"):
     """solve(py_env, policy, deterministic, num_searches, num_mcts_searches, C, max_expand_depth)
     -> ((success, reward), actions)   (python_interface/env.rs:180-191 over rl/solve.rs:73-101).
-    Best of `num_searches` greedy/sampled roll-outs from the env's CURRENT state; the env is not modified."""
+    Best of `num_searches` greedy/sampled roll-outs from the env's CURRENT state; the env is not modified.
+    `precision` (keyword-only; "fp32" exact | "fp16" | "fp16x2") goes to the library as it is: a DeviceEnv built with fp16_solve=True
+    runs "fp16" without MCTS on the f16 matrix core; what an environment does not take in that precision answers with the
+    library's own message ("... f32 only ...")."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
-    prm = _solve_params(deterministic, num_searches, num_mcts_searches, C, max_expand_depth, seed)
+    _check_precision(precision)
+    prm = _solve_params(deterministic, num_searches, num_mcts_searches, C, max_expand_depth, seed, precision)
     if isinstance(py_env, PyEnv):
         br = _PyEnvBridge(py_env, prototype=py_env._env.copy())             # (the caller's object is not touched)
         cap = br.max_records + 1
@@ -618,15 +627,16 @@ def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches
 
 
 def evaluate(py_env, policy: Policy, num_episodes, deterministic, num_searches, num_mcts_searches, seed, C, max_expand_depth,
-             num_cores):
+             num_cores, *, precision="fp32"):
     """evaluate(py_env, policy, num_episodes, deterministic, num_searches, num_mcts_searches, seed, C,
     max_expand_depth, num_cores) -> (success_rate, mean_reward)   (python_interface/env.rs:194-207 over
     rl/evaluate.rs:22-89).  `seed` keys the episode scrambles and action draws (the reference ignores it);
-    `num_cores` is accepted for compatibility."""
+    `num_cores` is accepted for compatibility; `precision` (keyword-only) as in solve()."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
+    _check_precision(precision)
     _u("num_cores", num_cores)
-    prm = _solve_params(deterministic, num_searches, num_mcts_searches, C, max_expand_depth, seed)
+    prm = _solve_params(deterministic, num_searches, num_mcts_searches, C, max_expand_depth, seed, precision)
     s, r = _c.c_float(), _c.c_float()
     if isinstance(py_env, PyEnv):
         br = _PyEnvBridge(py_env)

@@ -9,7 +9,8 @@
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
 // the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error; but a PPO
 // collect with precision fp16 of a module built with TW_DEVICE_ENV_FP16 runs in rollout_env16_kernel over EngineV16, its binary16
-// weight image packed into the collect's workspace by the module's launcher in front of every rollout), and -- for
+// weight image packed into the collect's workspace by the module's launcher in front of every rollout, and evaluate / solve without
+// MCTS of a module built with TW_DEVICE_ENV_FP16_SOLVE run likewise in solve_env16_kernel), and -- for
 // a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has no search launcher -- self-play,
 // evaluate and solve with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
 // 1..4 actions and (TW_DEVICE_ENV_WIDE_SEARCH) for 5..31, which lives in the module
@@ -125,7 +126,7 @@ int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
     return TW_OK;
 }
 
-// The grid of a module's rollout (0), solve (1) or f16 rollout (ENV_KERNEL_ROLLOUT16: tw_device_env::groups_per_cu16) kernel over
+// The grid of a module's rollout (0), solve (1), f16 solve (3) or f16 rollout (ENV_KERNEL_ROLLOUT16: tw_device_env::groups_per_cu16) kernel over
 // `columns` episodes or attempts.  (The search kernel, 2, has no persistent
 // form: a first one faulted on the device and was taken out again -- DESIGN.md §8.)  As many workgroups
 // as the kernel's own occupancy puts on the CUs that reserve_cus leaves are resident at once (TW_OPT_ENV_RESIDENT_GROUPS > 0 caps
@@ -443,14 +444,26 @@ namespace {
 // the most bytes of action rows (attempts x max_steps) a solve keeps on the device; a longer bound goes to the host-stepped path
 constexpr uint64_t SOLVE_ACTION_BYTES_MAX = 1ull << 30;
 
-// What solve_env_kernel / mcts_env_kernel take of an evaluate or a solve; everything else is the host-stepped path's (the callers
+// index of solve_env16_kernel for tw_device_env::groups_per_cu (a module built with TW_DEVICE_ENV_FP16_SOLVE)
+constexpr int ENV_KERNEL_SOLVE16 = 3;
+
+// precision="fp16" of evaluate / solve: solve_env16_kernel over EngineV16, when the module holds it (the capability query: kernel 3
+// with a null result, answered without the HIP runtime), the policy is a generic stack with both heads (at most GEN16_MAX_LAYERS
+// layers: the collect's own rule) and no MCTS is asked for (the search kernel is f32 only)
+bool attempts_f16(const tw_device_env *env, const PolicyDev *pd, const tw_solve_params *prm)
+{
+    return prm->precision == TW_PREC_F16 && prm->num_mcts_searches == 0 && pd->generic && pd->n_action >= 1 && pd->n_value >= 1 &&
+           pd->n_common + pd->n_action + pd->n_value <= GEN16_MAX_LAYERS && env->groups_per_cu(ENV_KERNEL_SOLVE16, 0, nullptr) == (int)hipSuccess;
+}
+
+// What solve_env_kernel / solve_env16_kernel / mcts_env_kernel take of an evaluate or a solve; everything else is the host-stepped path's (the callers
 // hand over to it).  node_cap: the search's tree size, for attempts_device_env.
 bool attempts_on_device(const tw_device_env *env, const PolicyDev *pd, const tw_solve_params *prm, uint64_t num_episodes, uint32_t max_steps,
                         uint64_t *node_cap)
 {
     const bool mcts = prm->num_mcts_searches != 0;
     *node_cap = 0;
-    return !(!pd->generic || prm->precision != TW_PREC_F32_EXACT || prm->num_searches == 0 || num_episodes == 0 || max_steps > 0x7fffffffu ||
+    return !(!pd->generic || (prm->precision != TW_PREC_F32_EXACT && !attempts_f16(env, pd, prm)) || prm->num_searches == 0 || num_episodes == 0 || max_steps > 0x7fffffffu ||
              (mcts && (!env->launch_search || !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_steps ? max_steps : 1u, node_cap))));
 }
 
@@ -464,24 +477,33 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
                         uint64_t node_cap, std::vector<float> &best_s, std::vector<float> &best_r, std::vector<uint32_t> *best_actions)
 {
     const bool mcts = prm->num_mcts_searches != 0;
+    const bool f16 = prm->precision == TW_PREC_F16;                       // (attempts_on_device: then attempts_f16 holds, and mcts is false)
     const uint32_t max_steps = max_steps_in ? max_steps_in : 1u;
     int rc = check_env_policy(vt, pd); if (rc) return rc;
     if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("%s: policy without its two-byte twist table", who); return TW_ERR_INVALID; }
     rc = require_device(); if (rc) return rc;
     const uint64_t N = prm->num_searches, NA = num_episodes * N;
     if (NA / N != num_episodes) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
-    const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
+    const size_t lds_bytes = f16 ? engine16_lds_bytes(env->engine_nc, *pd) : engine_lds_bytes(env->engine_nc, *pd);
     const size_t search_lds = mcts ? env_mcts_pending_bytes(env->n_obs) + env_mcts_probs_bytes(env->num_actions) : 0;
     if (lds_bytes + search_lds > 159 * 1024) {
         set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes + search_lds); return TW_ERR_UNSUPPORTED;
     }
     EnvGrid grid;                                                         // (MCTS-guided attempts: the search kernel, one column per attempt)
     grid.blocks = (NA + GEN_COLS - 1) / GEN_COLS; grid.persist = false;
-    if (!mcts) { rc = env_grid(env, 1, lds_bytes, NA, 0, &grid); if (rc) return rc; }
+    if (!mcts) { rc = env_grid(env, f16 ? ENV_KERNEL_SOLVE16 : 1, lds_bytes, NA, 0, &grid); if (rc) return rc; }
     const uint64_t blocks = grid.blocks;
     if (blocks > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
     // the played moves: one row of max_steps bytes per attempt (an attempt that ends has played at most max_steps)
     const uint32_t stride = best_actions ? max_steps : 0u;
+    // fp16: the image's size, as the collect reads it -- the layout function over the layer table's widths, which live on the device
+    size_t image_halves = 0;
+    if (f16) {
+        const int n_layers = pd->n_common + pd->n_action + pd->n_value;
+        std::vector<LayerDev> layers((size_t)n_layers);
+        TW_HIP(hipMemcpy(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost));
+        image_halves = gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
+    }
 
     std::vector<float> succ(NA), tot(NA);
     std::vector<uint32_t> steps(NA), ce;
@@ -492,6 +514,11 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
     const size_t o_s = seg(NA * 4), o_t = seg(NA * 4), o_n = seg(NA * 4), o_err = seg(32), o_ce = seg(mcts ? NA * 16 : 0),
                  o_arena = seg(mcts ? (size_t)NA * node_cap * ENV_MCTS_NODE_BYTES : 0), o_act = seg((size_t)NA * stride);
+    // fp16: the binary16 weight image behind o_act, appended as the fp16 collect appends its own (f32: no bytes, and nothing moves).
+    // Every half of it is written by pack_generic16_kernel before solve_env16_kernel reads it; tests/test_gpu_device_env_fp16_solve.py
+    // runs the call on pre-filled workspace memory for this region
+    const size_t o_img = cur;
+    cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
     if (mcts) { rc = check_memory_fit(cur, who); if (rc) return rc; }
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
@@ -526,9 +553,13 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
             const unsigned int first = (unsigned int)(blocks * GEN_COLS);
             TW_HIP(hipMemcpyAsync(sa.queue, &first, 4, hipMemcpyHostToDevice, s));
         }
+        if (f16) {                                                        // the module's launcher packs it, then solve_env16_kernel
+            sa.image.img = reinterpret_cast<_Float16 *>(ws + o_img); sa.image.halves = image_halves;
+        }
         const int lr = env->launch_solve(&sa, proto, (unsigned)blocks, lds_bytes, s);
         if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment evaluate launch", __FILE__, __LINE__);
-        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, 0, 0, grid.persist, from_state, false, false, (uint32_t)blocks, 256);
+        // (tw_debug_last_launch: nw = 16 marks the f16 kernel, 0 the f32 one -- include/twisterl_hip.h)
+        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, f16 ? 16 : 0, 0, grid.persist, from_state, false, false, (uint32_t)blocks, 256);
     }
     TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
     TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));

@@ -11,6 +11,8 @@
 // over takes the next one from a counter), which the library chooses from the kernel's own occupancy (tw_device_env::groups_per_cu).
 // A module built with TW_DEVICE_ENV_FP16 also holds rollout_env16_kernel<Env, NC>: the rollout's loop over EngineV16
 // (tw_engine_generic16.hpp), PPOCollector(precision="fp16"), within the a-priori bound of the f16-input spec instead of bit-equal.
+// A module built with TW_DEVICE_ENV_FP16_SOLVE holds solve_env16_kernel<Env, NC> as well: evaluate's loop over EngineV16,
+// collector.evaluate / collector.solve with precision="fp16" and no MCTS.
 #pragma once
 #include "tw_engine_generic.hpp"
 #include "tw_engine_generic16.hpp"
@@ -58,6 +60,9 @@ struct EnvSolveArgs {
     unsigned int *queue;             // as EnvRolloutArgs::queue, over attempts
     uint8_t  *actions;               // null, or [num_attempts][actions_stride]: the moves an attempt played, one byte each (A <= 31),
     uint32_t  actions_stride;        // addressed by attempt like the three results; a move at or beyond the stride is not stored
+    Gen16Image image;                // img null: solve_env_kernel, f32.  Else precision="fp16": solve_env16_kernel over EngineV16 (a module
+                                     // built with TW_DEVICE_ENV_FP16_SOLVE), the image carved from the call's workspace and packed by the
+                                     // launcher before the kernel; the f32 kernel never reads this member
 };
 
 // Self-play (solve_on == 0) and MCTS-guided evaluate (solve_on != 0) of mcts_env_kernel (tw_mcts_env.hpp), which a module has when it
@@ -128,7 +133,12 @@ struct tw_device_env {
     int (*launch_search)(const tw::EnvMctsArgs *a, const void *proto, unsigned blocks, size_t engine_lds_bytes, hipStream_t s);
     // how many workgroups of one of the module's kernels -- 0: rollout, 1: solve, 2: search -- a CU holds at once with lds_bytes of
     // dynamic LDS (what the launcher of that kernel is given): the kernel's own answer, hipOccupancyMaxActiveBlocksPerMultiprocessor,
-    // from which the library sizes a persistent grid.  A hipError_t; kernel 2 of a module without the search kernel: hipErrorInvalidValue
+    // from which the library sizes a persistent grid.  A hipError_t; kernel 2 of a module without the search kernel: hipErrorInvalidValue.
+    // Kernel 3: solve_env16_kernel of a module built with TW_DEVICE_ENV_FP16_SOLVE (lds_bytes = EngineV16<engine_nc>::lds_bytes(pol));
+    // any other module: hipErrorInvalidValue.  Kernel 3 with out == nullptr only asks whether the module holds that kernel: hipSuccess
+    // without a call into the HIP runtime (no device needed), which is how the library and DeviceEnv.fp16_solve learn it -- the
+    // descriptor has no member for it.  launch_solve runs that kernel, the pack of the image in front of it, when EnvSolveArgs::image.img
+    // is not null (a module without the kernel, or a policy EngineV16 does not take: hipErrorInvalidValue)
     int (*groups_per_cu)(int kernel, size_t lds_bytes, int *out);
     // null unless the module was built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)): pack_generic16_kernel (the policy's
     // f32 device copies -> the binary16 image a->image, on stream s) and then rollout_env16_kernel, with launch_rollout's return
@@ -723,6 +733,130 @@ __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a,
     eng.end();
 }
 
+// The same loop over EngineV16: precision="fp16" of collector.evaluate and collector.solve without MCTS.  A module holds it when it
+// was built with TW_DEVICE_ENV_FP16_SOLVE (build_device_env(..., fp16_solve=True)); pack_generic16_kernel runs in front of it, on the
+// same stream, into EnvSolveArgs::image.  Its OWN COPY of solve_env_kernel's step loop, line for line but for the engine and the
+// image, as rollout_env16_kernel is of rollout_env_kernel's and for the same reason: the f32 kernels are to stay what they are.  A
+// change to one loop belongs in the other: tests/test_gpu_device_env_fp16_solve.py holds this kernel, attempt by attempt, to the
+// oracle's ARITH_F16 loop over the module's host code.
+template <class Env, int NC>
+__global__ void __launch_bounds__(256, 1) solve_env16_kernel(const EnvSolveArgs a, const Env proto)
+{
+    using Eng = EngineV16<NC>;
+    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    Eng eng;
+    eng.img = a.image.img;
+    eng.begin1(a.pol, lds);
+    const int j = eng.j;
+    const uint64_t att_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+    const bool valid = att_first < a.num_attempts, writer = eng.h == 0 && eng.primary();
+    uint32_t att_taken = 0xffffffffu;                                                 // the attempt taken from the queue; none: att_first
+    Env st = proto;
+    bool  alive = valid;                                                              // (a fresh attempt: until its reset below says otherwise)
+    bool  fresh = valid;                                                              // the column's attempt is still to be reset
+    bool  more  = valid && a.queue != nullptr;
+    float total = 0.0f;
+    int   t = 0;
+    eng.begin2();
+    while (__syncthreads_or(alive ? 1 : 0)) {
+        const uint64_t att = att_taken != 0xffffffffu ? (uint64_t)att_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
+        const uint64_t key = a.episode_offset * (uint64_t)a.num_searches + att;       // keys this attempt's draws
+        bool ended = false;                                                           // the attempt ended by itself in this step
+        // the ONE place reset() is called from (see rollout_env_kernel).  A fresh attempt whose reset state is already final is over
+        // at once (solve.rs:29): its column feeds no row to this step's forward and takes the next attempt at the end of it
+        if (fresh) {
+            st = proto;                                                               // evaluate.rs:39 / solve.rs:85
+            if (!a.from_state) st.reset(a.seed, a.episode_offset + att / a.num_searches);   // the episode keys the start state
+            total = 0.0f; t = 0; fresh = false;
+            alive = !st.is_final();
+            ended = !alive;
+        }
+        int perm = -1;
+        if (eng.pol.n_perms > 0) {
+            const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_PERM);
+            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
+        }
+        int ids[NO], rowoff[NC];
+        bool bad = false; int bad_id = 0;
+        [[maybe_unused]] bool bad_count = false;
+        if (alive) {
+            if constexpr (EnvHasObserveN<Env>::value) (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count, nullptr);
+            else env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
+        }
+        float lg[4], value;
+        [[maybe_unused]] const float *head = nullptr;
+        if constexpr (A > 4) head = eng.forward_head(rowoff, value);
+        else {
+            eng.forward(rowoff, lg, value);
+            env_act_perm<A>(eng.pol, perm, lg);
+        }
+        const uint32_t mb = (alive ? st.masks() : 0u) & ((1u << A) - 1u);
+        [[maybe_unused]] float probs[4];
+        if constexpr (A <= 4) masked_softmax4(lg, mb, probs);                         // policy.rs:43-47 (masked entries add +0.0)
+        if (alive) {
+            if (bad) {
+                if (writer) {
+                    atomicOr(a.err, bad_count ? 8u : 1u);
+                    a.success[att] = bad_count ? 2.0f : (st.success() ? 1.0f : 0.0f);
+                    a.total[att]   = __builtin_bit_cast(float, bad_id);
+                    a.n_steps[att] = (uint32_t)t | 0x80000000u;
+                }
+                alive = false;
+            } else {
+                total = total + st.reward();                                          // solve.rs:31
+                int action = 0;
+                if constexpr (A > 4) {
+                    float u = 0.0f;
+                    if (!a.deterministic) u = u32_to_unit(rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE).x);
+                    action = env_predict_stream<A>(eng.pol, head, j, perm, mb, a.deterministic != 0u, u);
+                } else if (a.deterministic) {
+                    float bv = probs[0];
+#pragma unroll
+                    for (int i = 1; i < A; ++i) if (probs[i] > bv) { bv = probs[i]; action = i; }
+                } else {
+                    const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE);
+                    action = sample_weighted4(probs, A, u32_to_unit(w.x));
+                }
+                st.step(action);                                                      // solve.rs:56
+                // solve.rs:57-59: the move, into the attempt's own row (alive: att < num_attempts)
+                if (writer && a.actions != nullptr && (uint32_t)t < a.actions_stride) a.actions[att * (uint64_t)a.actions_stride + (uint64_t)t] = (uint8_t)action;
+                ++t;
+                if (st.is_final()) alive = false;
+                else if ((uint32_t)t >= a.max_steps) {                                // the host path's max_steps
+                    if (writer) atomicOr(a.err, 4u);
+                    alive = false;
+                }
+                ended = !alive;
+            }
+        }
+        if (ended && writer) {                                                        // its results (solve.rs:65-68), after t moves
+            a.success[att] = st.success() ? 1.0f : 0.0f;
+            a.total[att]   = total + st.reward();
+            a.n_steps[att] = (uint32_t)t;
+        }
+        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
+            const bool want = !alive && more;
+            unsigned got = 0xffffffffu;
+            if (want && writer) got = atomicAdd(a.queue, 1u);
+            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
+            if (writer) bc[j] = got;
+            __syncthreads();
+            got = bc[j];
+            if (want) {
+                if ((uint64_t)got < a.num_attempts) {
+                    att_taken = got;
+                    alive = true; fresh = true;                                       // (reset at the top of the next step)
+                } else more = false;
+            }
+        }
+    }
+    eng.end();
+}
+
 template <class Env>
 int launch_rollout_env(const EnvRolloutArgs *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
 {
@@ -775,6 +909,17 @@ template <class Env>
 int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
 {
     constexpr int NC = env_engine_nc(Env::N_OBS);
+#ifdef TW_DEVICE_ENV_FP16_SOLVE
+    // kernel 3: solve_env16_kernel, lds_bytes = EngineV16<engine_nc>::lds_bytes(pol).  With out == nullptr the question is only whether
+    // the module HOLDS the kernel (the library's attempts_on_device(), DeviceEnv.fp16_solve): answered without the HIP runtime
+    if (kernel == 3) {
+        if (!out) return (int)hipSuccess;
+        const void *k16 = reinterpret_cast<const void *>(&solve_env16_kernel<Env, NC>);
+        hipError_t e16 = hipFuncSetAttribute(k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e16 != hipSuccess) return (int)e16;
+        return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k16, EngineV16<NC>::THREADS, lds_bytes);
+    }
+#endif
     if (!out || (kernel != 0 && kernel != 1)) return (int)hipErrorInvalidValue;
     const void *k = kernel == 0 ? reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>) : reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
@@ -782,12 +927,34 @@ int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
     return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, EngineV<NC>::THREADS, lds_bytes);
 }
 
+// tw_device_env::launch_solve.  EnvSolveArgs::image.img null: solve_env_kernel.  Else the pack of the image and solve_env16_kernel,
+// as launch_rollout_env16 runs the collect's -- in a module built with TW_DEVICE_ENV_FP16_SOLVE; any other module holds no such kernel
+// and refuses (hipErrorInvalidValue), as this one refuses a policy EngineV16 does not take.
 template <class Env>
 int launch_solve_env(const EnvSolveArgs *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
 {
     constexpr int NC = env_engine_nc(Env::N_OBS);
     Env p;
     __builtin_memcpy(&p, proto, sizeof(Env));
+    if (a->image.img) {
+#ifdef TW_DEVICE_ENV_FP16_SOLVE
+        const PolicyDev &pol = a->pol;
+        const int n_layers = pol.n_common + pol.n_action + pol.n_value;
+        if (!pol.generic || n_layers > GEN16_MAX_LAYERS) return (int)hipErrorInvalidValue;
+        const void *k16 = reinterpret_cast<const void *>(&solve_env16_kernel<Env, NC>);
+        hipError_t e16 = hipFuncSetAttribute(k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e16 != hipSuccess) return (int)e16;
+        uint64_t pb = (a->image.halves / 8 + 255) / 256;
+        if (pb > 1024) pb = 1024;
+        hipLaunchKernelGGL((pack_generic16_kernel<256>), dim3((unsigned)(pb ? pb : 1)), dim3(256), 0, s, pol, a->image);
+        e16 = hipGetLastError();
+        if (e16 != hipSuccess) return (int)e16;
+        hipLaunchKernelGGL((solve_env16_kernel<Env, NC>), dim3(blocks), dim3(EngineV16<NC>::THREADS), lds_bytes, s, *a, p);
+        return (int)hipGetLastError();
+#else
+        return (int)hipErrorInvalidValue;
+#endif
+    }
     const void *k = reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return (int)e;
