@@ -79,9 +79,26 @@ def pattern_bytes(pattern, n):
     return np.tile(np.frombuffer(np.uint32(pattern).tobytes(), dtype=np.uint8), (n + 3) // 4)[:n]
 
 
+_before_snapshot = []
+
+
+@contextlib.contextmanager
+def before_snapshot(hook):
+    """While the block runs, hook(g) sees every collect's result before snap_collected's first read of it.  The family runners build
+    their snapshots inside closures, so a driver that has to look at a result first (tests/test_gpu_stream_matrix.py, run d) says so
+    here instead of every runner passing an argument through."""
+    _before_snapshot.append(hook)
+    try:
+        yield
+    finally:
+        _before_snapshot.remove(hook)
+
+
 def snap_collected(g, pattern, counters=True, extra=None):
     """Everything a collect returned, as bytes: the front end's arrays, the arena's bytes inside the fields, the launch shape and (where
     `counters`) the counts.  With a pattern: the arena outside the fields and the four-column scratch must still hold it."""
+    for hook in _before_snapshot:
+        hook(g)
     dev = g._dev
     snap = {}
     for name, arr in g.to_numpy().items():
@@ -140,7 +157,9 @@ def assert_same(a, b, what):
 
 def four_runs(case, check, call, leftovers=None):
     """check(pattern) -> the snapshot of run a (the row's own check, under the first fill); call(policy, pattern) -> a snapshot of the
-    plain call with policy "P2" (the case's) or "P1" (other weights; run d's first call, whose result is dropped before P2 runs)."""
+    plain call with policy "P2" (the case's) or "P1" (other weights; run d's first call, whose result is dropped before P2 runs).
+    This is the driver of this file; every family runner takes another one as its `driver` argument (tests/test_gpu_stream_matrix.py
+    runs the same families, with the same assertions, on a caller's stream)."""
     p_a, p_b, p_c = mm.PATTERNS
     with _lib.debug_fill_memory(p_a):
         a = check(p_a)
@@ -158,22 +177,21 @@ def four_runs(case, check, call, leftovers=None):
 
 
 # ------------------------------------------------------------------------------------------ families
-def fam_tail(case, tw, oracle, cus):
+def fam_tail(case, tw, oracle, cus, driver=None):
     """tw_debug_collect_tail: tests/test_gpu_finalize.py's check compares every field with the numpy reference as bits and the gaps with
-    the hook's own arena fill (which follows the pool's), so four passes of it are four results equal to one reference."""
+    the hook's own arena fill (which follows the pool's), so every pass of it is a result equal to one reference; the snapshot the
+    driver compares is that reference."""
     from tests import finalize_matrix as fm
     from tests.test_gpu_finalize import _check
     fc = case.ref
     assert fc.values == "normal"                  # (no NaN anywhere: the check's one relaxation is never used)
-    for p in mm.PATTERNS:
-        with _lib.debug_fill_memory(p):
-            _check(fc)
-    _check(fm._ppo(fm.E0 + 3, fc.t_pad + 1, n_cells=fc.n_cells, ids=fc.ids, A=fc.A) if fc.kind == "ppo" else
-           fm._az(fm.E0 + 3, fc.t_pad + 1, n_cells=fc.n_cells, ids=fc.ids, A=fc.A))              # other records first, hook off ...
-    _check(fc)                                                                                   # ... then the case on their leftovers
+    other = (fm._ppo(fm.E0 + 3, fc.t_pad + 1, n_cells=fc.n_cells, ids=fc.ids, A=fc.A) if fc.kind == "ppo" else
+             fm._az(fm.E0 + 3, fc.t_pad + 1, n_cells=fc.n_cells, ids=fc.ids, A=fc.A))              # other records: what run d leaves behind
+    snap = lambda ref: {"ref:" + k: (str(v.dtype), v.shape, v.tobytes()) for k, v in ref.items()}
+    (driver or four_runs)(case, lambda p: snap(_check(fc)), lambda who, p: snap(_check(fc if who == "P2" else other)))
 
 
-def fam_km(case, tw, oracle, cus):
+def fam_km(case, tw, oracle, cus, driver=None):
     from tests import kernel_matrix as km
     from tests import test_gpu_kernel_matrix as t
     row = case.ref
@@ -182,10 +200,10 @@ def fam_km(case, tw, oracle, cus):
     counters = lambda: tuple(_lib.debug_counters(2)) if row.prec == "fp32" and row.common is None else None
     check = lambda p: snap_collected(t.check_row(tw, oracle, cus, row), p, case.counters, counters())
     call = lambda who, p: snap_collected(t._collect(tw, row, pol[who], cus, seed, merge_order=False), p, case.counters, counters())
-    four_runs(case, check, call)
+    (driver or four_runs)(case, check, call)
 
 
-def fam_drain(case, tw, oracle, cus):
+def fam_drain(case, tw, oracle, cus, driver=None):
     import bench
     from tests import test_gpu_rollout_drain as t
     name, thr = case.ref
@@ -201,10 +219,10 @@ def fam_drain(case, tw, oracle, cus):
     def call(who, p):
         g, cnt = t.collect(tw, cus, side, diff, E, pol[who], seed, merge, thr)
         return snap_collected(g, p, case.counters, tuple(cnt))
-    four_runs(case, check, call)
+    (driver or four_runs)(case, check, call)
 
 
-def fam_reuse(case, tw, oracle, cus):
+def fam_reuse(case, tw, oracle, cus, driver=None):
     import bench
     from tests import test_gpu_rollout_reuse as t
     name = case.ref
@@ -216,10 +234,10 @@ def fam_reuse(case, tw, oracle, cus):
         g = t.check_shape(tw, oracle, name)
         assert g.stats["reused_evals"] > 0
         return snap_collected(g, p, case.counters)
-    four_runs(case, check, lambda who, p: snap_collected(t.collect_shape(tw, name, pol[who]), p, case.counters))
+    (driver or four_runs)(case, check, lambda who, p: snap_collected(t.collect_shape(tw, name, pol[who]), p, case.counters))
 
 
-def fam_range(case, tw, oracle, cus):
+def fam_range(case, tw, oracle, cus, driver=None):
     """fp16x2 outside its range: the kernel raises the range flag, the collect runs again in fp32 on the same workspace."""
     from tests import test_gpu_kernel_matrix as t
     w, name = case.ref
@@ -235,7 +253,7 @@ def fam_range(case, tw, oracle, cus):
         g2, was_inside = t.check_range_case(tw, oracle, cus, w, name)
         assert not was_inside
         return snap_collected(g2, p, case.counters)
-    four_runs(case, check, lambda who, p: snap_collected(collect(who), p, case.counters))
+    (driver or four_runs)(case, check, lambda who, p: snap_collected(collect(who), p, case.counters))
 
 
 def _sm_policies(t, oracle, row):
@@ -245,16 +263,16 @@ def _sm_policies(t, oracle, row):
     return gp, opol, t.policies(oracle, row, seed=P1_SEED)[0], 100 + idx
 
 
-def fam_sm_ppo(case, tw, oracle, cus):
+def fam_sm_ppo(case, tw, oracle, cus, driver=None):
     from tests import test_gpu_search_matrix as t
     row = mm.row_of(case)
     gp, opol, p1, seed = _sm_policies(t, oracle, row)
     pol = {"P2": gp, "P1": p1}
     check = lambda p: snap_collected(t.run_ppo(tw, oracle, cus, row, gp, opol, seed), p, case.counters)
-    four_runs(case, check, lambda who, p: snap_collected(t.collect_ppo(tw, row, pol[who], seed), p, case.counters))
+    (driver or four_runs)(case, check, lambda who, p: snap_collected(t.collect_ppo(tw, row, pol[who], seed), p, case.counters))
 
 
-def fam_sm_az(case, tw, oracle, cus):
+def fam_sm_az(case, tw, oracle, cus, driver=None):
     from tests import search_matrix as sm
     from tests import test_gpu_search_matrix as t
     row = mm.row_of(case)
@@ -269,10 +287,10 @@ def fam_sm_az(case, tw, oracle, cus):
         assert c[12] == 0 and c[13] == 0, c
         return snap_collected(g, p, case.counters)
     check = lambda p: after(t.run_self_play(tw, oracle, cus, row, gp, opol, seed), p)
-    four_runs(case, check, lambda who, p: after(t.collect_self_play(tw, cus, row, pol[who], seed), p))
+    (driver or four_runs)(case, check, lambda who, p: after(t.collect_self_play(tw, cus, row, pol[who], seed), p))
 
 
-def fam_sm_eval(case, tw, oracle, cus):
+def fam_sm_eval(case, tw, oracle, cus, driver=None):
     from tests import test_gpu_search_matrix as t
     row = mm.row_of(case)
     gp, opol, p1, seed = _sm_policies(t, oracle, row)
@@ -285,7 +303,7 @@ def fam_sm_eval(case, tw, oracle, cus):
     def call(who, p):
         _, _, result, actions = t.call_evaluate(tw, oracle, row, pol[who], seed)
         return snap_attempts(result, actions)
-    four_runs(case, check, call)
+    (driver or four_runs)(case, check, call)
 
 
 def _denv_p1(module_table, module):
@@ -296,7 +314,7 @@ def _denv_p1(module_table, module):
     return amd_policy(arrs, *module_table.twists(module))
 
 
-def fam_denv_ppo(case, tw, oracle, cus):
+def fam_denv_ppo(case, tw, oracle, cus, driver=None):
     which, module, E = case.ref
     if which == "matrix":
         from tests import device_env_matrix as table
@@ -311,10 +329,10 @@ def fam_denv_ppo(case, tw, oracle, cus):
         check = lambda p: snap_collected(t.check_ppo_collect(tw, module), p)
         collect = lambda pol: t._collect(tw, r, env, pol)
     pol = {"P2": gp, "P1": _denv_p1(table, module)}
-    four_runs(case, check, lambda who, p: snap_collected(collect(pol[who]), p))
+    (driver or four_runs)(case, check, lambda who, p: snap_collected(collect(pol[who]), p))
 
 
-def fam_denv_ppo_queued(case, tw, oracle, cus):
+def fam_denv_ppo_queued(case, tw, oracle, cus, driver=None):
     which, module, groups = case.ref
     if which == "matrix":
         from tests import device_env_matrix as table
@@ -335,17 +353,17 @@ def fam_denv_ppo_queued(case, tw, oracle, cus):
             g = collect(pol[who])
         assert g.stats["rollout_blocks"] == groups
         return snap_collected(g, p)
-    four_runs(case, check, call)
+    (driver or four_runs)(case, check, call)
 
 
-def fam_denv_var(case, tw, oracle, cus):
+def fam_denv_var(case, tw, oracle, cus, driver=None):
     from tests import test_gpu_var_obs as t
     from tests.var_obs_util import E, GAMMA, LAM, SEED, lamps, lamps_policy_arrays
     n = case.ref
     env = lamps(n)
     pol = {"P2": t._policies(oracle, n)[0], "P1": amd_policy(lamps_policy_arrays(n, seed=P1_SEED))}
     check = lambda p: snap_collected(t.check_device_collect(tw, oracle, n, E), p)
-    four_runs(case, check, lambda who, p: snap_collected(tw.collector.PPOCollector(E, GAMMA, LAM, 4).collect(env, pol[who], seed=SEED), p))
+    (driver or four_runs)(case, check, lambda who, p: snap_collected(tw.collector.PPOCollector(E, GAMMA, LAM, 4).collect(env, pol[who], seed=SEED), p))
 
 
 @contextlib.contextmanager
@@ -357,7 +375,7 @@ def _det_exp(oracle):
         oracle.set_det_exp(False)
 
 
-def fam_denv_az(case, tw, oracle, cus):
+def fam_denv_az(case, tw, oracle, cus, driver=None):
     which, module, shape = case.ref
     with _det_exp(oracle):
         if which == "matrix":
@@ -374,10 +392,10 @@ def fam_denv_az(case, tw, oracle, cus):
             check = lambda p: snap_collected(t.check_self_play(tw, oracle, module), p)
             collect = lambda pol: tw.collector.AZCollector(table.E, r.S, table.C_UCB, r.med, 4).collect(env, pol, seed=r.seed)
         pol = {"P2": gp, "P1": _denv_p1(table, module)}
-        four_runs(case, check, lambda who, p: snap_collected(collect(pol[who]), p))
+        (driver or four_runs)(case, check, lambda who, p: snap_collected(collect(pol[who]), p))
 
 
-def fam_denv_solve(case, tw, oracle, cus):
+def fam_denv_solve(case, tw, oracle, cus, driver=None):
     from tests import device_env_solve as D
     from tests import test_gpu_device_env_solve as t
     from tests.util import make_deep_policy_arrays
@@ -396,7 +414,7 @@ def fam_denv_solve(case, tw, oracle, cus):
         def call(who, p):
             res, _, att = t._solve(tw, env, pol[who], False, N, S, 1)
             return snap(res, att)
-        four_runs(case, check, call)
+        (driver or four_runs)(case, check, call)
 
 
 def _python_env(tw, oracle, w, h, steps, emb, common):
@@ -407,24 +425,24 @@ def _python_env(tw, oracle, w, h, steps, emb, common):
     return t, proto, env, pol, oracle_policy(oracle, arrs)
 
 
-def fam_host_ppo(case, tw, oracle, cus):
+def fam_host_ppo(case, tw, oracle, cus, driver=None):
     w, h, steps, emb, common, E = case.ref
     t, proto, env, pol, op = _python_env(tw, oracle, w, h, steps, emb, common)
     check = lambda p: snap_collected(t.check_python_env_ppo(tw, oracle, proto, env, pol["P2"], op, w * h, E, False), p)
     call = lambda who, p: snap_collected(tw.collector.PPOCollector(E, 0.99, 0.95, 4, merge_order=False).collect(env, pol[who], seed=77), p)
-    four_runs(case, check, call)
+    (driver or four_runs)(case, check, call)
 
 
-def fam_host_az(case, tw, oracle, cus):
+def fam_host_az(case, tw, oracle, cus, driver=None):
     w, h, steps, emb, common, E, S, med = case.ref
     t, proto, env, pol, op = _python_env(tw, oracle, w, h, steps, emb, common)
     with _det_exp(oracle):
         check = lambda p: snap_collected(t.check_python_env_self_play(tw, oracle, proto, env, pol["P2"], op, w * h, E, S, med), p)
         call = lambda who, p: snap_collected(tw.collector.AZCollector(min(E, 16), S, 1.41, med, 4).collect(env, pol[who], seed=79), p)
-        four_runs(case, check, call)
+        (driver or four_runs)(case, check, call)
 
 
-def fam_host_solve(case, tw, oracle, cus):
+def fam_host_solve(case, tw, oracle, cus, driver=None):
     w, h, steps, emb, common, (det, ns, S) = case.ref
     t, proto, env, pol, op = _python_env(tw, oracle, w, h, steps, emb, common)
     snap = lambda ge, sv: {"evaluate": tuple(f32_bits(np.float32(x)).tobytes() for x in ge), "solve": (sv[0][0], f32_bits(np.float32(sv[0][1])).tobytes()),
@@ -436,10 +454,10 @@ def fam_host_solve(case, tw, oracle, cus):
         cur = proto.copy(); cur.seed_episode(3, 1); cur.reset(3)
         return snap(ge, tw.collector.solve(tw.env.PyEnv(cur), pol[who], det, ns, S, 1.41, 1, seed=9))
     with _det_exp(oracle):
-        four_runs(case, lambda p: snap(*t.check_python_env_evaluate_and_solve(tw, oracle, proto, env, pol["P2"], op, det, ns, S)), call)
+        (driver or four_runs)(case, lambda p: snap(*t.check_python_env_evaluate_and_solve(tw, oracle, proto, env, pol["P2"], op, det, ns, S)), call)
 
 
-def _handoff(case, tw, normalize):
+def _handoff(case, tw, normalize, driver=None):
     """ppo_data_to_torch on a collect of a layout that follows no rule (tests/free_ids_env.py): the collect itself is host-stepped (its
     staging and its result arena are filled too), the hand-off's sums use call-local scratch."""
     from tests import test_gpu_trainer_handoff as t
@@ -475,18 +493,18 @@ def _handoff(case, tw, normalize):
         snap.update(snap_tensors(out))
         snap["form"], snap["adv_stats"] = form, None if stats is None else tuple(np.float64(x).tobytes() for x in stats)
         return snap
-    four_runs(case, lambda p: run("P2", p, True), lambda who, p: run(who, p, False))
+    (driver or four_runs)(case, lambda p: run("P2", p, True), lambda who, p: run(who, p, False))
 
 
-def fam_handoff_ppo(case, tw, oracle, cus):
-    _handoff(case, tw, True)
+def fam_handoff_ppo(case, tw, oracle, cus, driver=None):
+    _handoff(case, tw, True, driver)
 
 
-def fam_handoff_ppo_plain(case, tw, oracle, cus):
-    _handoff(case, tw, False)
+def fam_handoff_ppo_plain(case, tw, oracle, cus, driver=None):
+    _handoff(case, tw, False, driver)
 
 
-def fam_handoff_az(case, tw, oracle, cus):
+def fam_handoff_az(case, tw, oracle, cus, driver=None):
     from tests import test_gpu_trainer_handoff as t
     from tests.free_ids_env import ACTIONS, FreeIdsWalk, policy_arrays
     from twisterl_amd import trainer
@@ -510,7 +528,7 @@ def fam_handoff_az(case, tw, oracle, cus):
         snap.update(snap_tensors(out))
         snap["form"] = form
         return snap
-    four_runs(case, lambda p: run("P2", p, True), lambda who, p: run(who, p, False))
+    (driver or four_runs)(case, lambda p: run("P2", p, True), lambda who, p: run(who, p, False))
 
 
 FAMILIES = {name[4:]: fn for name, fn in list(globals().items()) if name.startswith("fam_")}

@@ -213,3 +213,39 @@ def test_pyenv_bridge_refuses_observations_that_do_not_fit_the_buffers():
             assert br.err and isinstance(br.err[0], exc)
             with pytest.raises(exc):
                 br.finish(0)
+
+
+# ------------------------------------------------------------------ tw_last_error ("Threads and streams")
+def test_last_error_is_thread_local():
+    """Two threads provoke two different TW_ERR_INVALID messages; after a barrier each reads its own, and the main thread's is untouched."""
+    import ctypes as C
+    import threading
+    from twisterl_amd import _lib
+    L = _lib.lib()
+    assert L.tw_collected_adv_stats(None, None, None) == _lib.TW_ERR_INVALID      # the main thread's own message
+    mine = _lib.last_error()
+    assert "tw_collected_adv_stats" in mine
+    barrier, got, errors = threading.Barrier(2), {}, []
+
+    def body(name, provoke):
+        try:
+            for _ in range(3):
+                assert provoke() == _lib.TW_ERR_INVALID
+                barrier.wait(60)                      # both messages are set ...
+                got.setdefault(name, []).append(_lib.last_error())
+                barrier.wait(60)                      # ... and both are read before either thread sets the next
+        except BaseException as e:                    # noqa: BLE001 (handed to the main thread)
+            errors.append(e)
+            barrier.abort()
+    threads = [threading.Thread(target=body, args=("info", lambda: L.tw_get_device_info(None))),
+               threading.Thread(target=body, args=("stats", lambda: L.tw_collected_stats(None, None)))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(120)
+        assert not t.is_alive()
+    assert not errors, errors
+    assert len(got["info"]) == 3 and len(got["stats"]) == 3
+    assert all("tw_get_device_info" in m and "tw_collected_stats" not in m for m in got["info"]), got
+    assert all("tw_collected_stats" in m and "tw_get_device_info" not in m for m in got["stats"]), got
+    assert _lib.last_error() == mine

@@ -326,6 +326,31 @@ class debug_fill_memory:
         return False
 
 
+class library_stream:
+    """`with library_stream(torch.cuda.Stream()): ...` -- while the block runs, the library calls of THE CALLING THREAD launch on the
+    given stream (tw_set_stream with the stream's raw handle, its `.cuda_stream`; None or 0: the null stream).  Leaving the block puts
+    the null stream back, whatever happened inside.  The setting is thread-local in the library: another thread's calls stay on the
+    stream that thread set (the null stream if it never set one), and a block entered on one thread must be left on the same thread.
+    Blocks do not nest (the library has no getter: the exit restores the null stream, not an enclosing block's stream).  A result
+    produced inside the block may be read, handed over and freed outside it, by any thread: every collect, evaluate and solve returns
+    after its stream has finished, and tw_collected_free fences the producing stream ("Threads and streams").
+    torch's own current stream is not changed: use `torch.cuda.stream(s)` for that."""
+
+    def __init__(self, stream):
+        handle = 0 if stream is None else getattr(stream, "cuda_stream", stream)
+        if not isinstance(handle, int) or handle < 0:
+            raise TypeError("library_stream: a torch.cuda.Stream (or a raw hipStream_t as an int) expected")
+        self.stream, self.handle = stream, handle       # (the stream object is kept alive for the block)
+
+    def __enter__(self):
+        check(lib().tw_set_stream(C.c_void_p(self.handle)))
+        return self
+
+    def __exit__(self, *exc):
+        check(lib().tw_set_stream(None))
+        return False
+
+
 def debug_counters(n: int = 16) -> list:
     """Diagnostic counters of this process's last self-play launch (tw_debug_counters); after an f32 PPO collect: [0] the episodes
     the persistent 256-episode launch handed over, [1] the workgroups of the drain launch (TW_OPT_ROLLOUT_DRAIN), the rest 0."""

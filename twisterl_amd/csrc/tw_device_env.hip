@@ -254,7 +254,9 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     if (f16) {
         const int n_layers = pd->n_common + pd->n_action + pd->n_value;
         std::vector<LayerDev> layers((size_t)n_layers);
-        TW_HIP(hipMemcpy(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost));
+        // (on the library's stream, not the null stream: a blocking copy there would wait for whatever else the process has queued on it)
+        TW_HIP(hipMemcpyAsync(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost, current_stream()));
+        TW_HIP(hipStreamSynchronize(current_stream()));
         image_halves = gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
     }
 
@@ -501,7 +503,8 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
     if (f16) {
         const int n_layers = pd->n_common + pd->n_action + pd->n_value;
         std::vector<LayerDev> layers((size_t)n_layers);
-        TW_HIP(hipMemcpy(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost));
+        TW_HIP(hipMemcpyAsync(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost, current_stream()));   // (as the collect)
+        TW_HIP(hipStreamSynchronize(current_stream()));
         image_halves = gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
     }
 
