@@ -72,6 +72,19 @@ def test_gridworld_kernels_use_no_scratch():
     assert len(sizes) == 2 and all(int(s) == 0 for s in sizes), sizes
 
 
+def test_each_step_loop_exists_once():
+    """The f32 and the f16 kernel of a pair include ONE body file inside their function bodies (no once-pragma: it is included twice);
+    tw_rollout_env.hpp itself holds no step loop.  A loop forked again fails here."""
+    csrc = os.path.join(ROOT, "twisterl_amd", "csrc")
+    head = "while (__syncthreads_or("
+    header = open(os.path.join(csrc, "tw_rollout_env.hpp")).read()
+    assert header.count(head) == 0
+    for body in ("tw_env_rollout_loop.hpp", "tw_env_solve_loop.hpp"):
+        text = open(os.path.join(csrc, body)).read()
+        assert text.count(head) == 1 and "#pragma once" not in text, body
+        assert header.count(f'#include "{body}"') == 2, body
+
+
 _VIOLATIONS = {
     "NUM_ACTIONS must be 1..4": ("NUM_ACTIONS = 5", "N_OBS = 2", ""),
     "N_OBS must be 1..64": ("NUM_ACTIONS = 2", "N_OBS = 65", ""),

@@ -499,10 +499,7 @@ int groups_per_cu_search_env(int kernel, size_t lds_bytes, int *out)
     if (kernel != 2) return groups_per_cu_env<Env>(kernel, lds_bytes, out);
     if (!out) return (int)hipErrorInvalidValue;
     const size_t all = lds_bytes + env_mcts_pending_bytes(Env::N_OBS) + env_mcts_probs_bytes(Env::NUM_ACTIONS);
-    const void *k = reinterpret_cast<const void *>(&mcts_env_kernel<Env, NC>);
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)all);
-    if (e != hipSuccess) return (int)e;
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, EngineV<NC>::THREADS, all);
+    return kernel_groups_per_cu(reinterpret_cast<const void *>(&mcts_env_kernel<Env, NC>), EngineV<NC>::THREADS, all, out);
 }
 
 }  // namespace tw

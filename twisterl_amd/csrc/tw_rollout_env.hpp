@@ -13,6 +13,11 @@
 // (tw_engine_generic16.hpp), PPOCollector(precision="fp16"), within the a-priori bound of the f16-input spec instead of bit-equal.
 // A module built with TW_DEVICE_ENV_FP16_SOLVE holds solve_env16_kernel<Env, NC> as well: evaluate's loop over EngineV16,
 // collector.evaluate / collector.solve with precision="fp16" and no MCTS.
+//
+// In this file: the argument structs and the descriptor; what the steps call (the Gumbel arg-max, the twist of the actions, the
+// streaming steps of 5 .. 31 actions, env_rows / env_rows_n); the four kernels; their launchers and occupancy queries.  The two step
+// loops are NOT here: tw_env_rollout_loop.hpp and tw_env_solve_loop.hpp hold the text of each once, and its f32 and f16 kernels
+// include it inside their bodies.  A change to a step is made there, and reaches both kernels.
 #pragma once
 #include "tw_engine_generic.hpp"
 #include "tw_engine_generic16.hpp"
@@ -335,280 +340,35 @@ __device__ __forceinline__ int env_rows_n(const Env &st, const PolicyDev &pol, i
     return n;
 }
 
-// Persistent form (a.queue != null; a kernel-argument-uniform branch, not a second instantiation): the grid holds fewer columns than
-// there are episodes, and at the end of a step -- where ids and rowoff are dead -- a column whose episode is over takes the next index
-// from the counter.  The writer lane draws it; it goes round to every lane of every wave that carries column j through lds_user and
-// one barrier, which depends on a.queue alone (as rollout_f32_kernel does for Eng::SPLIT).  Records, ids and ep_len are addressed by
-// episode, so the bytes are those of the plain launch whichever column ran an episode.
+// The four kernels.  Each step loop exists ONCE, as a body file that its f32 and its f16 kernel include inside their function
+// bodies (tw_env_rollout_loop.hpp, tw_env_solve_loop.hpp: the loops' comments are there, and what a kernel declares in front of the
+// #include).  A kernel is its engine, its LDS and that #include; the two of a pair differ in `Eng` and in where the arguments and the
+// image come from, and in nothing else.  Shared by inclusion and not through a function template, because the f32 kernels are to stay
+// what they are, instruction for instruction: with the loop in one __forceinline__ function that both kernels inline, this compiler
+// allocated the f32 kernels differently (ProbeO64A4S: 1,032 instead of 1,040 bytes of scratch memory, GridWorld 5 x 5: 160 instead of
+// 164 spilled SGPRs, or 280 instead of 276 VGPRs with the arguments by value), while the included text compiles to the assembly the
+// written-out loops compiled to (device environments; profiles/r19_env_loop_identity.txt).
 template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) rollout_env_kernel(const EnvRolloutArgs a, const Env proto)
 {
     using Eng = EngineV<NC>;
-    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
-    // EngineV<64> alone takes some 450 registers: a fixed-length observation of 37 .. 64 ids kept alive across the forward on top of
-    // them spilled to scratch memory.  There the ids are stored BEFORE the forward, as env_rows_n stores a variable-length record's
-    // (of an observation with a bad id the row is written all the same; the collect fails and nobody reads it)
-    constexpr bool EARLY_IDS = NC > 36 && !EnvHasObserveN<Env>::value;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
-    eng.begin1(a.pol, lds);
-    const int j = eng.j;
-    // every lane group of every wave carries the state of column j (the engine's mapping); lanes 0-15 of wave 0 store
-    const uint64_t e_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-    const bool valid  = e_first < a.num_episodes;
-    const bool writer = eng.h == 0 && eng.primary();
-    uint32_t e_taken = 0xffffffffu;                                                   // the episode taken from the queue; none: e_first
-    Env st = proto;
-    bool alive = valid;
-    bool fresh = valid;                                                               // the column's episode is still to be reset
-    bool more  = valid && a.queue != nullptr;                                         // the queue may still hold episodes
-    int  t = 0;
-    eng.begin2();
-    while (__syncthreads_or(alive ? 1 : 0)) {
-        const uint64_t e_local  = e_taken != 0xffffffffu ? (uint64_t)e_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-        const uint64_t e_global = a.episode_offset + e_local;
-        // the ONE place the struct's reset() is called from, the column's first episode and every one it takes from the queue alike
-        // (with a second call site the compiler stopped inlining it, and the state went to scratch memory)
-        if (fresh) {
-            st = proto;                                                               // clone of the prototype (ppo.rs:59)
-            st.reset(a.seed, e_global);                                               // ppo.rs:60
-            fresh = false;
-        }
-        int perm = -1;
-        if (eng.pol.n_perms > 0) {                                                    // get_perm_id (policy.rs:67-77)
-            const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_PERM);
-            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
-        }
-        int ids[NO], rowoff[NC];
-        bool bad = false; int bad_id = 0;
-        [[maybe_unused]] bool bad_count = false;                                      // (a struct with observe_n: a count outside 0 .. n_obs)
-        if (alive) {
-            if constexpr (EnvHasObserveN<Env>::value)
-                (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count,
-                                          writer ? a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)env_n_obs(st) : nullptr);
-            else {
-                env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
-                if constexpr (EARLY_IDS) {
-                    if (writer) {
-                        const int n = env_n_obs(st);
-                        uint16_t *o = a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)n;
-#pragma unroll
-                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
-        }
-        float lg[4]; float value, rew; int action;
-        if constexpr (A > 4) {
-            // the masked logits go to their own array (the record's four slots stay zero); a record that is not pushed stores none
-            const float *head = eng.forward_head(rowoff, value);
-            const uint32_t mb = alive ? st.masks() : 0u;
-            rew = alive ? st.reward() : 0.0f;
-            float *row = alive && !bad ? a.lgw + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)A : nullptr;
-            action = env_gumbel_stream<A>(eng.pol, head, j, eng.g, perm, mb, a.seed, e_global, (uint32_t)t, row);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) lg[i] = 0.0f;
-        } else {
-        eng.forward(rowoff, lg, value);
-        env_act_perm<A>(eng.pol, perm, lg);
-        const uint32_t mb = alive ? st.masks() : 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lg[i] = (i < A && ((mb >> i) & 1u)) ? lg[i] : -1e10f;    // policy.rs:62
-        rew = alive ? st.reward() : 0.0f;
-        const u32x4 gw = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_GUMBEL);
-        action = gumbel_argmax_n<A>(lg, gw);
-        }
-        if (alive) {
-            bool failed = false;
-            if (bad) {                                                                // (the host path fails the collect here)
-                if (writer) {                                                         // the library names the first one (t, episode)
-                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
-                    store_rec(a.out.rec + e_local * (uint64_t)a.out.t_pad + (uint64_t)t, zero4, lg, __builtin_bit_cast(float, bad_id), bad_count ? 1.0f : 0.0f, 0, -1);
-                    atomicOr(a.err, bad_count ? 8u : 1u);
-                }
-                failed = true;
-                alive = false;
-            } else {
-                if (writer) {                                                         // push the record (ppo.rs:71-76)
-                    const uint64_t rec = e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
-                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
-                    store_rec(a.out.rec + rec, zero4, lg, value, rew, action, perm);
-                    if constexpr (!EnvHasObserveN<Env>::value && !EARLY_IDS) {        // (observe_n: env_rows_n has stored them)
-                        const int n = env_n_obs(st);
-                        uint16_t *o = a.obs16 + rec * (uint64_t)n;
-#pragma unroll
-                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
-                    }
-                }
-                if (st.is_final()) alive = false;                                     // ppo.rs:78
-                else if (t + 1 >= a.out.t_pad) {                                      // the host path's max_records_per_episode
-                    if (writer) atomicOr(a.err, 2u);
-                    alive = false;
-                } else { st.step(action); ++t; }                                      // ppo.rs:79
-            }
-            // the episode is over: its length at once (the column may go on with another one)
-            if (!alive && writer) a.out.ep_len[e_local] = ((uint32_t)t + 1u) | (failed ? 0x80000000u : 0u);
-        }
-        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
-            const bool want = !alive && more;
-            unsigned got = 0xffffffffu;
-            if (want && writer) got = atomicAdd(a.queue, 1u);
-            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
-            if (writer) bc[j] = got;
-            __syncthreads();
-            got = bc[j];
-            if (want) {
-                if ((uint64_t)got < a.num_episodes) {
-                    e_taken = got;
-                    t = 0; alive = true; fresh = true;                                // (reset at the top of the next step)
-                } else more = false;
-            }
-        }
-    }
-    eng.end();
+#include "tw_env_rollout_loop.hpp"
 }
 
 // The same loop over EngineV16 (tw_engine_generic16.hpp): precision="fp16" of PPOCollector.collect.  A module holds it when it was
 // built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)); pack_generic16_kernel runs in front of it, on the same stream.
-// It carries its OWN COPY of rollout_env_kernel's step loop, line for line but for the engine and the argument struct: with the loop
-// in one function template that both kernels inline, this compiler allocated the f32 kernels differently (ProbeO64A4S: 1,032 instead
-// of 1,040 bytes of scratch memory, GridWorld 5 x 5: 160 instead of 164 spilled SGPRs), and the f32 kernels are to stay what they
-// are.  A change to one loop belongs in the other: tests/test_gpu_device_env_fp16.py holds this kernel's environment side, record
-// by record, to the same host code the f32 kernel is held to.
+// tests/test_gpu_device_env_fp16.py holds its environment side, record by record, to the host code the f32 kernel is held to.
 template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) rollout_env16_kernel(const EnvRollout16Args a16, const Env proto)
 {
     using Eng = EngineV16<NC>;
     const EnvRolloutArgs &a = a16.r;
-    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
-    // EngineV<64> alone takes some 450 registers: a fixed-length observation of 37 .. 64 ids kept alive across the forward on top of
-    // them spilled to scratch memory.  There the ids are stored BEFORE the forward, as env_rows_n stores a variable-length record's
-    // (of an observation with a bad id the row is written all the same; the collect fails and nobody reads it)
-    constexpr bool EARLY_IDS = NC > 36 && !EnvHasObserveN<Env>::value;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.img = a16.image.img;
-    eng.begin1(a.pol, lds);
-    const int j = eng.j;
-    // every lane group of every wave carries the state of column j (the engine's mapping); lanes 0-15 of wave 0 store
-    const uint64_t e_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-    const bool valid  = e_first < a.num_episodes;
-    const bool writer = eng.h == 0 && eng.primary();
-    uint32_t e_taken = 0xffffffffu;                                                   // the episode taken from the queue; none: e_first
-    Env st = proto;
-    bool alive = valid;
-    bool fresh = valid;                                                               // the column's episode is still to be reset
-    bool more  = valid && a.queue != nullptr;                                         // the queue may still hold episodes
-    int  t = 0;
-    eng.begin2();
-    while (__syncthreads_or(alive ? 1 : 0)) {
-        const uint64_t e_local  = e_taken != 0xffffffffu ? (uint64_t)e_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-        const uint64_t e_global = a.episode_offset + e_local;
-        // the ONE place the struct's reset() is called from, the column's first episode and every one it takes from the queue alike
-        // (with a second call site the compiler stopped inlining it, and the state went to scratch memory)
-        if (fresh) {
-            st = proto;                                                               // clone of the prototype (ppo.rs:59)
-            st.reset(a.seed, e_global);                                               // ppo.rs:60
-            fresh = false;
-        }
-        int perm = -1;
-        if (eng.pol.n_perms > 0) {                                                    // get_perm_id (policy.rs:67-77)
-            const u32x4 w = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_PERM);
-            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
-        }
-        int ids[NO], rowoff[NC];
-        bool bad = false; int bad_id = 0;
-        [[maybe_unused]] bool bad_count = false;                                      // (a struct with observe_n: a count outside 0 .. n_obs)
-        if (alive) {
-            if constexpr (EnvHasObserveN<Env>::value)
-                (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count,
-                                          writer ? a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)env_n_obs(st) : nullptr);
-            else {
-                env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
-                if constexpr (EARLY_IDS) {
-                    if (writer) {
-                        const int n = env_n_obs(st);
-                        uint16_t *o = a.obs16 + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)n;
-#pragma unroll
-                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
-        }
-        float lg[4]; float value, rew; int action;
-        if constexpr (A > 4) {
-            // the masked logits go to their own array (the record's four slots stay zero); a record that is not pushed stores none
-            const float *head = eng.forward_head(rowoff, value);
-            const uint32_t mb = alive ? st.masks() : 0u;
-            rew = alive ? st.reward() : 0.0f;
-            float *row = alive && !bad ? a.lgw + (e_local * (uint64_t)a.out.t_pad + (uint64_t)t) * (uint64_t)A : nullptr;
-            action = env_gumbel_stream<A>(eng.pol, head, j, eng.g, perm, mb, a.seed, e_global, (uint32_t)t, row);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) lg[i] = 0.0f;
-        } else {
-        eng.forward(rowoff, lg, value);
-        env_act_perm<A>(eng.pol, perm, lg);
-        const uint32_t mb = alive ? st.masks() : 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lg[i] = (i < A && ((mb >> i) & 1u)) ? lg[i] : -1e10f;    // policy.rs:62
-        rew = alive ? st.reward() : 0.0f;
-        const u32x4 gw = rng_draw(a.seed, e_global, (uint32_t)t, STREAM_GUMBEL);
-        action = gumbel_argmax_n<A>(lg, gw);
-        }
-        if (alive) {
-            bool failed = false;
-            if (bad) {                                                                // (the host path fails the collect here)
-                if (writer) {                                                         // the library names the first one (t, episode)
-                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
-                    store_rec(a.out.rec + e_local * (uint64_t)a.out.t_pad + (uint64_t)t, zero4, lg, __builtin_bit_cast(float, bad_id), bad_count ? 1.0f : 0.0f, 0, -1);
-                    atomicOr(a.err, bad_count ? 8u : 1u);
-                }
-                failed = true;
-                alive = false;
-            } else {
-                if (writer) {                                                         // push the record (ppo.rs:71-76)
-                    const uint64_t rec = e_local * (uint64_t)a.out.t_pad + (uint64_t)t;
-                    const uint32_t zero4[4] = {0u, 0u, 0u, 0u};
-                    store_rec(a.out.rec + rec, zero4, lg, value, rew, action, perm);
-                    if constexpr (!EnvHasObserveN<Env>::value && !EARLY_IDS) {        // (observe_n: env_rows_n has stored them)
-                        const int n = env_n_obs(st);
-                        uint16_t *o = a.obs16 + rec * (uint64_t)n;
-#pragma unroll
-                        for (int i = 0; i < NO; ++i) if (i < n) o[i] = (uint16_t)ids[i];
-                    }
-                }
-                if (st.is_final()) alive = false;                                     // ppo.rs:78
-                else if (t + 1 >= a.out.t_pad) {                                      // the host path's max_records_per_episode
-                    if (writer) atomicOr(a.err, 2u);
-                    alive = false;
-                } else { st.step(action); ++t; }                                      // ppo.rs:79
-            }
-            // the episode is over: its length at once (the column may go on with another one)
-            if (!alive && writer) a.out.ep_len[e_local] = ((uint32_t)t + 1u) | (failed ? 0x80000000u : 0u);
-        }
-        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
-            const bool want = !alive && more;
-            unsigned got = 0xffffffffu;
-            if (want && writer) got = atomicAdd(a.queue, 1u);
-            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
-            if (writer) bc[j] = got;
-            __syncthreads();
-            got = bc[j];
-            if (want) {
-                if ((uint64_t)got < a.num_episodes) {
-                    e_taken = got;
-                    t = 0; alive = true; fresh = true;                                // (reset at the top of the next step)
-                } else more = false;
-            }
-        }
-    }
-    eng.end();
+#include "tw_env_rollout_loop.hpp"
 }
 
 // evaluate() (rust/src/rl/evaluate.rs:22-89 over single_solve, rl/solve.rs:17-71), as solve_big_kernel: one column = one attempt
@@ -620,241 +380,50 @@ template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) solve_env_kernel(const EnvSolveArgs a, const Env proto)
 {
     using Eng = EngineV<NC>;
-    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
-    eng.begin1(a.pol, lds);
-    const int j = eng.j;
-    const uint64_t att_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-    const bool valid = att_first < a.num_attempts, writer = eng.h == 0 && eng.primary();
-    uint32_t att_taken = 0xffffffffu;                                                 // the attempt taken from the queue; none: att_first
-    Env st = proto;
-    bool  alive = valid;                                                              // (a fresh attempt: until its reset below says otherwise)
-    bool  fresh = valid;                                                              // the column's attempt is still to be reset
-    bool  more  = valid && a.queue != nullptr;
-    float total = 0.0f;
-    int   t = 0;
-    eng.begin2();
-    while (__syncthreads_or(alive ? 1 : 0)) {
-        const uint64_t att = att_taken != 0xffffffffu ? (uint64_t)att_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-        const uint64_t key = a.episode_offset * (uint64_t)a.num_searches + att;       // keys this attempt's draws
-        bool ended = false;                                                           // the attempt ended by itself in this step
-        // the ONE place reset() is called from (see rollout_env_kernel).  A fresh attempt whose reset state is already final is over
-        // at once (solve.rs:29): its column feeds no row to this step's forward and takes the next attempt at the end of it
-        if (fresh) {
-            st = proto;                                                               // evaluate.rs:39 / solve.rs:85
-            if (!a.from_state) st.reset(a.seed, a.episode_offset + att / a.num_searches);   // the episode keys the start state
-            total = 0.0f; t = 0; fresh = false;
-            alive = !st.is_final();
-            ended = !alive;
-        }
-        int perm = -1;
-        if (eng.pol.n_perms > 0) {
-            const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_PERM);
-            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
-        }
-        int ids[NO], rowoff[NC];
-        bool bad = false; int bad_id = 0;
-        [[maybe_unused]] bool bad_count = false;
-        if (alive) {
-            if constexpr (EnvHasObserveN<Env>::value) (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count, nullptr);
-            else env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
-        }
-        float lg[4], value;
-        [[maybe_unused]] const float *head = nullptr;
-        if constexpr (A > 4) head = eng.forward_head(rowoff, value);
-        else {
-            eng.forward(rowoff, lg, value);
-            env_act_perm<A>(eng.pol, perm, lg);
-        }
-        const uint32_t mb = (alive ? st.masks() : 0u) & ((1u << A) - 1u);
-        [[maybe_unused]] float probs[4];
-        if constexpr (A <= 4) masked_softmax4(lg, mb, probs);                         // policy.rs:43-47 (masked entries add +0.0)
-        if (alive) {
-            if (bad) {
-                if (writer) {
-                    atomicOr(a.err, bad_count ? 8u : 1u);
-                    a.success[att] = bad_count ? 2.0f : (st.success() ? 1.0f : 0.0f);
-                    a.total[att]   = __builtin_bit_cast(float, bad_id);
-                    a.n_steps[att] = (uint32_t)t | 0x80000000u;
-                }
-                alive = false;
-            } else {
-                total = total + st.reward();                                          // solve.rs:31
-                int action = 0;
-                if constexpr (A > 4) {
-                    float u = 0.0f;
-                    if (!a.deterministic) u = u32_to_unit(rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE).x);
-                    action = env_predict_stream<A>(eng.pol, head, j, perm, mb, a.deterministic != 0u, u);
-                } else if (a.deterministic) {
-                    float bv = probs[0];
-#pragma unroll
-                    for (int i = 1; i < A; ++i) if (probs[i] > bv) { bv = probs[i]; action = i; }
-                } else {
-                    const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE);
-                    action = sample_weighted4(probs, A, u32_to_unit(w.x));
-                }
-                st.step(action);                                                      // solve.rs:56
-                // solve.rs:57-59: the move, into the attempt's own row (alive: att < num_attempts)
-                if (writer && a.actions != nullptr && (uint32_t)t < a.actions_stride) a.actions[att * (uint64_t)a.actions_stride + (uint64_t)t] = (uint8_t)action;
-                ++t;
-                if (st.is_final()) alive = false;
-                else if ((uint32_t)t >= a.max_steps) {                                // the host path's max_steps
-                    if (writer) atomicOr(a.err, 4u);
-                    alive = false;
-                }
-                ended = !alive;
-            }
-        }
-        if (ended && writer) {                                                        // its results (solve.rs:65-68), after t moves
-            a.success[att] = st.success() ? 1.0f : 0.0f;
-            a.total[att]   = total + st.reward();
-            a.n_steps[att] = (uint32_t)t;
-        }
-        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
-            const bool want = !alive && more;
-            unsigned got = 0xffffffffu;
-            if (want && writer) got = atomicAdd(a.queue, 1u);
-            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
-            if (writer) bc[j] = got;
-            __syncthreads();
-            got = bc[j];
-            if (want) {
-                if ((uint64_t)got < a.num_attempts) {
-                    att_taken = got;
-                    alive = true; fresh = true;                                       // (reset at the top of the next step)
-                } else more = false;
-            }
-        }
-    }
-    eng.end();
+#include "tw_env_solve_loop.hpp"
 }
 
 // The same loop over EngineV16: precision="fp16" of collector.evaluate and collector.solve without MCTS.  A module holds it when it
 // was built with TW_DEVICE_ENV_FP16_SOLVE (build_device_env(..., fp16_solve=True)); pack_generic16_kernel runs in front of it, on the
-// same stream, into EnvSolveArgs::image.  Its OWN COPY of solve_env_kernel's step loop, line for line but for the engine and the
-// image, as rollout_env16_kernel is of rollout_env_kernel's and for the same reason: the f32 kernels are to stay what they are.  A
-// change to one loop belongs in the other: tests/test_gpu_device_env_fp16_solve.py holds this kernel, attempt by attempt, to the
-// oracle's ARITH_F16 loop over the module's host code.
+// same stream, into EnvSolveArgs::image.  tests/test_gpu_device_env_fp16_solve.py holds it, attempt by attempt, to the oracle's
+// ARITH_F16 loop over the module's host code.
 template <class Env, int NC>
 __global__ void __launch_bounds__(256, 1) solve_env16_kernel(const EnvSolveArgs a, const Env proto)
 {
     using Eng = EngineV16<NC>;
-    constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Eng eng;
     eng.img = a.image.img;
-    eng.begin1(a.pol, lds);
-    const int j = eng.j;
-    const uint64_t att_first = (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-    const bool valid = att_first < a.num_attempts, writer = eng.h == 0 && eng.primary();
-    uint32_t att_taken = 0xffffffffu;                                                 // the attempt taken from the queue; none: att_first
-    Env st = proto;
-    bool  alive = valid;                                                              // (a fresh attempt: until its reset below says otherwise)
-    bool  fresh = valid;                                                              // the column's attempt is still to be reset
-    bool  more  = valid && a.queue != nullptr;
-    float total = 0.0f;
-    int   t = 0;
-    eng.begin2();
-    while (__syncthreads_or(alive ? 1 : 0)) {
-        const uint64_t att = att_taken != 0xffffffffu ? (uint64_t)att_taken : (uint64_t)blockIdx.x * Eng::EPB + (uint64_t)j;
-        const uint64_t key = a.episode_offset * (uint64_t)a.num_searches + att;       // keys this attempt's draws
-        bool ended = false;                                                           // the attempt ended by itself in this step
-        // the ONE place reset() is called from (see rollout_env_kernel).  A fresh attempt whose reset state is already final is over
-        // at once (solve.rs:29): its column feeds no row to this step's forward and takes the next attempt at the end of it
-        if (fresh) {
-            st = proto;                                                               // evaluate.rs:39 / solve.rs:85
-            if (!a.from_state) st.reset(a.seed, a.episode_offset + att / a.num_searches);   // the episode keys the start state
-            total = 0.0f; t = 0; fresh = false;
-            alive = !st.is_final();
-            ended = !alive;
-        }
-        int perm = -1;
-        if (eng.pol.n_perms > 0) {
-            const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_PERM);
-            perm = (int)u32_below(w.x, (uint32_t)eng.pol.n_perms);
-        }
-        int ids[NO], rowoff[NC];
-        bool bad = false; int bad_id = 0;
-        [[maybe_unused]] bool bad_count = false;
-        if (alive) {
-            if constexpr (EnvHasObserveN<Env>::value) (void)env_rows_n<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id, bad_count, nullptr);
-            else env_rows<Env, NC>(st, eng.pol, perm, ids, rowoff, bad, bad_id);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NC; ++i) rowoff[i] = -1;
-        }
-        float lg[4], value;
-        [[maybe_unused]] const float *head = nullptr;
-        if constexpr (A > 4) head = eng.forward_head(rowoff, value);
-        else {
-            eng.forward(rowoff, lg, value);
-            env_act_perm<A>(eng.pol, perm, lg);
-        }
-        const uint32_t mb = (alive ? st.masks() : 0u) & ((1u << A) - 1u);
-        [[maybe_unused]] float probs[4];
-        if constexpr (A <= 4) masked_softmax4(lg, mb, probs);                         // policy.rs:43-47 (masked entries add +0.0)
-        if (alive) {
-            if (bad) {
-                if (writer) {
-                    atomicOr(a.err, bad_count ? 8u : 1u);
-                    a.success[att] = bad_count ? 2.0f : (st.success() ? 1.0f : 0.0f);
-                    a.total[att]   = __builtin_bit_cast(float, bad_id);
-                    a.n_steps[att] = (uint32_t)t | 0x80000000u;
-                }
-                alive = false;
-            } else {
-                total = total + st.reward();                                          // solve.rs:31
-                int action = 0;
-                if constexpr (A > 4) {
-                    float u = 0.0f;
-                    if (!a.deterministic) u = u32_to_unit(rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE).x);
-                    action = env_predict_stream<A>(eng.pol, head, j, perm, mb, a.deterministic != 0u, u);
-                } else if (a.deterministic) {
-                    float bv = probs[0];
-#pragma unroll
-                    for (int i = 1; i < A; ++i) if (probs[i] > bv) { bv = probs[i]; action = i; }
-                } else {
-                    const u32x4 w = rng_draw(a.seed, key, (uint32_t)t, STREAM_SOLVE);
-                    action = sample_weighted4(probs, A, u32_to_unit(w.x));
-                }
-                st.step(action);                                                      // solve.rs:56
-                // solve.rs:57-59: the move, into the attempt's own row (alive: att < num_attempts)
-                if (writer && a.actions != nullptr && (uint32_t)t < a.actions_stride) a.actions[att * (uint64_t)a.actions_stride + (uint64_t)t] = (uint8_t)action;
-                ++t;
-                if (st.is_final()) alive = false;
-                else if ((uint32_t)t >= a.max_steps) {                                // the host path's max_steps
-                    if (writer) atomicOr(a.err, 4u);
-                    alive = false;
-                }
-                ended = !alive;
-            }
-        }
-        if (ended && writer) {                                                        // its results (solve.rs:65-68), after t moves
-            a.success[att] = st.success() ? 1.0f : 0.0f;
-            a.total[att]   = total + st.reward();
-            a.n_steps[att] = (uint32_t)t;
-        }
-        if (a.queue) {                                                                // (uniform: the barrier depends on it alone)
-            const bool want = !alive && more;
-            unsigned got = 0xffffffffu;
-            if (want && writer) got = atomicAdd(a.queue, 1u);
-            unsigned *bc = reinterpret_cast<unsigned *>(eng.lds_user);
-            if (writer) bc[j] = got;
-            __syncthreads();
-            got = bc[j];
-            if (want) {
-                if ((uint64_t)got < a.num_attempts) {
-                    att_taken = got;
-                    alive = true; fresh = true;                                       // (reset at the top of the next step)
-                } else more = false;
-            }
-        }
-    }
-    eng.end();
+#include "tw_env_solve_loop.hpp"
+}
+
+// ---- launchers (host) ---------------------------------------------------------------------------------------------------------------------
+// hipFuncSetAttribute (the kernel's dynamic LDS) and then the kernel's own answer to how many of its workgroups a CU holds at once:
+// tw_device_env::groups_per_cu / groups_per_cu16 of every kernel
+inline int kernel_groups_per_cu(const void *k, int threads, size_t lds_bytes, int *out)
+{
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, threads, lds_bytes);
+}
+
+// What the launcher of an f16 kernel `k` does before it launches it: refuses a missing image and a policy EngineV16 does not take
+// (hipErrorInvalidValue, before any HIP call), sets k's dynamic LDS, and packs the policy's f32 copies into the image on stream s.
+// The pack runs in front of EVERY launch: the image is never older than the policy's f32 copies.  Its grid: one thread per eight
+// halves, at most 1,024 workgroups (grid-stride beyond).  (A template, so that only a module with an f16 kernel holds the pack kernel.)
+template <class Kernel>
+int pack_image_for(Kernel *k, size_t lds_bytes, const PolicyDev &pol, const Gen16Image &image, hipStream_t s)
+{
+    const int n_layers = pol.n_common + pol.n_action + pol.n_value;
+    if (!image.img || !pol.generic || n_layers > GEN16_MAX_LAYERS) return (int)hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    uint64_t pb = (image.halves / 8 + 255) / 256;
+    if (pb > 1024) pb = 1024;
+    hipLaunchKernelGGL((pack_generic16_kernel<256>), dim3((unsigned)(pb ? pb : 1)), dim3(256), 0, s, pol, image);
+    return (int)hipGetLastError();
 }
 
 template <class Env>
@@ -870,25 +439,16 @@ int launch_rollout_env(const EnvRolloutArgs *a, const void *proto, unsigned bloc
     return (int)hipGetLastError();
 }
 
-// tw_device_env::launch_rollout16 / groups_per_cu16.  The pack runs in front of EVERY rollout: the image is never older than the
-// policy's f32 copies.  Its grid: one thread per eight halves, at most 1,024 workgroups (grid-stride beyond).
+// tw_device_env::launch_rollout16 / groups_per_cu16
 template <class Env>
 int launch_rollout_env16(const EnvRollout16Args *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
 {
     constexpr int NC = env_engine_nc(Env::N_OBS);
     Env p;
     __builtin_memcpy(&p, proto, sizeof(Env));
-    const PolicyDev &pol = a->r.pol;
-    const int n_layers = pol.n_common + pol.n_action + pol.n_value;
-    if (!a->image.img || !pol.generic || n_layers > GEN16_MAX_LAYERS) return (int)hipErrorInvalidValue;
-    const void *k = reinterpret_cast<const void *>(&rollout_env16_kernel<Env, NC>);
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    uint64_t pb = (a->image.halves / 8 + 255) / 256;
-    if (pb > 1024) pb = 1024;
-    hipLaunchKernelGGL((pack_generic16_kernel<256>), dim3((unsigned)(pb ? pb : 1)), dim3(256), 0, s, pol, a->image);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    auto *k = &rollout_env16_kernel<Env, NC>;         // (taken BEFORE the call: a module's assembly lists its kernels in the order they are first named)
+    const int e = pack_image_for(k, lds_bytes, a->r.pol, a->image, s);
+    if (e != (int)hipSuccess) return e;
     hipLaunchKernelGGL((rollout_env16_kernel<Env, NC>), dim3(blocks), dim3(EngineV16<NC>::THREADS), lds_bytes, s, *a, p);
     return (int)hipGetLastError();
 }
@@ -898,10 +458,7 @@ int groups_per_cu_env16(size_t lds_bytes, int *out)
 {
     constexpr int NC = env_engine_nc(Env::N_OBS);
     if (!out) return (int)hipErrorInvalidValue;
-    const void *k = reinterpret_cast<const void *>(&rollout_env16_kernel<Env, NC>);
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, EngineV16<NC>::THREADS, lds_bytes);
+    return kernel_groups_per_cu(reinterpret_cast<const void *>(&rollout_env16_kernel<Env, NC>), EngineV16<NC>::THREADS, lds_bytes, out);
 }
 
 // tw_device_env::groups_per_cu of a module without the search kernel (with it: groups_per_cu_search_env, tw_mcts_env.hpp)
@@ -914,17 +471,12 @@ int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
     // the module HOLDS the kernel (the library's attempts_on_device(), DeviceEnv.fp16_solve): answered without the HIP runtime
     if (kernel == 3) {
         if (!out) return (int)hipSuccess;
-        const void *k16 = reinterpret_cast<const void *>(&solve_env16_kernel<Env, NC>);
-        hipError_t e16 = hipFuncSetAttribute(k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e16 != hipSuccess) return (int)e16;
-        return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k16, EngineV16<NC>::THREADS, lds_bytes);
+        return kernel_groups_per_cu(reinterpret_cast<const void *>(&solve_env16_kernel<Env, NC>), EngineV16<NC>::THREADS, lds_bytes, out);
     }
 #endif
     if (!out || (kernel != 0 && kernel != 1)) return (int)hipErrorInvalidValue;
     const void *k = kernel == 0 ? reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>) : reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, EngineV<NC>::THREADS, lds_bytes);
+    return kernel_groups_per_cu(k, EngineV<NC>::THREADS, lds_bytes, out);
 }
 
 // tw_device_env::launch_solve.  EnvSolveArgs::image.img null: solve_env_kernel.  Else the pack of the image and solve_env16_kernel,
@@ -938,17 +490,9 @@ int launch_solve_env(const EnvSolveArgs *a, const void *proto, unsigned blocks, 
     __builtin_memcpy(&p, proto, sizeof(Env));
     if (a->image.img) {
 #ifdef TW_DEVICE_ENV_FP16_SOLVE
-        const PolicyDev &pol = a->pol;
-        const int n_layers = pol.n_common + pol.n_action + pol.n_value;
-        if (!pol.generic || n_layers > GEN16_MAX_LAYERS) return (int)hipErrorInvalidValue;
-        const void *k16 = reinterpret_cast<const void *>(&solve_env16_kernel<Env, NC>);
-        hipError_t e16 = hipFuncSetAttribute(k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e16 != hipSuccess) return (int)e16;
-        uint64_t pb = (a->image.halves / 8 + 255) / 256;
-        if (pb > 1024) pb = 1024;
-        hipLaunchKernelGGL((pack_generic16_kernel<256>), dim3((unsigned)(pb ? pb : 1)), dim3(256), 0, s, pol, a->image);
-        e16 = hipGetLastError();
-        if (e16 != hipSuccess) return (int)e16;
+        auto *k16 = &solve_env16_kernel<Env, NC>;         // (taken before the call, as in launch_rollout_env16)
+        const int e16 = pack_image_for(k16, lds_bytes, a->pol, a->image, s);
+        if (e16 != (int)hipSuccess) return e16;
         hipLaunchKernelGGL((solve_env16_kernel<Env, NC>), dim3(blocks), dim3(EngineV16<NC>::THREADS), lds_bytes, s, *a, p);
         return (int)hipGetLastError();
 #else
