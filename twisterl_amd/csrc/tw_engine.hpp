@@ -221,6 +221,53 @@ struct Engine3 {
         }
     }
 
+    // rows_of for the step loop of the 256-episode rollout: the same rows from the launch constants of `a` (the kernel's view of its
+    // kernarg segment, read here and dead before the forward) instead of from members that live across the forward in spilled
+    // scalar registers, and without a branch per cell.  The twist tables in LDS (begin1) are read as LDS, not through a generic
+    // pointer.  Every twist of a lane is -1 or below n_perms here (the kernel draws it in front of this call), so
+    // perm * obs_size + id stays inside the table for the cells of the board; a cell beyond the board (n_cells < NC, one
+    // wave-uniform test for all of them) reads entry 0 and takes the zero row.  A row is at most 257: a 24-bit multiply-add.
+    template <class Args>
+    __device__ __forceinline__ void rows_of_args(Args &a, uint64_t board, int perm, int (&rowoff)[NC]) const
+    {
+        const int n_cells = a.env.n_cells, obs_size = a.pol.obs_size, n_perms = a.pol.n_perms;
+        const bool tw = perm >= 0, full = n_cells == NC;
+        uint32_t id[NC], row[NC];
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            uint32_t first = (uint32_t)(i * n_cells);                   // (a scalar product, not a 64-bit vector multiply-add per cell)
+            asm("" : "+s"(first));
+            id[i] = first + nib(board, i);
+        }
+        if (!full) {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) id[i] = i < n_cells ? id[i] : 0u;
+        }
+        if (n_perms > 0) {
+            const uint32_t pb = tw ? (uint32_t)perm * (uint32_t)obs_size : 0u;
+            if (n_perms <= MAX_LDS_PERMS) {
+                const __attribute__((address_space(3))) uint8_t *po = (const __attribute__((address_space(3))) uint8_t *)(lds_bh + 8) + pb;
+#pragma unroll
+                for (int i = 0; i < NC; ++i) row[i] = po[id[i]];
+            } else {
+                const uint8_t *po = a.pol.obs_perms + pb;
+#pragma unroll
+                for (int i = 0; i < NC; ++i) row[i] = po[id[i]];
+            }
+#pragma unroll
+            for (int i = 0; i < NC; ++i) row[i] = tw ? row[i] : id[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) row[i] = id[i];
+        }
+        if (!full) {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) row[i] = i < n_cells ? row[i] : (uint32_t)obs_size + 1u;
+        }
+#pragma unroll
+        for (int i = 0; i < NC; ++i) rowoff[i] = (int)(__umul24(row[i], (uint32_t)LSTR) + (uint32_t)(h * (KC / 2)));
+    }
+
     __device__ __forceinline__ void act_perm(int perm, float (&lg)[4]) const
     {
         if (perm < 0) return;
@@ -322,6 +369,8 @@ struct Engine3 {
     // the sequence is padded with bubble steps that exist only in the ring (no MFMAs, no barrier): chunk 0 of the next forward is
     // streamed by the last chunks as usual, and what the bubble's place would have streamed (chunk 1 of the next forward, into the
     // slot the last chunk frees) is issued behind the last barrier and waited for at the start of the next forward.
+    // FRESH_BUBBLE (the rollout kernel's step loop, 256-episode shape): see the bubble's streams below.
+    template <bool FRESH_BUBBLE = false>
     __device__ __forceinline__ void forward(const int (&rowoff)[NC], float (&lg)[4], float &value)
     {
         f32x16 acc[NT];
@@ -370,10 +419,23 @@ struct Engine3 {
         }
         if (V != n_chunks) {        // the bubble's streams: chunk 0 (only if no chunk streamed it) and chunk 1 of the next forward
             const int c1 = n_chunks > 1 ? 1 : 0;
+            if constexpr (FRESH_BUBBLE) {
+                // the ops' addresses from opaque copies of the four bases, which the chunk loop holds in scalar registers anyway.  Left
+                // to itself hipcc computes every op's source and destination once per kernel -- three scalars per op that then live
+                // across the caller's whole step loop in spilled registers, fetched back here with a v_readlane_b32 each.
+                Engine3 fresh = *this;
+                asm volatile("" : "+s"(fresh.dsrc_w), "+s"(fresh.dsrc_t), "+s"(fresh.ddst_w), "+s"(fresh.ddst_t));
 #pragma unroll
-            for (int op = 0; op < NOPS; ++op) {
-                if (V - 2 >= n_chunks) stream_op(0, 0, op);
-                stream_op(c1, 1, op);
+                for (int op = 0; op < NOPS; ++op) {
+                    if (V - 2 >= n_chunks) fresh.stream_op(0, 0, op);
+                    fresh.stream_op(c1, 1, op);
+                }
+            } else {
+#pragma unroll
+                for (int op = 0; op < NOPS; ++op) {
+                    if (V - 2 >= n_chunks) stream_op(0, 0, op);
+                    stream_op(c1, 1, op);
+                }
             }
         }
 

@@ -187,8 +187,30 @@ TW_STAMP_ARRAY(g_gen_stamps, 8);   // cycle stamps of the generic engine and the
 // Gumbel arg-max, the record, is_final / step, and in persistent mode the next episode off the queue.  `on`: this lane takes the
 // step (the forwarded step: every lane; a round: the lanes that hit).
 // entries of RolloutArgs::init_boards: the drain launch of a hand-over (the <NT, NC, -4, true> shape) reads the count the first launch left
+// The launch arguments as they sit in the kernarg segment, through a pointer the compiler cannot see through.  The 256-episode shape
+// reads every launch constant of the step's tail, of the rounds and of the loop top through such a view taken where it is needed:
+// a constant read from the by-value argument is loaded once in front of the loop and then lives across the forward, which has no
+// scalar register to spare -- it was parked in a lane of a spill VGPR and fetched back with a v_readlane_b32 (vector-ALU time: the
+// f32 MFMA hides none of it) at every use.  A scalar load behind the forward costs the vector ALU nothing.
+typedef const __attribute__((address_space(4))) RolloutArgs KernArgs;
+__device__ __forceinline__ KernArgs &kernarg_view()
+{
+    KernArgs *p = (KernArgs *)__builtin_amdgcn_kernarg_segment_ptr();   // (the kernel's one by-value argument: offset 0)
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+template <class Args>
+__device__ __forceinline__ PuzzleConsts env_of(Args &a)
+{
+    PuzzleConsts e;
+    e.width = a.env.width; e.height = a.env.height; e.n_cells = a.env.n_cells; e.difficulty = a.env.difficulty;
+    e.depth0 = a.env.depth0; e.r_step = a.env.r_step; e.ident = a.env.ident;
+    return e;
+}
+
 // Policy::get_perm_id of step t of an episode (policy.rs:67-77); n_perms > 0
-__device__ __forceinline__ int draw_twist(const RolloutArgs &a, int n_perms, uint32_t e_local, int t)
+template <class Args>
+__device__ __forceinline__ int draw_twist(Args &a, int n_perms, uint32_t e_local, int t)
 {
     const u32x4 w = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_PERM);
     return (int)u32_below(w.x, (uint32_t)n_perms);
@@ -226,8 +248,8 @@ __device__ __forceinline__ void ring_put(unsigned *ring, int t, uint64_t board, 
     reinterpret_cast<uint8_t *>(ring + RING_SLOTS * RING_DW * RING_EPS)[t & (RING_SLOTS - 1)] = (uint8_t)(perm & 0xff);
 }
 
-template <int NW>
-__device__ __forceinline__ uint64_t queue_entries(const RolloutArgs &a)
+template <int NW, class Args>
+__device__ __forceinline__ uint64_t queue_entries(Args &a)
 {
     if constexpr (NW == -4) { if (a.num_episodes_dev) return (uint64_t)*a.num_episodes_dev; }
     return a.num_episodes;
@@ -236,8 +258,8 @@ __device__ __forceinline__ uint64_t queue_entries(const RolloutArgs &a)
 // 256-episode shape (NW == 8): `perm` comes in as the twist of this step and goes out as the twist of the lane's pending step
 // (PERM_UNDRAWN where that is the first step of a new episode), and
 // the step's (board, twist) -> (logits, value) goes into the look-back ring (`ring`: the lane's view of it, below).
-template <int NW, bool PERSIST, bool RAW, class Eng>
-__device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleConsts &env, const Eng &eng, bool writer, bool on, int &perm, float (&lg)[4], float value,
+template <int NW, bool PERSIST, bool RAW, class Eng, class Args>
+__device__ __forceinline__ void step_tail(Args &a, const PuzzleConsts &env, const Eng &eng, bool writer, bool on, int &perm, float (&lg)[4], float value,
                                           uint32_t &e_local, uint64_t &board, int &depth, int &t, bool &alive, bool &more, unsigned *wg_words = nullptr, unsigned *ring = nullptr)
 {
     const int j = eng.j, h = eng.h;
@@ -261,7 +283,8 @@ __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleCons
         const auto s0 = __builtin_amdgcn_permlane32_swap(w.x, w.z, false, false);
         const auto s1 = __builtin_amdgcn_permlane32_swap(w.y, w.w, false, false);
         action = gumbel_argmax4_words(lg, s0[0], s1[0], h != 0);
-        if (eng.pol.n_perms > 0) perm_next = (int)u32_below(h ? w.x : s0[1], (uint32_t)eng.pol.n_perms);
+        const int n_perms = a.pol.n_perms;
+        if (n_perms > 0) perm_next = (int)u32_below(h ? w.x : s0[1], (uint32_t)n_perms);
     } else {
         const u32x4 gw = rng_draw(a.seed, a.episode_offset + (uint64_t)e_local, (uint32_t)t, STREAM_GUMBEL);
         action = gumbel_argmax4(lg, gw);
@@ -304,7 +327,7 @@ __device__ __forceinline__ void step_tail(const RolloutArgs &a, const PuzzleCons
             }
         }
         // a lane that took a new episode: its pending step is not (episode, t + 1) -- the loop top draws that twist
-        if constexpr (NW == 8) perm = want && alive && eng.pol.n_perms > 0 ? PERM_UNDRAWN : perm;
+        if constexpr (NW == 8) perm = want && alive && a.pol.n_perms > 0 ? PERM_UNDRAWN : perm;
     }
 }
 
@@ -413,13 +436,21 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
     // the queue is dry and no more than drain_live are left the workgroup hands them over instead of running 256-column forwards
     // for a handful of columns (RolloutArgs::resume; the flag was stored before this barrier, and the next store to it lies behind
     // the forward's barriers).  Exit plus stream order: nothing waits.
+    // (256-episode shape: the launch constants inside the loop come through kernarg_view(), taken anew on either side of the forward)
+    auto args = [&]() -> decltype(auto) { if constexpr (NW == 8) return kernarg_view(); else return (a); };
+    auto env_at = [&](auto &v) -> decltype(auto) { if constexpr (NW == 8) return env_of(v); else return (env); };
     auto go_on = [&]() -> bool {
         if constexpr (NW == 8 && PERSIST) {
             const unsigned live = (unsigned)__syncthreads_count(alive && writer ? 1 : 0);
             TW_DRAIN_ANATOMY_STEP(reuse_cnt, live, blockIdx.x);
             if (live == 0u) return false;
-            if (live > a.drain_live || !*(volatile unsigned *)(reuse_cnt + 1)) return true;
-            if (alive && writer) a.resume[atomicAdd(a.resume_cnt, 1u)] = make_uint4((uint32_t)board, (uint32_t)(board >> 32), e_local, (uint32_t)t);
+            // (every lane reads the same word: the first lane's copy makes the test a scalar one and this exit of the loop wave-uniform --
+            //  as a vector compare it sent the exit through a divergent region whose lane masks then lived across the forward)
+            if (live > args().drain_live || !__builtin_amdgcn_readfirstlane(*(volatile unsigned *)(reuse_cnt + 1))) return true;
+            if (alive && writer) {
+                auto &ha = args();
+                ha.resume[atomicAdd(ha.resume_cnt, 1u)] = make_uint4((uint32_t)board, (uint32_t)(board >> 32), e_local, (uint32_t)t);
+            }
             return false;
         } else return __syncthreads_or(alive ? 1 : 0) != 0;
     };
@@ -428,13 +459,14 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
         TW_STAMP_COUNT(n_fwd, 1);
         TW_STEP_STAMP(sq0);
         // ---- observe (puzzle.rs:183-185) + twist of the obs ids (policy.rs:67-83) -------------
+        auto &la = args();
         if constexpr (NW == 8) {
             // step_tail left the twist of the pending step with the step before it; only a lane whose pending step is an episode's
             // first one has none yet (persistent lanes: the first iteration, a lane that took an episode off the queue; the plain
             // launch drew it in front of the loop): one more pass, wave-uniform
             if constexpr (PERSIST) {
                 if (__builtin_amdgcn_ballot_w64(perm == PERM_UNDRAWN) != 0ull) {
-                    const int p = draw_twist(a, eng.pol.n_perms, e_local, t);
+                    const int p = draw_twist(la, la.pol.n_perms, e_local, t);
                     perm = perm == PERM_UNDRAWN ? p : perm;
                 }
             }
@@ -443,22 +475,26 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
             if (eng.pol.n_perms > 0) perm = draw_twist(a, eng.pol.n_perms, e_local, t);
         }
         int rowoff[NC];
-        eng.rows_of(board, env.n_cells, perm, rowoff);
+        if constexpr (NW == 8) eng.rows_of_args(la, board, perm, rowoff);
+        else eng.rows_of(board, env.n_cells, perm, rowoff);
 
         float lg[4]; float value;
-        eng.forward(rowoff, lg, value);
+        if constexpr (NW == 8) eng.template forward<true>(rowoff, lg, value);
+        else eng.forward(rowoff, lg, value);
         TW_STEP_USE(value); TW_STEP_STAMP(sq1); TW_STEP_ADD(s_fwd, sq0, sq1);
 
         // the lane's view of the look-back ring, computed behind the forward (through an opaque copy of the lane's column: an address
         // hoisted out of the loop would be one more register live across the forward)
         unsigned *ring = nullptr;
         if constexpr (NW == 8) { int jj = eng.j; asm volatile("" : "+v"(jj)); ring = reuse_cnt + RING_AT + eng.wave * EPW + jj; }
-        step_tail<NW, PERSIST, true>(a, env, eng, writer, true, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt, ring);
+        auto &ta = args();
+        const PuzzleConsts &tenv = env_at(ta);
+        step_tail<NW, PERSIST, true>(ta, tenv, eng, writer, true, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt, ring);
         TW_STEP_USE(t); TW_STEP_USE(perm); TW_STEP_STAMP(sq2); TW_STEP_ADD(s_tail, sq1, sq2); TW_STEP_ADD(s_iter, 0, 1);
 
         // ---- fast-forward rounds: a step whose (board, perm) the episode recorded 2k steps ago takes that record's output -----
         if constexpr (NW == 8) {
-            if (!a.reuse_off) {
+            if (!ta.reuse_off) {
                 static_assert(2 * REUSE_LB <= RING_SLOTS, "the look-back ring holds the last RING_SLOTS steps");
                 bool cand = true;                         // a lane that missed stays where it is: it would miss again
 #pragma unroll 1
@@ -484,7 +520,7 @@ __global__ void __launch_bounds__((Geom<NT, NC, NW>::WAVES * 64), ((NW == 8 || N
 #pragma unroll
                     for (int i = 0; i < 4; ++i) lg[i] = __uint_as_float(e[(2 + i) * RING_EPS]);
                     value = __uint_as_float(e[6 * RING_EPS]);
-                    step_tail<NW, PERSIST, false>(a, env, eng, writer, hit, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt, ring);
+                    step_tail<NW, PERSIST, false>(ta, tenv, eng, writer, hit, perm, lg, value, e_local, board, depth, t, alive, more, reuse_cnt, ring);
                 }
                 TW_STEP_USE(t); TW_STEP_STAMP(sq1); TW_STEP_ADD(s_rounds, sq2, sq1);
             }
