@@ -104,6 +104,7 @@ extern "C" {
     // a device environment (a module of twisterl_amd.build.build_device_env: `env` = its descriptor, `proto` = the struct in its current
     // state, not modified): solve() in one kernel launch -- best of prm.num_searches attempts, the played actions of the best one
     // (prm.precision = 1, TW_PREC_F16, without MCTS: on the f16 matrix core when the module was built with TW_DEVICE_ENV_FP16_SOLVE)
+    // (with MCTS, and tw_az_collect_device_env's self-play: when it was built with TW_DEVICE_ENV_FP16_SEARCH)
     #[allow(dead_code)] fn tw_solve_device_env(env: *const c_void, proto: *const c_void, proto_bytes: usize, policy: *const c_void, prm: *const TwSolveParams,
                                                max_steps: u32, success: *mut f32, reward: *mut f32, solution_out: *mut u32, solution_cap: u32,
                                                n_solution: *mut u32) -> c_int;

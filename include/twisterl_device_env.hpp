@@ -77,11 +77,20 @@
 // num_mcts_searches == 0 then run on the device for any generic policy, launched by the descriptor's launch_solve when its arguments
 // carry an image (EnvSolveArgs::image), its occupancy behind groups_per_cu(3, ...) -- the descriptor itself does not grow.  Again
 // everything outside the forward is the f32 kernel's sequence, and nothing is asked of the struct.  A module built with
-// TW_DEVICE_ENV_FP16 alone holds exactly the kernels it held.  The search kernel stays f32: MCTS-guided evaluate and solve in
-// another precision answer "f32 only", as every module without the define does.
+// TW_DEVICE_ENV_FP16 alone holds exactly the kernels it held.
+// `#define TW_DEVICE_ENV_FP16_SEARCH` (build_device_env(..., fp16_search=True); it implies TW_DEVICE_ENV_FP16 and belongs with
+// TW_DEVICE_ENV_SEARCH or TW_DEVICE_ENV_WIDE_SEARCH) adds mcts_env16_kernel, the search loop over EngineV16 and the same image:
+// AZCollector(precision="fp16").collect and collector.evaluate / collector.solve with precision="fp16" and num_mcts_searches > 0 then
+// run on the device, launched by the descriptor's launch_search when its arguments carry an image (EnvMctsArgs::image), its occupancy
+// and the capability query behind groups_per_cu(4, ...).  Everything behind the heads -- the soft-max, the tree, the draws -- is the
+// f32 kernel's text.  Without the define the search kernel is f32 alone: self-play and MCTS-guided evaluate and solve in another
+// precision answer "f32 only".
 #pragma once
 
 #if defined(TW_DEVICE_ENV_FP16_SOLVE) && !defined(TW_DEVICE_ENV_FP16)
+#define TW_DEVICE_ENV_FP16
+#endif
+#if defined(TW_DEVICE_ENV_FP16_SEARCH) && !defined(TW_DEVICE_ENV_FP16)
 #define TW_DEVICE_ENV_FP16
 #endif
 

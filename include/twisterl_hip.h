@@ -121,7 +121,10 @@ enum {
     TW_KERNEL_MCTS_F32 = 1,     /* mcts_f32_kernel<nt, nc, nw, PERSIST>                          */
     TW_KERNEL_SOLVE_F32 = 2,    /* solve_f32_kernel<nt, nc, nw>                                  */
     TW_KERNEL_MCTS_DEEP = 3,    /* mcts_deep_kernel<nt, nc, nw, nwk, SOLVE, DEC, SPL>            */
-    TW_KERNEL_MCTS_BIG = 4,     /* mcts_big_kernel<nc>; nt 1: mcts_env_kernel<Env, nc> of a device-environment module       */
+    TW_KERNEL_MCTS_BIG = 4,     /* mcts_big_kernel<nc>; nt 1: mcts_env_kernel<Env, nc> of a device-environment module (nw 0), or
+                                 * with nw 16 its mcts_env16_kernel<Env, nc>: precision fp16 of self-play and of MCTS-guided
+                                 * evaluate / solve of a module built with TW_DEVICE_ENV_FP16_SEARCH, the pack of the binary16
+                                 * weight image launched in front of it                                                        */
     TW_KERNEL_SOLVE_BIG = 5,    /* solve_big_kernel<nc>; nt 1: solve_env_kernel<Env, nc> of a device-environment module (nw 0), or
                                  * with nw 16 its solve_env16_kernel<Env, nc>: precision fp16 without MCTS of a module built with
                                  * TW_DEVICE_ENV_FP16_SOLVE, the pack of the binary16 weight image launched in front of it    */
@@ -422,8 +425,9 @@ int tw_solve_env32(const tw_env_vtable *env, const tw_policy *policy, const tw_s
  * environment struct (proto_bytes = its size), the prototype every episode clones and resets.  The library refuses a descriptor
  * built against another layout.  tw_ppo_collect_device_env / tw_evaluate_device_env / tw_solve_device_env run the whole loop in one kernel (the policy on
  * EngineV, f32; precision TW_PREC_F16 of a generic policy on EngineV16: the PPO collect of a module built with TW_DEVICE_ENV_FP16,
- * evaluate and solve without MCTS of one built with TW_DEVICE_ENV_FP16_SOLVE); what that kernel does not take -- a policy of the MFMA
- * shape, another precision (MCTS-guided evaluate and solve: any but f32) -- runs on the host-stepped path over
+ * evaluate and solve without MCTS of one built with TW_DEVICE_ENV_FP16_SOLVE, self-play and MCTS-guided evaluate and solve of one
+ * built with TW_DEVICE_ENV_FP16_SEARCH); what that kernel does not take -- a policy of the MFMA
+ * shape, another precision (the search kernel of a module without TW_DEVICE_ENV_FP16_SEARCH: any but f32) -- runs on the host-stepped path over
  * the module's own vtable (tw_ppo_collect_env / tw_az_collect_env / tw_evaluate_env: same bytes, same errors).  Self-play
  * (tw_az_collect_device_env) and evaluate with num_mcts_searches > 0 run in one kernel too when the module was built with
  * TW_DEVICE_ENV_SEARCH (build_device_env(search=True): its descriptor then holds the search kernel's launcher), and on the

@@ -47,6 +47,12 @@ side by side).  evaluate returns two means and no statistics, so a row carries t
 kernel, the copies back, the reduction on the host) as median / min / max of --reps after --warmup, and the two means.  A --tree from
 before the keyword builds the plain module and gives the fp32 rows only: the parent's figures of the same session.
 profiles/r17_device_env_fp16_solve.jsonl.
+
+--az and the MCTS shapes of --solve with --precision fp32,fp16 (and --policy default | deep): each listed precision from ONE module
+built with fp16_search=True (mcts_env_kernel and mcts_env16_kernel side by side; name + _f16), whole calls, median / min / max of --reps,
+rows APPENDED to --out with their "precision".  fp16 has no host-stepped counterpart: the fp16 rows of --solve are device rows only.  A
+--tree from before the flag builds the plain search module and gives the fp32 rows only: the parent's figures of the same session.
+profiles/r20_device_env_fp16_search.jsonl.
 """
 import argparse
 import ctypes as C
@@ -76,31 +82,47 @@ def az(args):
     if args.no_persist:
         _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
     params = inspect.signature(build_device_env).parameters
+    # --precision: every listed precision from one module built with fp16_search=True (a tree from before the flag: the plain search
+    # module, fp32 only)
+    f16 = {"fp16_search": True} if args.precision and "fp16_search" in params else {}
+    precs = [p for p in (args.precision or "fp32").split(",") if p == "fp32" or f16]
+    suffix = "_f16" if f16 else ""
     if args.env == "perm8":
         # 28 actions: the search kernel takes them in a module built with wide_search=True; a tree from before that builds the wide
         # module without the search kernel and its collect is host-stepped
         from tests.util import make_deep_policy_arrays_obs
         can_search = "wide_search" in params
-        name = "perm8_az" if can_search else "perm8"
+        name = ("perm8_az" if can_search else "perm8") + suffix
         so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", name,
-                              **({"wide_search": True} if can_search else {"wide": True}))
+                              **({"wide_search": True} if can_search else {"wide": True}), **f16)
         env = DeviceEnv(so, name, [8, 32, 4], max_records=33)
-        pol = amd_policy(make_deep_policy_arrays_obs(64, seed=0, emb=512, common=(128, 64), n_actions=28))
-        env_name, pol_name = "Permutation8 (28 actions)", "64-512-128-64+heads (generic)"
+        emb, common = {"default": (512, (128, 64)), "small": (128, (64, 64)), "deep": (256, (512, 256))}[args.policy]
+        pol = amd_policy(make_deep_policy_arrays_obs(64, seed=0, emb=emb, common=common, n_actions=28))
+        env_name, pol_name = "Permutation8 (28 actions)", "-".join(str(x) for x in (64, emb) + tuple(common)) + "+heads (generic)"
     elif args.env != "gridworld":
         raise SystemExit("--az: --env gridworld or perm8")
     else:
         can_search = "search" in params
-        name = "gridworld5x5_az" if can_search else "gridworld5x5"
-        so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if can_search else {}))
+        name = ("gridworld5x5_az" if can_search else "gridworld5x5") + suffix
+        so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if can_search else {}), **f16)
         env = DeviceEnv(so, name, [5, 5, 64, 1], max_records=65)
-        pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
-        env_name, pol_name = "GridWorld5x5", "625-512-128+heads (generic)"
+        emb, common = {"default": (512, (128,)), "small": (128, (64,)), "deep": (256, (512, 256))}[args.policy]
+        pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=emb, common=common, n_actions=4))
+        env_name, pol_name = "GridWorld5x5", "-".join(str(x) for x in (625, emb) + tuple(common)) + "+heads (generic)"
     E, S = (int(x) for x in args.az_shape.lower().split("x"))
+    for prec in precs:
+        az_rows(args, env, pol, env_name, pol_name, E, S, prec if args.precision else None)
+
+
+def az_rows(args, env, pol, env_name, pol_name, E, S, prec):
+    """The row of one precision (None: the collector's default, for a tree from before the keyword reached the device)."""
+    import numpy as np
+    import twisterl_amd
+    from twisterl_amd import _lib, twisterl
 
     def collect(seed):
         t0 = time.perf_counter()
-        c = twisterl.collector.AZCollector(E, S, 1.41, 1, 32).collect(env, pol, seed=seed)
+        c = twisterl.collector.AZCollector(E, S, 1.41, 1, 32, **({"precision": prec} if prec else {})).collect(env, pol, seed=seed)
         n = len(c)
         return time.perf_counter() - t0, n, c.stats
 
@@ -115,6 +137,8 @@ def az(args):
     k = int(np.argsort([r[0] for r in runs])[len(runs) // 2])
     t, n, stats = runs[k]
     on_device = _lib.debug_last_launch()["family"] == _lib.TW_KERNEL_MCTS_BIG
+    if prec:
+        assert on_device and _lib.debug_last_launch()["nw"] == (16 if prec == "fp16" else 0), _lib.debug_last_launch()
     evals = int(stats.get("forward_evals", 0)) if on_device else None
     row = {"bench": "az", "env": env_name, "policy": pol_name, "path": "device" if on_device else "host_stepped",
            "episodes": E, "num_mcts_searches": S, "max_expand_depth": 1, "shape_fell_back": fell_back, "records": n,
@@ -124,6 +148,9 @@ def az(args):
            "persist": _lib.debug_last_launch()["persist"] if on_device else None, "blocks": _lib.debug_last_launch()["blocks"] if on_device else None,
            "wall_ms_all": [round(r[0] * 1e3, 3) for r in runs],
            "reps": args.reps, "device": twisterl_amd.device_info()["name"]}
+    if prec:
+        row.update(precision=prec, wall_ms_min=round(min(r[0] for r in runs) * 1e3, 3), wall_ms_max=round(max(r[0] for r in runs) * 1e3, 3),
+                   tree=os.path.basename(ROOT) if args.tree else "this")
     print(json.dumps(row), flush=True)
     if args.out:
         with open(args.out, "a") as f:
@@ -151,14 +178,18 @@ def solve(args):
     grid_pol = amd_policy(make_deep_policy_arrays(25, seed=0, emb=512, common=(128,), n_actions=4))
     perm_pol = amd_policy(make_deep_policy_arrays_obs(64, seed=0, emb=512, common=(128, 64), n_actions=28))
 
+    # --precision: the MCTS shapes in every listed precision from one module built with fp16_search=True
+    f16 = {"fp16_search": True} if args.precision and "fp16_search" in params else {}
+    precs = [p for p in (args.precision or "fp32").split(",") if p == "fp32" or f16]
+
     def grid(search):
-        name = "gridworld5x5_az" if search else "gridworld5x5"
-        so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True} if search else {}))
+        name = ("gridworld5x5_az" + ("_f16" if f16 else "")) if search else "gridworld5x5"
+        so = build_device_env(GRIDWORLD_HPP, "tw_examples::GridWorld5x5", name, **({"search": True, **f16} if search else {}))
         return DeviceEnv(so, name, [5, 5, 64, 8], max_records=65)
 
     def perm(search):
-        name = "perm8_az" if search else "perm8"
-        so = build_device_env(perm_hpp, "tw_examples::Permutation8", name, **({"wide_search": True} if search else {"wide": True}))
+        name = ("perm8_az" + ("_f16" if f16 else "")) if search else "perm8"
+        so = build_device_env(perm_hpp, "tw_examples::Permutation8", name, **({"wide_search": True, **f16} if search else {"wide": True}))
         return DeviceEnv(so, name, [8, 32, 4], max_records=33)
 
     S = args.solve_mcts
@@ -176,8 +207,8 @@ def solve(args):
         vt = _lib.EnvVTable()
         _lib.check(_lib.lib().tw_device_env_host_vtable(*env._args(), C.byref(vt)))
 
-        def call(N, seed):
-            return twisterl.collector.solve(env, pol, False, N, mcts, 1.41, 1, seed=seed)
+        def call(N, seed, prec=None):
+            return twisterl.collector.solve(env, pol, False, N, mcts, 1.41, 1, seed=seed, **({"precision": prec} if prec else {}))
 
         def host(N, seed):
             prm = _lib.SolveParams(0, N, mcts, 1.41, 1, seed, _lib.TW_PREC_F32_EXACT)
@@ -207,6 +238,30 @@ def solve(args):
                        "wall_ms": round(ts_ms[len(ts_ms) // 2], 3), "wall_ms_min": round(ts_ms[0], 3), "wall_ms_max": round(ts_ms[-1], 3),
                        "wall_ms_all": [round(t * 1e3, 3) for t in ts], "reps": args.reps,
                        "persist": last["persist"] if fn is call and on_device else None, "blocks": last["blocks"] if fn is call and on_device else None,
+                       "tree": os.path.basename(ROOT) if args.tree else "this", "device": info["name"]}
+                if args.precision:
+                    row.update(precision="fp32")
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(json.dumps(row) + "\n")
+            if mcts and "fp16" in precs:
+                # the f16 search kernel of the same module: device rows only (the host-stepped path is f32)
+                for i in range(args.warmup):
+                    call(N, 100 + i, "fp16")
+                ts = []
+                for i in range(args.reps):
+                    t0 = time.perf_counter()
+                    call(N, 1000 + i, "fp16")
+                    ts.append(time.perf_counter() - t0)
+                last = _lib.debug_last_launch()
+                assert (last["family"], last["nw"]) == (_lib.TW_KERNEL_MCTS_BIG, 16), last
+                ts_ms = sorted(t * 1e3 for t in ts)
+                row = {"bench": "solve", "env": env_name, "policy": pol_name, "path": "device", "entry": "collector.solve", "precision": "fp16",
+                       "num_searches": N, "num_mcts_searches": mcts, "max_expand_depth": 1, "deterministic": False, "same_result_as_host_stepped": None,
+                       "wall_ms": round(ts_ms[len(ts_ms) // 2], 3), "wall_ms_min": round(ts_ms[0], 3), "wall_ms_max": round(ts_ms[-1], 3),
+                       "wall_ms_all": [round(t * 1e3, 3) for t in ts], "reps": args.reps, "persist": last["persist"], "blocks": last["blocks"],
                        "tree": os.path.basename(ROOT) if args.tree else "this", "device": info["name"]}
                 rows.append(row)
                 print(json.dumps(row), flush=True)

@@ -596,7 +596,7 @@ def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches
     -> ((success, reward), actions)   (python_interface/env.rs:180-191 over rl/solve.rs:73-101).
     Best of `num_searches` greedy/sampled roll-outs from the env's CURRENT state; the env is not modified.
     `precision` (keyword-only; "fp32" exact | "fp16" | "fp16x2") goes to the library as it is: a DeviceEnv built with fp16_solve=True
-    runs "fp16" without MCTS on the f16 matrix core; what an environment does not take in that precision answers with the
+    runs "fp16" without MCTS on the f16 matrix core, one built with fp16_search=True "fp16" with MCTS; what an environment does not take in that precision answers with the
     library's own message ("... f32 only ...")."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")

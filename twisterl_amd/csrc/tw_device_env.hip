@@ -10,7 +10,8 @@
 // the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error; but a PPO
 // collect with precision fp16 of a module built with TW_DEVICE_ENV_FP16 runs in rollout_env16_kernel over EngineV16, its binary16
 // weight image packed into the collect's workspace by the module's launcher in front of every rollout, and evaluate / solve without
-// MCTS of a module built with TW_DEVICE_ENV_FP16_SOLVE run likewise in solve_env16_kernel), and -- for
+// MCTS of a module built with TW_DEVICE_ENV_FP16_SOLVE run likewise in solve_env16_kernel, self-play and evaluate / solve WITH MCTS of
+// one built with TW_DEVICE_ENV_FP16_SEARCH in mcts_env16_kernel), and -- for
 // a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has no search launcher -- self-play,
 // evaluate and solve with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
 // 1..4 actions and (TW_DEVICE_ENV_WIDE_SEARCH) for 5..31, which lives in the module
@@ -190,6 +191,34 @@ int search_launch_refused(const char *who)
     return TW_ERR_INVALID;
 }
 
+// What EngineV16 takes of a policy: a generic stack with both heads, at most GEN16_MAX_LAYERS layers (the fp16 collect's own rule)
+bool engine16_takes(const PolicyDev *pd)
+{
+    return pd->generic && pd->n_action >= 1 && pd->n_value >= 1 && pd->n_common + pd->n_action + pd->n_value <= GEN16_MAX_LAYERS;
+}
+
+// index of mcts_env16_kernel for tw_device_env::groups_per_cu (a module built with TW_DEVICE_ENV_FP16_SEARCH)
+constexpr int ENV_KERNEL_SEARCH16 = 4;
+
+// precision="fp16" of self-play and of MCTS-guided evaluate / solve: mcts_env16_kernel over EngineV16, when the module holds it (the
+// capability query: kernel 4 with a null result, answered without the HIP runtime) and EngineV16 takes the policy
+bool search_f16(const tw_device_env *env, const PolicyDev *pd, uint32_t precision)
+{
+    return precision == TW_PREC_F16 && env->launch_search && engine16_takes(pd) && env->groups_per_cu(ENV_KERNEL_SEARCH16, 0, nullptr) == (int)hipSuccess;
+}
+
+// the size of the f16 weight image of a generic policy: the layout function the pack kernel and the engine index with
+// (tw_engine_generic16.hpp) over the layer table's widths, which live on the device and are read on the call's stream `s`
+int gen16_image_size(const PolicyDev *pd, hipStream_t s, size_t *halves)
+{
+    const int n_layers = pd->n_common + pd->n_action + pd->n_value;
+    std::vector<LayerDev> layers((size_t)n_layers);
+    TW_HIP(hipMemcpyAsync(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost, s));
+    TW_HIP(hipStreamSynchronize(s));
+    *halves = gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
+    return TW_OK;
+}
+
 }  // namespace
 
 int tw::launch_compact_obs8(const uint16_t *obs16, const uint32_t *ep_len, const uint64_t *ep_start, uint64_t E, int t_pad, int n_obs,
@@ -359,7 +388,10 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     const tw_env_vtable vt = host_table(env, proto);
     const PolicyDev *pd = policy_dev(policy);
     uint64_t node_cap = 0;
-    if (!env->launch_search || !pd->generic || prm->precision != TW_PREC_F32_EXACT || max_records_per_episode > FINALIZE_AZ_MAX_T_PAD ||
+    // precision="fp16": mcts_env16_kernel, when the module holds it and EngineV16 takes the policy (search_f16); any other precision but
+    // f32, and fp16 without that, are the host-stepped path's to refuse
+    const bool f16 = search_f16(env, pd, prm->precision);
+    if (!env->launch_search || !pd->generic || (prm->precision != TW_PREC_F32_EXACT && !f16) || max_records_per_episode > FINALIZE_AZ_MAX_T_PAD ||
         !search_fits(env->num_actions, prm->num_mcts_searches, prm->max_expand_depth, max_records_per_episode, &node_cap))
         return tw_az_collect_env(&vt, policy, prm, max_records_per_episode, out);
     if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
@@ -372,7 +404,7 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     const bool ragged = vt.observe_n != nullptr;
     const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
-    const size_t lds_bytes = engine_lds_bytes(env->engine_nc, *pd);
+    const size_t lds_bytes = f16 ? engine16_lds_bytes(env->engine_nc, *pd) : engine_lds_bytes(env->engine_nc, *pd);
     const size_t search_lds = env_mcts_pending_bytes(env->n_obs) + env_mcts_probs_bytes(env->num_actions);      // what the launcher adds
     if (lds_bytes + search_lds > 159 * 1024) {
         set_error("mcts: %zu bytes of LDS needed, 159 KiB available", lds_bytes + search_lds); return TW_ERR_UNSUPPORTED;
@@ -382,11 +414,17 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
 
     std::lock_guard<std::mutex> lock(workspace_mutex());
     hipStream_t s = current_stream();
+    size_t image_halves = 0;                                              // fp16: the image's size, as the PPO collect reads it
+    if (f16) { rc = gen16_image_size(pd, s, &image_halves); if (rc) return rc; }
     size_t cur = 0;
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
     const size_t o_rec = seg(R * sizeof(PaddedRec)), o_len = seg(E * 4), o_start = seg(E * 8), o_total = seg(32), o_scan = seg(scan_scratch_bytes(E)),
                  o_obs16 = seg(R * NO * 2), o_ce = seg(E * 16), o_arena = seg((size_t)E * node_cap * ENV_MCTS_NODE_BYTES),
                  o_pw = seg(A > 4 ? R * A * sizeof(float) : 0);           // more than four actions: the MCTS probabilities, [E][t_pad][A]
+    // fp16: the binary16 weight image behind everything else, so that no f32 offset moves (f32: no bytes).  Every half of it is written
+    // by pack_generic16_kernel before mcts_env16_kernel reads it (tests/test_gpu_device_env_fp16_search.py runs on pre-filled memory)
+    const size_t o_img = cur;
+    cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
     rc = check_memory_fit(cur, "tw_az_collect_device_env"); if (rc) return rc;
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
@@ -402,6 +440,7 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     ma.num_searches = prm->num_mcts_searches; ma.max_expand_depth = prm->max_expand_depth; ma.C = prm->C; ma.node_cap = (uint32_t)node_cap;
     ma.arena = ws + o_arena;
     if (A > 4) ma.pw = reinterpret_cast<float *>(ws + o_pw);
+    if (f16) { ma.image.img = reinterpret_cast<_Float16 *>(ws + o_img); ma.image.halves = image_halves; }   // the launcher packs it, then mcts_env16_kernel
     uint64_t *ep_start_ws = reinterpret_cast<uint64_t *>(ws + o_start), *total_d = reinterpret_cast<uint64_t *>(ws + o_total);
 
     EventSet ev; rc = ev.init(); if (rc) return rc;
@@ -411,7 +450,8 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
     if (lr == (int)hipErrorInvalidValue) return search_launch_refused("tw_az_collect_device_env");
     if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
-    note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, false, false, false, (uint32_t)blocks, 256);
+    // (tw_debug_last_launch: nw = 16 marks the f16 kernel, 0 the f32 one -- include/twisterl_hip.h)
+    note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, f16 ? 16 : 0, 0, false, false, false, false, (uint32_t)blocks, 256);
     TW_HIP(hipEventRecord(ev.ev[1], s));
     rc = launch_scan(ma.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;
@@ -451,11 +491,11 @@ constexpr int ENV_KERNEL_SOLVE16 = 3;
 
 // precision="fp16" of evaluate / solve: solve_env16_kernel over EngineV16, when the module holds it (the capability query: kernel 3
 // with a null result, answered without the HIP runtime), the policy is a generic stack with both heads (at most GEN16_MAX_LAYERS
-// layers: the collect's own rule) and no MCTS is asked for (the search kernel is f32 only)
+// layers: the collect's own rule).  With MCTS the kernel is mcts_env16_kernel instead, under the same rule: search_f16
 bool attempts_f16(const tw_device_env *env, const PolicyDev *pd, const tw_solve_params *prm)
 {
-    return prm->precision == TW_PREC_F16 && prm->num_mcts_searches == 0 && pd->generic && pd->n_action >= 1 && pd->n_value >= 1 &&
-           pd->n_common + pd->n_action + pd->n_value <= GEN16_MAX_LAYERS && env->groups_per_cu(ENV_KERNEL_SOLVE16, 0, nullptr) == (int)hipSuccess;
+    if (prm->num_mcts_searches != 0) return search_f16(env, pd, prm->precision);
+    return prm->precision == TW_PREC_F16 && engine16_takes(pd) && env->groups_per_cu(ENV_KERNEL_SOLVE16, 0, nullptr) == (int)hipSuccess;
 }
 
 // What solve_env_kernel / solve_env16_kernel / mcts_env_kernel take of an evaluate or a solve; everything else is the host-stepped path's (the callers
@@ -479,7 +519,7 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
                         uint64_t node_cap, std::vector<float> &best_s, std::vector<float> &best_r, std::vector<uint32_t> *best_actions)
 {
     const bool mcts = prm->num_mcts_searches != 0;
-    const bool f16 = prm->precision == TW_PREC_F16;                       // (attempts_on_device: then attempts_f16 holds, and mcts is false)
+    const bool f16 = prm->precision == TW_PREC_F16;                       // (attempts_on_device: then attempts_f16 holds; with mcts: search_f16)
     const uint32_t max_steps = max_steps_in ? max_steps_in : 1u;
     int rc = check_env_policy(vt, pd); if (rc) return rc;
     if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("%s: policy without its two-byte twist table", who); return TW_ERR_INVALID; }
@@ -539,11 +579,12 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
         ma.solve_on = 1u; ma.deterministic = prm->deterministic ? 1u : 0u; ma.attempts = (uint32_t)N; ma.max_steps = max_steps;
         ma.success = reinterpret_cast<float *>(ws + o_s); ma.total = reinterpret_cast<float *>(ws + o_t); ma.n_steps = reinterpret_cast<uint32_t *>(ws + o_n);
         ma.from_state = from_state ? 1u : 0u; ma.actions = act_d; ma.actions_stride = stride;
+        if (f16) { ma.image.img = reinterpret_cast<_Float16 *>(ws + o_img); ma.image.halves = image_halves; }   // the launcher packs it, then mcts_env16_kernel
         TW_HIP(hipMemsetAsync(ws + o_ce, 0, NA * 16, s));
         const int lr = env->launch_search(&ma, proto, (unsigned)blocks, lds_bytes, s);
         if (lr == (int)hipErrorInvalidValue) return search_launch_refused(who);
         if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment search launch", __FILE__, __LINE__);
-        note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, 0, 0, false, true, false, false, (uint32_t)blocks, 256);
+        note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, f16 ? 16 : 0, 0, false, true, false, false, (uint32_t)blocks, 256);
     } else {
         EnvSolveArgs sa{};
         sa.pol = *pd; sa.num_attempts = NA; sa.episode_offset = episode_offset; sa.seed = prm->seed;

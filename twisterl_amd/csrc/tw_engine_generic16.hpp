@@ -117,6 +117,8 @@ struct EngineV16 {
         const size_t heads = (size_t)(head_rows(p.value_out) + head_rows(p.n_actions)) * GEN_STRIDE * sizeof(float);
         return act + heads + (GEN_COLS * 8 + 256 + GEN_COLS * NC + GEN16_MAX_LAYERS) * 4 + 512;
     }
+    // the same in floats, as EngineV::lds_floats: where a kernel's own LDS starts behind the engine's (every term above is a multiple of 4 bytes)
+    __host__ __device__ static size_t lds_floats(const PolicyDev &p) { return lds_bytes(p) / sizeof(float); }
     __device__ __forceinline__ bool primary() const { return wave == 0; }
     __device__ __forceinline__ int  ep_lane() const { return j; }
     __device__ __forceinline__ bool owns_lane() const { return wave == j / (EPB / NS); }

@@ -12,7 +12,8 @@
 // A module built with TW_DEVICE_ENV_FP16 also holds rollout_env16_kernel<Env, NC>: the rollout's loop over EngineV16
 // (tw_engine_generic16.hpp), PPOCollector(precision="fp16"), within the a-priori bound of the f16-input spec instead of bit-equal.
 // A module built with TW_DEVICE_ENV_FP16_SOLVE holds solve_env16_kernel<Env, NC> as well: evaluate's loop over EngineV16,
-// collector.evaluate / collector.solve with precision="fp16" and no MCTS.
+// collector.evaluate / collector.solve with precision="fp16" and no MCTS.  One built with TW_DEVICE_ENV_FP16_SEARCH beside a search form
+// holds mcts_env16_kernel<Env, NC> (tw_mcts_env.hpp): self-play and MCTS-guided evaluate / solve with precision="fp16".
 //
 // In this file: the argument structs and the descriptor; what the steps call (the Gumbel arg-max, the twist of the actions, the
 // streaming steps of 5 .. 31 actions, env_rows / env_rows_n); the four kernels; their launchers and occupancy queries.  The two step
@@ -96,6 +97,9 @@ struct EnvMctsArgs {
                                      // addressed like obs16 (the record's four logit slots are then zero and nobody reads them); else null
     uint32_t   from_state, actions_stride;   // solve mode, as EnvSolveArgs: no reset of the prototype; the row stride of `actions`
     uint8_t   *actions;              // solve mode: null, or [columns][actions_stride] the moves a column played
+    Gen16Image image;                // img null: mcts_env_kernel, f32.  Else precision="fp16": mcts_env16_kernel over EngineV16 (a module
+                                     // built with TW_DEVICE_ENV_FP16_SEARCH), the image carved from the call's workspace and packed by the
+                                     // launcher before the kernel; the f32 kernel never reads this member
 };
 constexpr int ENV_MCTS_NODE_BYTES = 32;
 // the most nodes one move's tree can hold: the root, its children, and per search at most max(max_expand_depth, 1) expansions
@@ -143,7 +147,12 @@ struct tw_device_env {
     // any other module: hipErrorInvalidValue.  Kernel 3 with out == nullptr only asks whether the module holds that kernel: hipSuccess
     // without a call into the HIP runtime (no device needed), which is how the library and DeviceEnv.fp16_solve learn it -- the
     // descriptor has no member for it.  launch_solve runs that kernel, the pack of the image in front of it, when EnvSolveArgs::image.img
-    // is not null (a module without the kernel, or a policy EngineV16 does not take: hipErrorInvalidValue)
+    // is not null (a module without the kernel, or a policy EngineV16 does not take: hipErrorInvalidValue).
+    // Kernel 4: mcts_env16_kernel of a module built with TW_DEVICE_ENV_FP16_SEARCH beside a search form (lds_bytes = the f16 engine's
+    // share, EngineV16<engine_nc>::lds_bytes(pol); the pending ids and the rows of probabilities are added as for kernel 2); any other
+    // module: hipErrorInvalidValue.  Kernel 4 with out == nullptr is that kernel's capability query, as kernel 3's (the library's
+    // search_f16(), DeviceEnv.fp16_search).  launch_search runs that kernel, the pack of the image in front of it, when
+    // EnvMctsArgs::image.img is not null
     int (*groups_per_cu)(int kernel, size_t lds_bytes, int *out);
     // null unless the module was built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)): pack_generic16_kernel (the policy's
     // f32 device copies -> the binary16 image a->image, on stream s) and then rollout_env16_kernel, with launch_rollout's return
