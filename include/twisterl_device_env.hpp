@@ -85,12 +85,24 @@
 // and the capability query behind groups_per_cu(4, ...).  Everything behind the heads -- the soft-max, the tree, the draws -- is the
 // f32 kernel's text.  Without the define the search kernel is f32 alone: self-play and MCTS-guided evaluate and solve in another
 // precision answer "f32 only".
+// Split precision: `#define TW_DEVICE_ENV_FP16X2` (build_device_env(..., fp16x2=True); it implies TW_DEVICE_ENV_FP16) adds
+// rollout_env16x2_kernel -- the same step loop over EngineV16x2 (twisterl_amd/csrc/tw_engine_generic16x2.hpp: every Linear operand
+// split into two binary16 terms, three products per k-group on v_mfma_f32_16x16x32_f16, DESIGN.md §2 "Forward, split-f16 mode, generic
+// stacks") -- and the kernel that packs its two-plane weight image at the start of every collect:
+// PPOCollector(precision="fp16x2").collect then runs on the device for any generic policy, f32 answers within the split mode's
+// a-priori bound.  The descriptor does not grow: the request travels to launch_rollout16 as bit 63 of EnvRollout16Args::image.halves,
+// the kernel's occupancy and the capability query are behind groups_per_cu(5, ...).  A weight or an activation of 4095 or more has no
+// finite pair of terms; the kernels flag it and the library returns the f32 kernel's collect instead.  evaluate, solve and the search
+// kernel in this precision answer "f32 only".  Without the define a module holds exactly the kernels it held.
 #pragma once
 
 #if defined(TW_DEVICE_ENV_FP16_SOLVE) && !defined(TW_DEVICE_ENV_FP16)
 #define TW_DEVICE_ENV_FP16
 #endif
 #if defined(TW_DEVICE_ENV_FP16_SEARCH) && !defined(TW_DEVICE_ENV_FP16)
+#define TW_DEVICE_ENV_FP16
+#endif
+#if defined(TW_DEVICE_ENV_FP16X2) && !defined(TW_DEVICE_ENV_FP16)
 #define TW_DEVICE_ENV_FP16
 #endif
 

@@ -130,7 +130,10 @@ enum {
                                  * TW_DEVICE_ENV_FP16_SOLVE, the pack of the binary16 weight image launched in front of it    */
     TW_KERNEL_ROLLOUT_BIG = 6,  /* rollout_big_kernel<nc>; nt 1: rollout_env_kernel<Env, nc> of a device-environment module (nw 0), or
                                  * with nw 16 its rollout_env16_kernel<Env, nc>: precision fp16 of a module built with
-                                 * TW_DEVICE_ENV_FP16, the pack of the binary16 weight image launched in front of it          */
+                                 * TW_DEVICE_ENV_FP16, the pack of the binary16 weight image launched in front of it; with nw 32
+                                 * its rollout_env16x2_kernel<Env, nc>: precision fp16x2 of a module built with
+                                 * TW_DEVICE_ENV_FP16X2, the pack of the two-plane split image launched in front of it (a collect
+                                 * that left the split terms' range ran again in f32 and reports nw 0)                        */
     TW_KERNEL_ONEHOT = 7        /* nt 4: onehot4_kernel<8>, 1: onehot_kernel, 0: memset + onehot_scatter_kernel, 2: the same on
                                  * two-byte ids (0xFFFF = no id, skipped); nc: the rows a workgroup writes per trip of its loop
                                  * (32, 4; 0: one id per thread, no loop)                                                      */

@@ -39,7 +39,9 @@ rows only).  --policy small: embedding 128, common [64] (perm8: [64, 64] -- with
 policy has the MFMA shape, which device environments hand to the host-stepped path); --policy deep: embedding 256, common [512, 256].
 Every row carries the rollout's milliseconds (the events around the launch: in fp16 the pack of the weight image and the rollout)
 as median / min / max of --reps, and records per second of rollout time.  Rows are APPENDED to --out.
-profiles/r16_device_env_fp16.jsonl.
+profiles/r16_device_env_fp16.jsonl.  With fp16x2 in the list (--precision fp32,fp16,fp16x2) the module is built with fp16x2=True
+instead and holds rollout_env16x2_kernel as well (EngineV16x2: split binary16 operands, f32 answers); a --tree from before that flag
+builds the fp16 module and gives the other rows.  profiles/r21_device_env_fp16x2.jsonl.
 
 --evaluate (with --precision, --policy, --env gridworld or perm8 as above): collector.evaluate of --episodes episodes x 1 search,
 deterministic and sampled, in each listed precision from ONE module built with fp16_solve=True (solve_env_kernel and solve_env16_kernel
@@ -284,15 +286,20 @@ def precisions(args):
         _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
     # (--tree of a checkout from before the fp16 form: the plain module, fp32 rows only -- the parent's figure of the same run)
     import inspect
-    fp16 = {"fp16": True} if "fp16" in inspect.signature(build_device_env).parameters else {}
+    params = inspect.signature(build_device_env).parameters
+    fp16 = {"fp16": True} if "fp16" in params else {}
+    split = "fp16x2" in args.precision.split(",") and "fp16x2" in params        # the split kernel beside the other two, in one module
+    if split:
+        fp16 = {"fp16x2": True}
+    suffix = "_fp16x2" if split else "_fp16"
     if args.env == "perm8":
-        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", "perm8_fp16", wide=True, **fp16)
-        env = DeviceEnv(so, "perm8_fp16", [8, 32, 4], max_records=33)
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", "perm8" + suffix, wide=True, **fp16)
+        env = DeviceEnv(so, "perm8" + suffix, [8, 32, 4], max_records=33)
         env_name, obs_size, A = "Permutation8 (28 actions)", 64, 28
         emb, common = {"default": (512, (128, 64)), "small": (128, (64, 64)), "deep": (256, (512, 256))}[args.policy]
     elif args.env == "gridworld":
-        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "gridworld.hpp"), "tw_examples::GridWorld5x5", "gridworld5x5_fp16", **fp16)
-        env = DeviceEnv(so, "gridworld5x5_fp16", [5, 5, 64, 1], max_records=65)
+        so = build_device_env(os.path.join(ROOT, "examples", "device_env", "gridworld.hpp"), "tw_examples::GridWorld5x5", "gridworld5x5" + suffix, **fp16)
+        env = DeviceEnv(so, "gridworld5x5" + suffix, [5, 5, 64, 1], max_records=65)
         env_name, obs_size, A = "GridWorld5x5", 625, 4
         emb, common = {"default": (512, (128,)), "small": (128, (64,)), "deep": (256, (512, 256))}[args.policy]
     else:
@@ -302,7 +309,7 @@ def precisions(args):
     info = twisterl_amd.device_info()
     for E in [int(x) for x in args.episodes.split(",")]:
         for prec in args.precision.split(","):
-            if prec != "fp32" and not fp16:
+            if (prec != "fp32" and not fp16) or (prec == "fp16x2" and not split):
                 continue
             fn = lambda seed: twisterl.collector.PPOCollector(E, 0.995, 0.995, 32, precision=prec).collect(env, pol, seed=seed)
             for i in range(args.warmup):
@@ -316,7 +323,7 @@ def precisions(args):
                 recs.append(n)
                 roll.append(float(c.stats.get("ms_rollout", 0.0)))
             last = _lib.debug_last_launch()
-            assert (last["family"], last["nw"]) == (_lib.TW_KERNEL_ROLLOUT_BIG, 16 if prec == "fp16" else 0), last
+            assert (last["family"], last["nw"]) == (_lib.TW_KERNEL_ROLLOUT_BIG, {"fp16": 16, "fp16x2": 32}.get(prec, 0)), last
             k = int(np.argsort(roll)[len(roll) // 2])
             row = {"bench": "precision", "env": env_name, "policy": pol_name, "precision": prec, "path": "device", "episodes": E, "records": recs[k],
                    "ms_rollout": round(roll[k], 3), "ms_rollout_min": round(min(roll), 3), "ms_rollout_max": round(max(roll), 3),
@@ -402,7 +409,7 @@ def main():
     ap.add_argument("--tree", default=None, help="the checkout to measure (default: this one)")
     ap.add_argument("--no-persist", action="store_true", help="TW_OPT_NO_PERSIST = 1: never the persistent grid + episode queue")
     ap.add_argument("--skip-host", action="store_true", help="device rows only (no host-stepped rows, no byte comparison with them)")
-    ap.add_argument("--precision", default=None, help="fp32,fp16: device rows in these precisions from one module built with fp16=True; appends to --out")
+    ap.add_argument("--precision", default=None, help="fp32,fp16[,fp16x2]: device rows in these precisions from one module built with fp16=True (fp16x2=True); appends to --out")
     ap.add_argument("--policy", default="default", choices=["default", "small", "deep"], help="with --precision: the policy's widths")
     ap.add_argument("--evaluate", action="store_true", help="collector.evaluate (episodes x 1 search) instead of the PPO collect, in the precisions of --precision; appends to --out")
     args = ap.parse_args()

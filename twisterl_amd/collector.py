@@ -286,7 +286,12 @@ class PPOCollector(PyBaseCollector):
     `PPOCollector(**config["collecting"])` (src/twisterl/rl/ppo.py:23).  `num_cores` is accepted
     for compatibility; the episodes run as GPU lanes, not rayon tasks.  Build extensions (all
     keyword-only, defaulted): seed, precision ("fp32" exact | "fp16" | "fp16x2"), episode_offset /
-    merge_order / reserve_cus for sharded collection (twisterl_amd.dist).
+    merge_order / reserve_cus for sharded collection (twisterl_amd.dist).  On a DeviceEnv the collect
+    runs inside one kernel for any generic policy: "fp32" always, "fp16" in a module built with
+    fp16=True (rounded activations, logits within ~1e-4 of float64), "fp16x2" in one built with
+    fp16x2=True (every operand split into two binary16 terms: f32 answers on the f16 matrix core;
+    a weight or an activation of 4095 or more has no such pair, and that collect runs in fp32 with
+    one line on stderr); a module without the kernel answers "f32 only".
     """
 
     def __init__(self, *args, **kwargs):

@@ -11,7 +11,9 @@
 // collect with precision fp16 of a module built with TW_DEVICE_ENV_FP16 runs in rollout_env16_kernel over EngineV16, its binary16
 // weight image packed into the collect's workspace by the module's launcher in front of every rollout, and evaluate / solve without
 // MCTS of a module built with TW_DEVICE_ENV_FP16_SOLVE run likewise in solve_env16_kernel, self-play and evaluate / solve WITH MCTS of
-// one built with TW_DEVICE_ENV_FP16_SEARCH in mcts_env16_kernel), and -- for
+// one built with TW_DEVICE_ENV_FP16_SEARCH in mcts_env16_kernel; a PPO collect with precision fp16x2 of a module built with
+// TW_DEVICE_ENV_FP16X2 runs in rollout_env16x2_kernel over EngineV16x2, its split image packed likewise, and runs again in the f32
+// kernel when an operand left the split terms' range), and -- for
 // a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has no search launcher -- self-play,
 // evaluate and solve with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
 // 1..4 actions and (TW_DEVICE_ENV_WIDE_SEARCH) for 5..31, which lives in the module
@@ -119,6 +121,19 @@ size_t engine16_lds_bytes(uint32_t nc, const PolicyDev &p)
     }
 }
 
+// EngineV16x2 (tw_engine_generic16x2.hpp): the split-f16 rollout kernel of a module built with TW_DEVICE_ENV_FP16X2
+size_t engine16x2_lds_bytes(uint32_t nc, const PolicyDev &p)
+{
+    switch (nc) {
+        case 4:  return EngineV16x2<4>::lds_bytes(p);
+        case 9:  return EngineV16x2<9>::lds_bytes(p);
+        case 16: return EngineV16x2<16>::lds_bytes(p);
+        case 25: return EngineV16x2<25>::lds_bytes(p);
+        case 36: return EngineV16x2<36>::lds_bytes(p);
+        default: return EngineV16x2<64>::lds_bytes(p);
+    }
+}
+
 // the checks of the host path (tw_env_generic.hip), with its messages
 int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
 {
@@ -127,7 +142,7 @@ int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
     return TW_OK;
 }
 
-// The grid of a module's rollout (0), solve (1), f16 solve (3) or f16 rollout (ENV_KERNEL_ROLLOUT16: tw_device_env::groups_per_cu16) kernel over
+// The grid of a module's rollout (0), solve (1), f16 solve (3), split-f16 rollout (5) or f16 rollout (ENV_KERNEL_ROLLOUT16: tw_device_env::groups_per_cu16) kernel over
 // `columns` episodes or attempts.  (The search kernel, 2, has no persistent
 // form: a first one faulted on the device and was taken out again -- DESIGN.md §8.)  As many workgroups
 // as the kernel's own occupancy puts on the CUs that reserve_cus leaves are resident at once (TW_OPT_ENV_RESIDENT_GROUPS > 0 caps
@@ -197,6 +212,9 @@ bool engine16_takes(const PolicyDev *pd)
     return pd->generic && pd->n_action >= 1 && pd->n_value >= 1 && pd->n_common + pd->n_action + pd->n_value <= GEN16_MAX_LAYERS;
 }
 
+// index of rollout_env16x2_kernel for tw_device_env::groups_per_cu (a module built with TW_DEVICE_ENV_FP16X2)
+constexpr int ENV_KERNEL_ROLLOUT16X2 = 5;
+
 // index of mcts_env16_kernel for tw_device_env::groups_per_cu (a module built with TW_DEVICE_ENV_FP16_SEARCH)
 constexpr int ENV_KERNEL_SEARCH16 = 4;
 
@@ -244,6 +262,10 @@ extern "C" int tw_device_env_host_vtable(const tw_device_env *env, const void *p
     return TW_OK;
 }
 
+// precision="fp16x2" computes what the f32 kernel computes only while every operand has a finite pair of binary16 terms
+// (tw_engine_generic16x2.hpp, "Range": every |weight| and every |activation that feeds a Linear| below 4095).  The pack kernel and
+// the engine flag a collect that left that range; the library then says so on stderr and returns the f32 kernel's collect, on the
+// same workspace, instead -- never results the f32 mode would not have given (as tw_ppo_collect does for the Puzzle kernels).
 extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *proto, size_t proto_bytes, const tw_policy *policy,
                                          const tw_ppo_params *prm, uint32_t max_records_per_episode, tw_collected **out)
 {
@@ -257,9 +279,14 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     // is a generic stack with both heads (at most GEN16_MAX_LAYERS layers: tw_policy_create's own limit)
     const bool f16 = prm->precision == TW_PREC_F16 && env->launch_rollout16 && env->groups_per_cu16 && pd->generic && pd->n_action >= 1 &&
                      pd->n_value >= 1 && pd->n_common + pd->n_action + pd->n_value <= GEN16_MAX_LAYERS;
+    // precision="fp16x2": rollout_env16x2_kernel over EngineV16x2, when the module holds it (the capability query: kernel 5 with a null
+    // result, answered without the HIP runtime -- asked BEFORE anything else, so that a module built without TW_DEVICE_ENV_FP16X2 is
+    // never handed a split request) and EngineV16 takes the policy.  It travels through launch_rollout16
+    const bool f16x2 = prm->precision == TW_PREC_F16X2 && env->launch_rollout16 && engine16_takes(pd) &&
+                       env->groups_per_cu(ENV_KERNEL_ROLLOUT16X2, 0, nullptr) == (int)hipSuccess;
     // what the kernels do not take: the host-stepped path over the module's own vtable (same bytes; its messages).  Episodes
     // longer than the finalize step's LDS tile holds (finalize_ppo_max_t_pad: 1,820 records) go there too.
-    if (!pd->generic || (prm->precision != TW_PREC_F32_EXACT && !f16) || max_records_per_episode > (uint32_t)finalize_ppo_max_t_pad(0))
+    if (!pd->generic || (prm->precision != TW_PREC_F32_EXACT && !f16 && !f16x2) || max_records_per_episode > (uint32_t)finalize_ppo_max_t_pad(0))
         return tw_ppo_collect_env(&vt, policy, prm, max_records_per_episode, out);
     if (prm->num_episodes == 0) { set_error("Something went wrong. No data in collected data chunks to merge. "); return TW_ERR_EMPTY; }   // collector.rs:41
     rc = check_env_policy(vt, pd); if (rc) return rc;
@@ -271,25 +298,27 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     const bool ragged = vt.observe_n != nullptr;                          // observations of variable length: two-byte ids, 0xFFFF = no id
     const uint32_t A = env->num_actions, NO = vt.n_obs, OW = (ragged || pd->obs_size > 256) ? 2u : 1u;
     const uint64_t t_pad = max_records_per_episode, R = E * t_pad;
-    const size_t lds_bytes = f16 ? engine16_lds_bytes(env->engine_nc, *pd) : engine_lds_bytes(env->engine_nc, *pd);
+    const size_t lds_bytes = f16x2 ? engine16x2_lds_bytes(env->engine_nc, *pd) : f16 ? engine16_lds_bytes(env->engine_nc, *pd) : engine_lds_bytes(env->engine_nc, *pd);
     if (lds_bytes > 159 * 1024) { set_error("rollout: %zu bytes of LDS needed, 159 KiB available", lds_bytes); return TW_ERR_UNSUPPORTED; }
     EnvGrid grid;
-    rc = env_grid(env, f16 ? ENV_KERNEL_ROLLOUT16 : 0, lds_bytes, E, prm->reserve_cus, &grid); if (rc) return rc;
+    rc = env_grid(env, f16x2 ? ENV_KERNEL_ROLLOUT16X2 : f16 ? ENV_KERNEL_ROLLOUT16 : 0, lds_bytes, E, prm->reserve_cus, &grid); if (rc) return rc;
     const uint64_t blocks = grid.blocks;
     if (blocks > 0x7fffffffull || t_pad > 0x7fffffffull) { set_error("tw_ppo_collect_device_env: bad episode count %llu", (unsigned long long)E); return TW_ERR_INVALID; }
     // the f16 image's size, from the layout function the pack kernel and the engine index with (tw_engine_generic16.hpp), over the
     // layer table's widths -- which live on the device (they never change after tw_policy_create)
     size_t image_halves = 0;
-    if (f16) {
+    if (f16 || f16x2) {
         const int n_layers = pd->n_common + pd->n_action + pd->n_value;
         std::vector<LayerDev> layers((size_t)n_layers);
         // (on the library's stream, not the null stream: a blocking copy there would wait for whatever else the process has queued on it)
         TW_HIP(hipMemcpyAsync(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost, current_stream()));
         TW_HIP(hipStreamSynchronize(current_stream()));
-        image_halves = gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
+        // (fp16x2: two planes per layer and no table, tw_engine_generic16x2.hpp)
+        image_halves = f16x2 ? gen16x2_image_halves(layers.data(), n_layers)
+                             : gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
     }
 
-    std::lock_guard<std::mutex> lock(workspace_mutex());
+    std::unique_lock<std::mutex> lock(workspace_mutex());      // (released before the f32 run of an out-of-range fp16x2 collect)
     hipStream_t s = current_stream();
     size_t cur = 0;
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
@@ -299,7 +328,8 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     // fp16: the binary16 weight image behind the f32 carve, which does not move (f32: no bytes).  Every half of it -- table padding,
     // weight padding and read slack included -- is written by pack_generic16_kernel before the rollout reads it; the table of
     // tests/memory_matrix.py lists the f32 carve's segments, and tests/test_gpu_device_env_fp16.py runs the fp16 collect on pre-filled
-    // workspace memory (tw_debug_fill_memory) for this one
+    // workspace memory (tw_debug_fill_memory) for this one.  fp16x2: the split image in the same place, every half of it written by
+    // pack_generic16x2_kernel (tests/test_gpu_device_env_fp16x2.py)
     const size_t o_img = cur;
     cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
     void *wsp = nullptr;
@@ -323,16 +353,17 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     }
     TW_HIP(hipEventRecord(ev.ev[0], s));
     int lr;
-    if (f16) {                                                            // the pack of the image, then the rollout (the module's launcher)
+    if (f16 || f16x2) {                                                   // the pack of the image, then the rollout (the module's launcher)
         EnvRollout16Args ra16{};
         ra16.r = ra;
-        ra16.image.img = reinterpret_cast<_Float16 *>(ws + o_img); ra16.image.halves = image_halves;
+        ra16.image.img = reinterpret_cast<_Float16 *>(ws + o_img);
+        ra16.image.halves = f16x2 ? ((uint64_t)image_halves | GEN16X2_REQUEST) : (uint64_t)image_halves;   // (the request: bit 63)
         lr = env->launch_rollout16(&ra16, proto, (unsigned)blocks, lds_bytes, s);
     } else
         lr = env->launch_rollout(&ra, proto, (unsigned)blocks, lds_bytes, s);
     if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment rollout launch", __FILE__, __LINE__);
-    // (tw_debug_last_launch: nw = 16 marks the f16 kernel, 0 the f32 one -- include/twisterl_hip.h)
-    note_launch(TW_KERNEL_ROLLOUT_BIG, 1, (int)env->engine_nc, f16 ? 16 : 0, 0, grid.persist, false, false, false, (uint32_t)blocks, 256);
+    // (tw_debug_last_launch: nw = 32 marks the split-f16 kernel, 16 the f16 one, 0 the f32 one -- include/twisterl_hip.h)
+    note_launch(TW_KERNEL_ROLLOUT_BIG, 1, (int)env->engine_nc, f16x2 ? 32 : f16 ? 16 : 0, 0, grid.persist, false, false, false, (uint32_t)blocks, 256);
     TW_HIP(hipEventRecord(ev.ev[1], s));
     rc = launch_scan(ra.out.ep_len, E, prm->merge_order ? 1 : 0, ep_start_ws, total_d, ws + o_scan, scan_scratch_bytes(E), s);
     if (rc) return rc;
@@ -342,6 +373,14 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     TW_HIP(hipStreamSynchronize(s));
     const uint64_t total = hv[0];
     const uint32_t err = (uint32_t)hv[1];
+    if (f16x2 && (err & GEN16X2_ERR_RANGE)) {                             // before every other error: the f32 kernel's run decides those
+        lock.unlock();
+        fprintf(stderr, "[twisterl_hip] precision fp16x2: a weight or an activation is outside the range of the split-f16 terms "
+                        "(|weight| < 4095, |activation| < 4095): this collect runs in fp32\n");
+        tw_ppo_params p32 = *prm;
+        p32.precision = TW_PREC_F32_EXACT;
+        return tw_ppo_collect_device_env(env, proto, proto_bytes, policy, &p32, max_records_per_episode, out);
+    }
     if (err & 9u) {
         // the id (or the count of observe_n) the host path reports: the first it meets -- the smallest record index, then the smallest
         // episode (the kernel flagged each such episode in ep_len and left the id / the count in that record's value field, which of

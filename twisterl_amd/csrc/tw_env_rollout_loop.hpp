@@ -1,14 +1,14 @@
-// tw_env_rollout_loop.hpp -- the step loop of the device-environment PPO rollout: the BODY of rollout_env_kernel and of
-// rollout_env16_kernel (tw_rollout_env.hpp), which include this file inside their function bodies.  NO once-pragma and no include
-// guard: it is included twice, once per kernel.  It is no header of its own -- nothing else may include it.
+// tw_env_rollout_loop.hpp -- the step loop of the device-environment PPO rollout: the BODY of rollout_env_kernel, of
+// rollout_env16_kernel and of rollout_env16x2_kernel (tw_rollout_env.hpp), which include this file inside their function bodies.  NO
+// once-pragma and no include guard: it is included three times, once per kernel.  It is no header of its own -- nothing else may include it.
 //
 // The including kernel has in scope, before the #include:
 //   Env, NC    its template parameters
-//   Eng        the engine: EngineV<NC> or EngineV16<NC>
+//   Eng        the engine: EngineV<NC>, EngineV16<NC> or EngineV16x2<NC>
 //   a          an EnvRolloutArgs, by value or by const reference
 //   proto      the prototype, a const Env
 //   lds        the dynamic LDS (extern __shared__ float lds[], aligned to 16)
-//   eng        a declared `Eng eng`; EngineV16: with eng.img already set
+//   eng        a declared `Eng eng`; EngineV16: with eng.img already set; EngineV16x2: with eng.img and eng.err already set
 //
 // Shared as TEXT and not as a function template: a function that both kernels inline changed how this compiler allocates the f32
 // kernels (device environments), and those stay what they are, instruction for instruction.

@@ -14,6 +14,8 @@
 // A module built with TW_DEVICE_ENV_FP16_SOLVE holds solve_env16_kernel<Env, NC> as well: evaluate's loop over EngineV16,
 // collector.evaluate / collector.solve with precision="fp16" and no MCTS.  One built with TW_DEVICE_ENV_FP16_SEARCH beside a search form
 // holds mcts_env16_kernel<Env, NC> (tw_mcts_env.hpp): self-play and MCTS-guided evaluate / solve with precision="fp16".
+// A module built with TW_DEVICE_ENV_FP16X2 holds rollout_env16x2_kernel<Env, NC>: the rollout's loop over EngineV16x2
+// (tw_engine_generic16x2.hpp), PPOCollector(precision="fp16x2"), f32 answers from split binary16 operands on the f16 matrix core.
 //
 // In this file: the argument structs and the descriptor; what the steps call (the Gumbel arg-max, the twist of the actions, the
 // streaming steps of 5 .. 31 actions, env_rows / env_rows_n); the four kernels; their launchers and occupancy queries.  The two step
@@ -22,6 +24,7 @@
 #pragma once
 #include "tw_engine_generic.hpp"
 #include "tw_engine_generic16.hpp"
+#include "tw_engine_generic16x2.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -35,7 +38,8 @@ struct EnvRolloutArgs {
     uint16_t  *obs16;                // [E][t_pad][n_obs] obs ids as the environment wrote them (before the twist); a struct with
                                      // observe_n: the ids of the record, then 0xFFFF up to the row stride n_obs
     uint32_t  *err;                  // |= 1: an obs id outside [0, obs_size); |= 2: an episode did not end within t_pad records;
-                                     // |= 8: observe_n returned a count outside 0 .. n_obs; zeroed by the library before the launch.
+                                     // |= 8: observe_n returned a count outside 0 .. n_obs; |= 16 (rollout_env16x2_kernel and its pack
+                                     // kernel alone): an operand outside the split terms' range; zeroed by the library before the launch.
                                      // An episode that met a bad id (count) at record t ends there: its ep_len is (t + 1) | 1 << 31,
                                      // record t's value field holds the id (the count) as bits and its reward field is 0.0f (1.0f)
     uint64_t   num_episodes, episode_offset, seed;
@@ -49,7 +53,10 @@ struct EnvRolloutArgs {
 // ... and what rollout_env16_kernel (precision="fp16": the same loop over EngineV16, tw_engine_generic16.hpp) needs on top
 struct EnvRollout16Args {
     EnvRolloutArgs r;
-    Gen16Image     image;            // carved from the collect's workspace, packed by the launcher before the rollout
+    Gen16Image     image;            // carved from the collect's workspace, packed by the launcher before the rollout.  image.halves with
+                                     // GEN16X2_REQUEST (bit 63) set: precision="fp16x2" -- the image is EngineV16x2's (gen16x2_image_halves()
+                                     // halves in the low bits) and the launcher runs pack_generic16x2_kernel and rollout_env16x2_kernel.
+                                     // Only a module that answers groups_per_cu(5, 0, nullptr) is ever handed such a request
 };
 
 // evaluate(): one column = one attempt (episode, search), as solve_big_kernel
@@ -152,7 +159,12 @@ struct tw_device_env {
     // share, EngineV16<engine_nc>::lds_bytes(pol); the pending ids and the rows of probabilities are added as for kernel 2); any other
     // module: hipErrorInvalidValue.  Kernel 4 with out == nullptr is that kernel's capability query, as kernel 3's (the library's
     // search_f16(), DeviceEnv.fp16_search).  launch_search runs that kernel, the pack of the image in front of it, when
-    // EnvMctsArgs::image.img is not null
+    // EnvMctsArgs::image.img is not null.
+    // Kernel 5: rollout_env16x2_kernel of a module built with TW_DEVICE_ENV_FP16X2 (lds_bytes = EngineV16x2<engine_nc>::lds_bytes(pol));
+    // any other module: hipErrorInvalidValue.  Kernel 5 with out == nullptr is that kernel's capability query, as kernel 3's (the PPO
+    // collect's dispatch, DeviceEnv.fp16x2): the library asks it BEFORE it hands launch_rollout16 a split request -- bit 63 of
+    // EnvRollout16Args::image.halves, GEN16X2_REQUEST -- so a module from before that kernel never sees one.  launch_rollout16 then
+    // runs pack_generic16x2_kernel and that kernel instead of the fp16 pair
     int (*groups_per_cu)(int kernel, size_t lds_bytes, int *out);
     // null unless the module was built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)): pack_generic16_kernel (the policy's
     // f32 device copies -> the binary16 image a->image, on stream s) and then rollout_env16_kernel, with launch_rollout's return
@@ -380,6 +392,9 @@ __global__ void __launch_bounds__(256, 1) rollout_env16_kernel(const EnvRollout1
 #include "tw_env_rollout_loop.hpp"
 }
 
+// rollout_env16x2_kernel, the same loop over EngineV16x2 (precision="fp16x2" of PPOCollector.collect), its launcher and its occupancy
+// query live in tw_rollout_env16x2.hpp, which the end of this file includes: a third kernel that includes tw_env_rollout_loop.hpp.
+
 // evaluate() (rust/src/rl/evaluate.rs:22-89 over single_solve, rl/solve.rs:17-71), as solve_big_kernel: one column = one attempt
 // (episode e, search a): reset, then while !is_final { total += reward; probs = Policy::predict (masked softmax, random twist);
 // action = argmax | weighted sample; step }.  Best-of-N and the means are reduced on the host.  An attempt's three results are
@@ -448,6 +463,12 @@ int launch_rollout_env(const EnvRolloutArgs *a, const void *proto, unsigned bloc
     return (int)hipGetLastError();
 }
 
+// defined in tw_rollout_env16x2.hpp (used below only inside #ifdef TW_DEVICE_ENV_FP16X2)
+template <class Env>
+int launch_rollout_env16x2(const EnvRollout16Args *a, const Env &p, unsigned blocks, size_t lds_bytes, hipStream_t s);
+template <class Env>
+int groups_per_cu_env16x2(size_t lds_bytes, int *out);
+
 // tw_device_env::launch_rollout16 / groups_per_cu16
 template <class Env>
 int launch_rollout_env16(const EnvRollout16Args *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
@@ -455,6 +476,9 @@ int launch_rollout_env16(const EnvRollout16Args *a, const void *proto, unsigned 
     constexpr int NC = env_engine_nc(Env::N_OBS);
     Env p;
     __builtin_memcpy(&p, proto, sizeof(Env));
+#ifdef TW_DEVICE_ENV_FP16X2
+    if (a->image.halves & GEN16X2_REQUEST) return launch_rollout_env16x2<Env>(a, p, blocks, lds_bytes, s);
+#endif
     auto *k = &rollout_env16_kernel<Env, NC>;         // (taken BEFORE the call: a module's assembly lists its kernels in the order they are first named)
     const int e = pack_image_for(k, lds_bytes, a->r.pol, a->image, s);
     if (e != (int)hipSuccess) return e;
@@ -482,6 +506,10 @@ int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
         if (!out) return (int)hipSuccess;
         return kernel_groups_per_cu(reinterpret_cast<const void *>(&solve_env16_kernel<Env, NC>), EngineV16<NC>::THREADS, lds_bytes, out);
     }
+#endif
+#ifdef TW_DEVICE_ENV_FP16X2
+    // kernel 5: rollout_env16x2_kernel, lds_bytes = EngineV16x2<engine_nc>::lds_bytes(pol); out == nullptr: the capability query
+    if (kernel == 5) return groups_per_cu_env16x2<Env>(lds_bytes, out);
 #endif
     if (!out || (kernel != 0 && kernel != 1)) return (int)hipErrorInvalidValue;
     const void *k = kernel == 0 ? reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>) : reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
@@ -516,3 +544,5 @@ int launch_solve_env(const EnvSolveArgs *a, const void *proto, unsigned blocks, 
 }
 
 }  // namespace tw
+
+#include "tw_rollout_env16x2.hpp"
