@@ -92,8 +92,16 @@
 // PPOCollector(precision="fp16x2").collect then runs on the device for any generic policy, f32 answers within the split mode's
 // a-priori bound.  The descriptor does not grow: the request travels to launch_rollout16 as bit 63 of EnvRollout16Args::image.halves,
 // the kernel's occupancy and the capability query are behind groups_per_cu(5, ...).  A weight or an activation of 4095 or more has no
-// finite pair of terms; the kernels flag it and the library returns the f32 kernel's collect instead.  evaluate, solve and the search
-// kernel in this precision answer "f32 only".  Without the define a module holds exactly the kernels it held.
+// finite pair of terms; the kernels flag it and the library returns the f32 kernel's collect instead.  Without the define a module
+// holds exactly the kernels it held.
+// `#define TW_DEVICE_ENV_FP16X2_SOLVE` (build_device_env(..., fp16x2_solve=True); it implies TW_DEVICE_ENV_FP16X2) adds
+// solve_env16x2_kernel, the evaluate loop over the same EngineV16x2 and the same two-plane image (twisterl_amd/csrc/tw_solve_env16x2.hpp):
+// collector.evaluate / collector.solve with precision="fp16x2" and num_mcts_searches == 0 then run on the device for any generic
+// policy, launched by the descriptor's launch_solve when its image carries the request bit (bit 63 of EnvSolveArgs::image.halves), its
+// occupancy and the capability query behind groups_per_cu(6, ...) -- again the descriptor does not grow.  Out of range, the library
+// returns the f32 kernel's answer, as for the collect.  The search kernel has no split form: self-play and MCTS-guided evaluate /
+// solve with precision="fp16x2" answer "f32 only" (tw_mcts_env.hpp includes the search loop exactly twice, and a test pins that).
+// A module built with TW_DEVICE_ENV_FP16X2 alone holds exactly the kernels it held.
 #pragma once
 
 #if defined(TW_DEVICE_ENV_FP16_SOLVE) && !defined(TW_DEVICE_ENV_FP16)
@@ -101,6 +109,9 @@
 #endif
 #if defined(TW_DEVICE_ENV_FP16_SEARCH) && !defined(TW_DEVICE_ENV_FP16)
 #define TW_DEVICE_ENV_FP16
+#endif
+#if defined(TW_DEVICE_ENV_FP16X2_SOLVE) && !defined(TW_DEVICE_ENV_FP16X2)
+#define TW_DEVICE_ENV_FP16X2
 #endif
 #if defined(TW_DEVICE_ENV_FP16X2) && !defined(TW_DEVICE_ENV_FP16)
 #define TW_DEVICE_ENV_FP16

@@ -127,7 +127,10 @@ enum {
                                  * weight image launched in front of it                                                        */
     TW_KERNEL_SOLVE_BIG = 5,    /* solve_big_kernel<nc>; nt 1: solve_env_kernel<Env, nc> of a device-environment module (nw 0), or
                                  * with nw 16 its solve_env16_kernel<Env, nc>: precision fp16 without MCTS of a module built with
-                                 * TW_DEVICE_ENV_FP16_SOLVE, the pack of the binary16 weight image launched in front of it    */
+                                 * TW_DEVICE_ENV_FP16_SOLVE, the pack of the binary16 weight image launched in front of it; with
+                                 * nw 32 its solve_env16x2_kernel<Env, nc>: precision fp16x2 without MCTS of a module built with
+                                 * TW_DEVICE_ENV_FP16X2_SOLVE, the pack of the two-plane split image launched in front of it (a
+                                 * call that left the split terms' range ran again in f32 and reports nw 0)                    */
     TW_KERNEL_ROLLOUT_BIG = 6,  /* rollout_big_kernel<nc>; nt 1: rollout_env_kernel<Env, nc> of a device-environment module (nw 0), or
                                  * with nw 16 its rollout_env16_kernel<Env, nc>: precision fp16 of a module built with
                                  * TW_DEVICE_ENV_FP16, the pack of the binary16 weight image launched in front of it; with nw 32
@@ -429,7 +432,9 @@ int tw_solve_env32(const tw_env_vtable *env, const tw_policy *policy, const tw_s
  * built against another layout.  tw_ppo_collect_device_env / tw_evaluate_device_env / tw_solve_device_env run the whole loop in one kernel (the policy on
  * EngineV, f32; precision TW_PREC_F16 of a generic policy on EngineV16: the PPO collect of a module built with TW_DEVICE_ENV_FP16,
  * evaluate and solve without MCTS of one built with TW_DEVICE_ENV_FP16_SOLVE, self-play and MCTS-guided evaluate and solve of one
- * built with TW_DEVICE_ENV_FP16_SEARCH); what that kernel does not take -- a policy of the MFMA
+ * built with TW_DEVICE_ENV_FP16_SEARCH; precision TW_PREC_F16X2 on EngineV16x2, f32 answers from split binary16 operands: the PPO
+ * collect of a module built with TW_DEVICE_ENV_FP16X2, evaluate and solve without MCTS of one built with
+ * TW_DEVICE_ENV_FP16X2_SOLVE); what that kernel does not take -- a policy of the MFMA
  * shape, another precision (the search kernel of a module without TW_DEVICE_ENV_FP16_SEARCH: any but f32) -- runs on the host-stepped path over
  * the module's own vtable (tw_ppo_collect_env / tw_az_collect_env / tw_evaluate_env: same bytes, same errors).  Self-play
  * (tw_az_collect_device_env) and evaluate with num_mcts_searches > 0 run in one kernel too when the module was built with

@@ -48,7 +48,9 @@ deterministic and sampled, in each listed precision from ONE module built with f
 side by side).  evaluate returns two means and no statistics, so a row carries the WHOLE CALL (checks, the image's pack in fp16, the
 kernel, the copies back, the reduction on the host) as median / min / max of --reps after --warmup, and the two means.  A --tree from
 before the keyword builds the plain module and gives the fp32 rows only: the parent's figures of the same session.
-profiles/r17_device_env_fp16_solve.jsonl.
+profiles/r17_device_env_fp16_solve.jsonl.  With fp16x2 in the list (--precision fp32,fp16,fp16x2) the module is built with
+fp16_solve=True, fp16x2_solve=True and holds solve_env16x2_kernel as well (EngineV16x2: split binary16 operands, f32 answers); a --tree
+from before that flag builds the module it can and gives the rows it has.  profiles/r22_device_env_fp16x2_solve.jsonl.
 
 --az and the MCTS shapes of --solve with --precision fp32,fp16 (and --policy default | deep): each listed precision from ONE module
 built with fp16_search=True (mcts_env_kernel and mcts_env16_kernel side by side; name + _f16), whole calls, median / min / max of --reps,
@@ -337,7 +339,8 @@ def precisions(args):
 
 
 def evaluate_bench(args):
-    """collector.evaluate on the device in fp32 and fp16 from ONE module built with fp16_solve=True: whole-call milliseconds, their spread."""
+    """collector.evaluate on the device in fp32, fp16 (and fp16x2) from ONE module built with fp16_solve=True (and fp16x2_solve=True):
+    whole-call milliseconds, their spread."""
     import inspect
     import numpy as np
     import twisterl_amd
@@ -352,6 +355,10 @@ def evaluate_bench(args):
     # (--tree of a checkout from before the fp16_solve form: the plain module, fp32 rows only)
     has16 = "fp16_solve" in inspect.signature(build_device_env).parameters
     kw, suffix = ({"fp16_solve": True}, "_fp16s") if has16 else ({}, "")
+    # fp16x2 in the list: the split evaluate kernel beside the other two, in one module (a tree from before the flag: the rows it has)
+    split = "fp16x2" in (args.precision or "").split(",") and "fp16x2_solve" in inspect.signature(build_device_env).parameters
+    if split:
+        kw, suffix = {"fp16_solve": True, "fp16x2_solve": True}, "_fp16s_x2s"
     if args.env == "perm8":
         so = build_device_env(os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", "perm8" + suffix, wide=True, **kw)
         env = DeviceEnv(so, "perm8" + suffix, [8, 32, 4], max_records=33)
@@ -369,7 +376,7 @@ def evaluate_bench(args):
     info = twisterl_amd.device_info()
     for E in [int(x) for x in args.episodes.split(",")]:
         for prec in (args.precision or "fp32").split(","):
-            if prec != "fp32" and not has16:
+            if (prec != "fp32" and not has16) or (prec == "fp16x2" and not split):
                 continue
             for det in (True, False):
                 pkw = {"precision": prec} if has16 else {}
@@ -382,7 +389,7 @@ def evaluate_bench(args):
                     res = fn(1000 + i)
                     ts.append((time.perf_counter() - t0) * 1e3)
                 last = _lib.debug_last_launch()
-                assert (last["family"], last["nw"]) == (_lib.TW_KERNEL_SOLVE_BIG, 16 if prec == "fp16" else 0), last
+                assert (last["family"], last["nw"]) == (_lib.TW_KERNEL_SOLVE_BIG, {"fp16": 16, "fp16x2": 32}.get(prec, 0)), last
                 row = {"bench": "evaluate", "env": env_name, "policy": pol_name, "precision": prec, "deterministic": det, "path": "device",
                        "episodes": E, "searches": 1, "wall_ms": round(float(np.median(ts)), 3), "wall_ms_min": round(min(ts), 3),
                        "wall_ms_max": round(max(ts), 3), "wall_ms_all": [round(t, 3) for t in ts], "success_rate": res[0], "mean_reward": res[1],

@@ -154,7 +154,7 @@ def _scan_asm(paths, who: str) -> int:
 
 def build_device_env(header: str, type_name: str, name: str, out_dir: str = None, force: bool = False, search: bool = False,
                      wide: bool = False, wide_search: bool = False, fp16: bool = False, fp16_solve: bool = False,
-                     fp16_search: bool = False, fp16x2: bool = False) -> str:
+                     fp16_search: bool = False, fp16x2: bool = False, fp16x2_solve: bool = False) -> str:
     """Compiles a user-written device environment (include/twisterl_device_env.hpp) into a loadable module:
     `#include "<header>"` + `TW_DEVICE_ENV(<type_name>, <name>)` with the library's own FLAGS (-ffp-contract=off: bit parity with the
     host path), the device assembly kept beside the module (<out_dir>/libtw_env_<name>.s) and scanned for MFMA hazards like the
@@ -177,9 +177,13 @@ def build_device_env(header: str, type_name: str, name: str, out_dir: str = None
     to the cache.  fp16x2=True implies fp16=True as well and puts `#define TW_DEVICE_ENV_FP16X2` in front of the header, with any of the
     forms and flags above: the module then also holds rollout_env16x2_kernel and the kernel that packs its two-plane binary16 weight
     image (twisterl_amd/csrc/tw_engine_generic16x2.hpp), and PPOCollector(precision="fp16x2").collect runs on the device
-    (DeviceEnv.fp16x2 says so); one more kind to the cache.  Every other combination of flags generates the source it generated before."""
+    (DeviceEnv.fp16x2 says so); one more kind to the cache.  fp16x2_solve=True implies fp16x2=True (and so fp16=True) and puts
+    `#define TW_DEVICE_ENV_FP16X2_SOLVE` in front of the header as well, with any of the forms and flags above: the module then also holds
+    solve_env16x2_kernel (twisterl_amd/csrc/tw_solve_env16x2.hpp), and collector.evaluate / collector.solve with precision="fp16x2" (no
+    MCTS) run on the device (DeviceEnv.fp16x2_solve says so); one more kind to the cache.  Every other combination of flags generates the source it generated before."""
     if fp16_search and not (search or wide_search):
         raise ValueError("build_device_env: fp16_search=True needs the search kernel: search=True or wide_search=True")
+    fp16x2 = fp16x2 or fp16x2_solve
     fp16 = fp16 or fp16_solve or fp16_search or fp16x2
     if wide_search and search:
         raise ValueError("build_device_env: wide_search=True is a form of its own, not an addition to search=True")
@@ -193,7 +197,7 @@ def build_device_env(header: str, type_name: str, name: str, out_dir: str = None
     stem = f"libtw_env_{name}"
     so, asm, src = (os.path.join(out_dir, stem + ext) for ext in (".so", ".s", ".hip"))
     text = (f'// generated by twisterl_amd.build.build_device_env\n{"#define TW_DEVICE_ENV_WIDE" + chr(10) if wide or wide_search else ""}'
-            f'{"#define TW_DEVICE_ENV_FP16" + chr(10) if fp16 else ""}{"#define TW_DEVICE_ENV_FP16_SOLVE" + chr(10) if fp16_solve else ""}{"#define TW_DEVICE_ENV_FP16_SEARCH" + chr(10) if fp16_search else ""}{"#define TW_DEVICE_ENV_FP16X2" + chr(10) if fp16x2 else ""}#include "{header}"\n'
+            f'{"#define TW_DEVICE_ENV_FP16" + chr(10) if fp16 else ""}{"#define TW_DEVICE_ENV_FP16_SOLVE" + chr(10) if fp16_solve else ""}{"#define TW_DEVICE_ENV_FP16_SEARCH" + chr(10) if fp16_search else ""}{"#define TW_DEVICE_ENV_FP16X2" + chr(10) if fp16x2 else ""}{"#define TW_DEVICE_ENV_FP16X2_SOLVE" + chr(10) if fp16x2_solve else ""}#include "{header}"\n'
             f'{"TW_DEVICE_ENV_WIDE_SEARCH" if wide_search else "TW_DEVICE_ENV_SEARCH" if search else "TW_DEVICE_ENV"}({type_name}, {name})\n')
     deps = [header] + HEADERS + sorted(glob.glob(os.path.join(ROOT, "include", "*.hpp")))
     if not force and os.path.exists(src) and open(src).read() == text and not _stale(so, deps + [src]) and os.path.exists(asm):

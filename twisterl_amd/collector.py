@@ -601,14 +601,16 @@ def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches
     -> ((success, reward), actions)   (python_interface/env.rs:180-191 over rl/solve.rs:73-101).
     Best of `num_searches` greedy/sampled roll-outs from the env's CURRENT state; the env is not modified.
     `precision` (keyword-only; "fp32" exact | "fp16" | "fp16x2") goes to the library as it is: a DeviceEnv built with fp16_solve=True
-    runs "fp16" without MCTS on the f16 matrix core, one built with fp16_search=True "fp16" with MCTS; what an environment does not take in that precision answers with the
-    library's own message ("... f32 only ...")."""
+    runs "fp16" without MCTS on the f16 matrix core, one built with fp16_search=True "fp16" with MCTS, one built with
+    fp16x2_solve=True "fp16x2" without MCTS (f32 answers from split binary16 operands; a weight or an activation of 4095 or more:
+    one line on stderr and the fp32 call's answer); what an environment does not take in that precision -- "fp16x2" with MCTS
+    always -- answers with the library's own message ("... f32 only ...")."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
     _check_precision(precision)
     prm = _solve_params(deterministic, num_searches, num_mcts_searches, C, max_expand_depth, seed, precision)
     if isinstance(py_env, PyEnv):
-        br = _PyEnvBridge(py_env, prototype=py_env._env.copy())             # (the caller's object is not touched)
+        br = _PyEnvBridge(py_env, prototype=py_env._env.copy())            # (the caller's object is not touched)
         cap = br.max_records + 1
         # 32-bit entries: an environment that tracks its own solution returns THAT (solve.rs:57-64), and its entries need not be actions
         cap = max(cap, int(getattr(py_env._env, "max_solution", 0)))
@@ -636,7 +638,8 @@ def evaluate(py_env, policy: Policy, num_episodes, deterministic, num_searches, 
     """evaluate(py_env, policy, num_episodes, deterministic, num_searches, num_mcts_searches, seed, C,
     max_expand_depth, num_cores) -> (success_rate, mean_reward)   (python_interface/env.rs:194-207 over
     rl/evaluate.rs:22-89).  `seed` keys the episode scrambles and action draws (the reference ignores it);
-    `num_cores` is accepted for compatibility; `precision` (keyword-only) as in solve()."""
+    `num_cores` is accepted for compatibility; `precision` (keyword-only) as in solve(): a DeviceEnv built with fp16x2_solve=True
+    evaluates in "fp16x2" on the device, the precision of a PPOCollector(precision="fp16x2") collect."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
     _check_precision(precision)

@@ -13,7 +13,8 @@
 // MCTS of a module built with TW_DEVICE_ENV_FP16_SOLVE run likewise in solve_env16_kernel, self-play and evaluate / solve WITH MCTS of
 // one built with TW_DEVICE_ENV_FP16_SEARCH in mcts_env16_kernel; a PPO collect with precision fp16x2 of a module built with
 // TW_DEVICE_ENV_FP16X2 runs in rollout_env16x2_kernel over EngineV16x2, its split image packed likewise, and runs again in the f32
-// kernel when an operand left the split terms' range), and -- for
+// kernel when an operand left the split terms' range, and evaluate / solve without MCTS of one built with
+// TW_DEVICE_ENV_FP16X2_SOLVE run likewise in solve_env16x2_kernel, with the same f32 run out of range), and -- for
 // a module built without TW_DEVICE_ENV_SEARCH / TW_DEVICE_ENV_WIDE_SEARCH, whose descriptor has no search launcher -- self-play,
 // evaluate and solve with MCTS.  With the launcher those two run in mcts_env_kernel (tw_mcts_env.hpp), for
 // 1..4 actions and (TW_DEVICE_ENV_WIDE_SEARCH) for 5..31, which lives in the module
@@ -142,7 +143,7 @@ int check_env_policy(const tw_env_vtable &vt, const PolicyDev *pd)
     return TW_OK;
 }
 
-// The grid of a module's rollout (0), solve (1), f16 solve (3), split-f16 rollout (5) or f16 rollout (ENV_KERNEL_ROLLOUT16: tw_device_env::groups_per_cu16) kernel over
+// The grid of a module's rollout (0), solve (1), f16 solve (3), split-f16 rollout (5), split-f16 solve (6) or f16 rollout (ENV_KERNEL_ROLLOUT16: tw_device_env::groups_per_cu16) kernel over
 // `columns` episodes or attempts.  (The search kernel, 2, has no persistent
 // form: a first one faulted on the device and was taken out again -- DESIGN.md §8.)  As many workgroups
 // as the kernel's own occupancy puts on the CUs that reserve_cus leaves are resident at once (TW_OPT_ENV_RESIDENT_GROUPS > 0 caps
@@ -528,16 +529,30 @@ constexpr uint64_t SOLVE_ACTION_BYTES_MAX = 1ull << 30;
 // index of solve_env16_kernel for tw_device_env::groups_per_cu (a module built with TW_DEVICE_ENV_FP16_SOLVE)
 constexpr int ENV_KERNEL_SOLVE16 = 3;
 
+// index of solve_env16x2_kernel for tw_device_env::groups_per_cu (a module built with TW_DEVICE_ENV_FP16X2_SOLVE)
+constexpr int ENV_KERNEL_SOLVE16X2 = 6;
+
+// precision="fp16x2" of evaluate / solve: solve_env16x2_kernel over EngineV16x2, without MCTS alone (the search kernel has no split
+// form), when EngineV16 takes the policy and the module holds the kernel (the capability query: kernel 6 with a null result, answered
+// without the HIP runtime -- asked BEFORE a split request is formed, so that a module built without TW_DEVICE_ENV_FP16X2_SOLVE is
+// never handed one)
+bool attempts_f16x2(const tw_device_env *env, const PolicyDev *pd, const tw_solve_params *prm)
+{
+    return prm->precision == TW_PREC_F16X2 && prm->num_mcts_searches == 0 && engine16_takes(pd) &&
+           env->groups_per_cu(ENV_KERNEL_SOLVE16X2, 0, nullptr) == (int)hipSuccess;
+}
+
 // precision="fp16" of evaluate / solve: solve_env16_kernel over EngineV16, when the module holds it (the capability query: kernel 3
 // with a null result, answered without the HIP runtime), the policy is a generic stack with both heads (at most GEN16_MAX_LAYERS
 // layers: the collect's own rule).  With MCTS the kernel is mcts_env16_kernel instead, under the same rule: search_f16
 bool attempts_f16(const tw_device_env *env, const PolicyDev *pd, const tw_solve_params *prm)
 {
+    if (prm->precision == TW_PREC_F16X2) return attempts_f16x2(env, pd, prm);
     if (prm->num_mcts_searches != 0) return search_f16(env, pd, prm->precision);
     return prm->precision == TW_PREC_F16 && engine16_takes(pd) && env->groups_per_cu(ENV_KERNEL_SOLVE16, 0, nullptr) == (int)hipSuccess;
 }
 
-// What solve_env_kernel / solve_env16_kernel / mcts_env_kernel take of an evaluate or a solve; everything else is the host-stepped path's (the callers
+// What solve_env_kernel / solve_env16_kernel / solve_env16x2_kernel / mcts_env_kernel take of an evaluate or a solve; everything else is the host-stepped path's (the callers
 // hand over to it).  node_cap: the search's tree size, for attempts_device_env.
 bool attempts_on_device(const tw_device_env *env, const PolicyDev *pd, const tw_solve_params *prm, uint64_t num_episodes, uint32_t max_steps,
                         uint64_t *node_cap)
@@ -553,44 +568,51 @@ bool attempts_on_device(const tw_device_env *env, const PolicyDev *pd, const tw_
 // num_mcts_searches > 0, of mcts_env_kernel in solve mode: checks, grid, workspace, launch, the errors of the host-stepped path, and
 // run_attempts_env's reduction -- per episode the first attempt whose (success, total) is strictly better (solve.rs:84-98).
 // best_actions (solve; else null): the moves of that attempt, the only row that is copied back.
+// precision="fp16x2" (attempts_f16x2) computes what the f32 kernel computes only while every operand has a finite pair of binary16
+// terms; the pack kernel and the engine flag a call that left that range (GEN16X2_ERR_RANGE), and this function then says so on stderr
+// and runs itself again in f32, on the same workspace -- never results the f32 mode would not have given, as the PPO collect above.
 int attempts_device_env(const char *who, const tw_device_env *env, const void *proto, const tw_env_vtable &vt, const PolicyDev *pd,
                         const tw_solve_params *prm, uint64_t num_episodes, uint64_t episode_offset, bool from_state, uint32_t max_steps_in,
                         uint64_t node_cap, std::vector<float> &best_s, std::vector<float> &best_r, std::vector<uint32_t> *best_actions)
 {
     const bool mcts = prm->num_mcts_searches != 0;
     const bool f16 = prm->precision == TW_PREC_F16;                       // (attempts_on_device: then attempts_f16 holds; with mcts: search_f16)
+    const bool f16x2 = prm->precision == TW_PREC_F16X2;                   // (attempts_on_device: then attempts_f16x2 holds, and mcts does not)
     const uint32_t max_steps = max_steps_in ? max_steps_in : 1u;
     int rc = check_env_policy(vt, pd); if (rc) return rc;
     if (pd->n_perms > 0 && pd->obs_size > 256 && !pd->obs_perms16) { set_error("%s: policy without its two-byte twist table", who); return TW_ERR_INVALID; }
     rc = require_device(); if (rc) return rc;
     const uint64_t N = prm->num_searches, NA = num_episodes * N;
     if (NA / N != num_episodes) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
-    const size_t lds_bytes = f16 ? engine16_lds_bytes(env->engine_nc, *pd) : engine_lds_bytes(env->engine_nc, *pd);
+    const size_t lds_bytes = f16x2 ? engine16x2_lds_bytes(env->engine_nc, *pd) : f16 ? engine16_lds_bytes(env->engine_nc, *pd) : engine_lds_bytes(env->engine_nc, *pd);
     const size_t search_lds = mcts ? env_mcts_pending_bytes(env->n_obs) + env_mcts_probs_bytes(env->num_actions) : 0;
     if (lds_bytes + search_lds > 159 * 1024) {
         set_error("solve: %zu bytes of LDS needed, 159 KiB available", lds_bytes + search_lds); return TW_ERR_UNSUPPORTED;
     }
     EnvGrid grid;                                                         // (MCTS-guided attempts: the search kernel, one column per attempt)
     grid.blocks = (NA + GEN_COLS - 1) / GEN_COLS; grid.persist = false;
-    if (!mcts) { rc = env_grid(env, f16 ? ENV_KERNEL_SOLVE16 : 1, lds_bytes, NA, 0, &grid); if (rc) return rc; }
+    if (!mcts) { rc = env_grid(env, f16x2 ? ENV_KERNEL_SOLVE16X2 : f16 ? ENV_KERNEL_SOLVE16 : 1, lds_bytes, NA, 0, &grid); if (rc) return rc; }
     const uint64_t blocks = grid.blocks;
     if (blocks > 0x7fffffffull) { set_error("solve: bad attempt count %llu", (unsigned long long)NA); return TW_ERR_INVALID; }
     // the played moves: one row of max_steps bytes per attempt (an attempt that ends has played at most max_steps)
     const uint32_t stride = best_actions ? max_steps : 0u;
     // fp16: the image's size, as the collect reads it -- the layout function over the layer table's widths, which live on the device
     size_t image_halves = 0;
-    if (f16) {
+    if (f16 || f16x2) {
         const int n_layers = pd->n_common + pd->n_action + pd->n_value;
         std::vector<LayerDev> layers((size_t)n_layers);
         TW_HIP(hipMemcpyAsync(layers.data(), pd->layers, (size_t)n_layers * sizeof(LayerDev), hipMemcpyDeviceToHost, current_stream()));   // (as the collect)
         TW_HIP(hipStreamSynchronize(current_stream()));
-        image_halves = gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
+        // (fp16x2: two planes per layer and no table, tw_engine_generic16x2.hpp)
+        image_halves = f16x2 ? gen16x2_image_halves(layers.data(), n_layers)
+                             : gen16_image_halves((uint32_t)pd->obs_size, (uint32_t)pd->emb, layers.data(), n_layers);
     }
 
     std::vector<float> succ(NA), tot(NA);
     std::vector<uint32_t> steps(NA), ce;
     uint64_t hv[2] = {0, 0};
-    std::lock_guard<std::mutex> lock(workspace_mutex());                  // (to the end: the best attempt's row is read from the workspace)
+    std::unique_lock<std::mutex> lock(workspace_mutex());                 // (to the end: the best attempt's row is read from the workspace;
+                                                                          // released before the f32 run of an out-of-range fp16x2 call)
     hipStream_t s = current_stream();
     size_t cur = 0;
     auto seg = [&](size_t bytes) { size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
@@ -598,7 +620,8 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
                  o_arena = seg(mcts ? (size_t)NA * node_cap * ENV_MCTS_NODE_BYTES : 0), o_act = seg((size_t)NA * stride);
     // fp16: the binary16 weight image behind o_act, appended as the fp16 collect appends its own (f32: no bytes, and nothing moves).
     // Every half of it is written by pack_generic16_kernel before solve_env16_kernel reads it; tests/test_gpu_device_env_fp16_solve.py
-    // runs the call on pre-filled workspace memory for this region
+    // runs the call on pre-filled workspace memory for this region.  fp16x2: the split image in the same place, every half of it
+    // written by pack_generic16x2_kernel (tests/test_gpu_device_env_fp16x2_solve.py)
     const size_t o_img = cur;
     cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
     if (mcts) { rc = check_memory_fit(cur, who); if (rc) return rc; }
@@ -636,13 +659,14 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
             const unsigned int first = (unsigned int)(blocks * GEN_COLS);
             TW_HIP(hipMemcpyAsync(sa.queue, &first, 4, hipMemcpyHostToDevice, s));
         }
-        if (f16) {                                                        // the module's launcher packs it, then solve_env16_kernel
-            sa.image.img = reinterpret_cast<_Float16 *>(ws + o_img); sa.image.halves = image_halves;
+        if (f16 || f16x2) {                                               // the module's launcher packs it, then solve_env16_kernel
+            sa.image.img = reinterpret_cast<_Float16 *>(ws + o_img);      // (fp16x2, the request: bit 63 -- then solve_env16x2_kernel)
+            sa.image.halves = f16x2 ? ((uint64_t)image_halves | GEN16X2_REQUEST) : (uint64_t)image_halves;
         }
         const int lr = env->launch_solve(&sa, proto, (unsigned)blocks, lds_bytes, s);
         if (lr != (int)hipSuccess) return hip_fail((hipError_t)lr, "device environment evaluate launch", __FILE__, __LINE__);
-        // (tw_debug_last_launch: nw = 16 marks the f16 kernel, 0 the f32 one -- include/twisterl_hip.h)
-        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, f16 ? 16 : 0, 0, grid.persist, from_state, false, false, (uint32_t)blocks, 256);
+        // (tw_debug_last_launch: nw = 32 marks the split-f16 kernel, 16 the f16 one, 0 the f32 one -- include/twisterl_hip.h)
+        note_launch(TW_KERNEL_SOLVE_BIG, 1, (int)env->engine_nc, f16x2 ? 32 : f16 ? 16 : 0, 0, grid.persist, from_state, false, false, (uint32_t)blocks, 256);
     }
     TW_HIP(hipMemcpyAsync(succ.data(), ws + o_s, NA * 4, hipMemcpyDeviceToHost, s));
     TW_HIP(hipMemcpyAsync(tot.data(), ws + o_t, NA * 4, hipMemcpyDeviceToHost, s));
@@ -650,6 +674,14 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
     TW_HIP(hipMemcpyAsync(hv, ws + o_err, 8, hipMemcpyDeviceToHost, s));
     TW_HIP(hipStreamSynchronize(s));
     const uint32_t err = (uint32_t)hv[0];
+    if (f16x2 && (err & GEN16X2_ERR_RANGE)) {                             // before every other error: the f32 kernel's run decides those
+        lock.unlock();
+        fprintf(stderr, "[twisterl_hip] precision fp16x2: a weight or an activation is outside the range of the split-f16 terms "
+                        "(|weight| < 4095, |activation| < 4095): this %s runs in fp32\n", from_state ? "solve" : "evaluate");
+        tw_solve_params p32 = *prm;
+        p32.precision = TW_PREC_F32_EXACT;
+        return attempts_device_env(who, env, proto, vt, pd, &p32, num_episodes, episode_offset, from_state, max_steps_in, node_cap, best_s, best_r, best_actions);
+    }
     if (mcts) {
         if (err & 13u) {
             ce.resize(NA * 4);

@@ -1,14 +1,16 @@
 // tw_env_solve_loop.hpp -- the step loop of the device-environment evaluate / solve: the BODY of solve_env_kernel and of
-// solve_env16_kernel (tw_rollout_env.hpp), which include this file inside their function bodies.  NO once-pragma and no include
-// guard: it is included twice, once per kernel.  It is no header of its own -- nothing else may include it.
+// solve_env16_kernel (tw_rollout_env.hpp) and of solve_env16x2_kernel (tw_solve_env16x2.hpp), which include this file inside their
+// function bodies.  NO once-pragma and no include guard: it is included three times, once per kernel.  It is no header of its own --
+// nothing else may include it.
 //
 // The including kernel has in scope, before the #include:
 //   Env, NC    its template parameters
-//   Eng        the engine: EngineV<NC> or EngineV16<NC>
+//   Eng        the engine: EngineV<NC>, EngineV16<NC> or EngineV16x2<NC>
 //   a          an EnvSolveArgs, by value or by const reference
 //   proto      the prototype, a const Env
 //   lds        the dynamic LDS (extern __shared__ float lds[], aligned to 16)
-//   eng        a declared `Eng eng`; EngineV16: with eng.img already set
+//   eng        a declared `Eng eng`; EngineV16: with eng.img already set; EngineV16x2: with eng.img and eng.err (= a.err, where
+//              eng.end() raises GEN16X2_ERR_RANGE) already set
 //
 // Shared as TEXT and not as a function template, for the reason tw_env_rollout_loop.hpp gives.
     constexpr int A = Env::NUM_ACTIONS, NO = Env::N_OBS;

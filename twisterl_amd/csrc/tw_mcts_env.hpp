@@ -160,6 +160,7 @@ int groups_per_cu_search_env(int kernel, size_t lds_bytes, int *out)
         return kernel_groups_per_cu(reinterpret_cast<const void *>(&mcts_env16_kernel<Env, NC>), EngineV16<NC>::THREADS, all16, out);
     }
 #endif
+    // (kernels 0, 1, 3, 5 and 6 -- solve_env16x2_kernel of TW_DEVICE_ENV_FP16X2_SOLVE -- are the plain module's, with its answers)
     if (kernel != 2) return groups_per_cu_env<Env>(kernel, lds_bytes, out);
     if (!out) return (int)hipErrorInvalidValue;
     const size_t all = lds_bytes + env_mcts_pending_bytes(Env::N_OBS) + env_mcts_probs_bytes(Env::NUM_ACTIONS);

@@ -16,6 +16,8 @@
 // holds mcts_env16_kernel<Env, NC> (tw_mcts_env.hpp): self-play and MCTS-guided evaluate / solve with precision="fp16".
 // A module built with TW_DEVICE_ENV_FP16X2 holds rollout_env16x2_kernel<Env, NC>: the rollout's loop over EngineV16x2
 // (tw_engine_generic16x2.hpp), PPOCollector(precision="fp16x2"), f32 answers from split binary16 operands on the f16 matrix core.
+// One built with TW_DEVICE_ENV_FP16X2_SOLVE holds solve_env16x2_kernel<Env, NC> as well (tw_solve_env16x2.hpp): evaluate's loop over
+// EngineV16x2, collector.evaluate / collector.solve with precision="fp16x2" and no MCTS.
 //
 // In this file: the argument structs and the descriptor; what the steps call (the Gumbel arg-max, the twist of the actions, the
 // streaming steps of 5 .. 31 actions, env_rows / env_rows_n); the four kernels; their launchers and occupancy queries.  The two step
@@ -75,7 +77,11 @@ struct EnvSolveArgs {
     uint32_t  actions_stride;        // addressed by attempt like the three results; a move at or beyond the stride is not stored
     Gen16Image image;                // img null: solve_env_kernel, f32.  Else precision="fp16": solve_env16_kernel over EngineV16 (a module
                                      // built with TW_DEVICE_ENV_FP16_SOLVE), the image carved from the call's workspace and packed by the
-                                     // launcher before the kernel; the f32 kernel never reads this member
+                                     // launcher before the kernel; the f32 kernel never reads this member.  image.halves with
+                                     // GEN16X2_REQUEST (bit 63) set: precision="fp16x2" -- the image is EngineV16x2's and the launcher runs
+                                     // pack_generic16x2_kernel and solve_env16x2_kernel (a module built with TW_DEVICE_ENV_FP16X2_SOLVE:
+                                     // only one that answers groups_per_cu(6, 0, nullptr) is ever handed such a request); err then also
+                                     // takes |= 16, GEN16X2_ERR_RANGE: an operand outside the split terms' range
 };
 
 // Self-play (solve_on == 0) and MCTS-guided evaluate (solve_on != 0) of mcts_env_kernel (tw_mcts_env.hpp), which a module has when it
@@ -164,7 +170,11 @@ struct tw_device_env {
     // any other module: hipErrorInvalidValue.  Kernel 5 with out == nullptr is that kernel's capability query, as kernel 3's (the PPO
     // collect's dispatch, DeviceEnv.fp16x2): the library asks it BEFORE it hands launch_rollout16 a split request -- bit 63 of
     // EnvRollout16Args::image.halves, GEN16X2_REQUEST -- so a module from before that kernel never sees one.  launch_rollout16 then
-    // runs pack_generic16x2_kernel and that kernel instead of the fp16 pair
+    // runs pack_generic16x2_kernel and that kernel instead of the fp16 pair.
+    // Kernel 6: solve_env16x2_kernel of a module built with TW_DEVICE_ENV_FP16X2_SOLVE (lds_bytes = EngineV16x2<engine_nc>::lds_bytes(pol));
+    // any other module: hipErrorInvalidValue.  Kernel 6 with out == nullptr is that kernel's capability query (evaluate's and solve's
+    // dispatch, DeviceEnv.fp16x2_solve): the library asks it BEFORE it hands launch_solve a split request -- bit 63 of
+    // EnvSolveArgs::image.halves -- so a module from before that kernel never sees one
     int (*groups_per_cu)(int kernel, size_t lds_bytes, int *out);
     // null unless the module was built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)): pack_generic16_kernel (the policy's
     // f32 device copies -> the binary16 image a->image, on stream s) and then rollout_env16_kernel, with launch_rollout's return
@@ -394,6 +404,7 @@ __global__ void __launch_bounds__(256, 1) rollout_env16_kernel(const EnvRollout1
 
 // rollout_env16x2_kernel, the same loop over EngineV16x2 (precision="fp16x2" of PPOCollector.collect), its launcher and its occupancy
 // query live in tw_rollout_env16x2.hpp, which the end of this file includes: a third kernel that includes tw_env_rollout_loop.hpp.
+// solve_env16x2_kernel, the evaluate loop over EngineV16x2, lives likewise in tw_solve_env16x2.hpp: the third kernel of that loop.
 
 // evaluate() (rust/src/rl/evaluate.rs:22-89 over single_solve, rl/solve.rs:17-71), as solve_big_kernel: one column = one attempt
 // (episode e, search a): reset, then while !is_final { total += reward; probs = Policy::predict (masked softmax, random twist);
@@ -468,6 +479,11 @@ template <class Env>
 int launch_rollout_env16x2(const EnvRollout16Args *a, const Env &p, unsigned blocks, size_t lds_bytes, hipStream_t s);
 template <class Env>
 int groups_per_cu_env16x2(size_t lds_bytes, int *out);
+// defined in tw_solve_env16x2.hpp (used below only inside #ifdef TW_DEVICE_ENV_FP16X2_SOLVE)
+template <class Env>
+int launch_solve_env16x2(const EnvSolveArgs *a, const Env &p, unsigned blocks, size_t lds_bytes, hipStream_t s);
+template <class Env>
+int groups_per_cu_solve_env16x2(size_t lds_bytes, int *out);
 
 // tw_device_env::launch_rollout16 / groups_per_cu16
 template <class Env>
@@ -511,6 +527,10 @@ int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
     // kernel 5: rollout_env16x2_kernel, lds_bytes = EngineV16x2<engine_nc>::lds_bytes(pol); out == nullptr: the capability query
     if (kernel == 5) return groups_per_cu_env16x2<Env>(lds_bytes, out);
 #endif
+#ifdef TW_DEVICE_ENV_FP16X2_SOLVE
+    // kernel 6: solve_env16x2_kernel, lds_bytes = EngineV16x2<engine_nc>::lds_bytes(pol); out == nullptr: the capability query
+    if (kernel == 6) return groups_per_cu_solve_env16x2<Env>(lds_bytes, out);
+#endif
     if (!out || (kernel != 0 && kernel != 1)) return (int)hipErrorInvalidValue;
     const void *k = kernel == 0 ? reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>) : reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
     return kernel_groups_per_cu(k, EngineV<NC>::THREADS, lds_bytes, out);
@@ -518,13 +538,18 @@ int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
 
 // tw_device_env::launch_solve.  EnvSolveArgs::image.img null: solve_env_kernel.  Else the pack of the image and solve_env16_kernel,
 // as launch_rollout_env16 runs the collect's -- in a module built with TW_DEVICE_ENV_FP16_SOLVE; any other module holds no such kernel
-// and refuses (hipErrorInvalidValue), as this one refuses a policy EngineV16 does not take.
+// and refuses (hipErrorInvalidValue), as this one refuses a policy EngineV16 does not take.  An image whose size carries
+// GEN16X2_REQUEST: the split pack and solve_env16x2_kernel (launch_solve_env16x2), in a module built with TW_DEVICE_ENV_FP16X2_SOLVE --
+// the library asks groups_per_cu(6, 0, nullptr) first, so no other module is handed one.
 template <class Env>
 int launch_solve_env(const EnvSolveArgs *a, const void *proto, unsigned blocks, size_t lds_bytes, hipStream_t s)
 {
     constexpr int NC = env_engine_nc(Env::N_OBS);
     Env p;
     __builtin_memcpy(&p, proto, sizeof(Env));
+#ifdef TW_DEVICE_ENV_FP16X2_SOLVE
+    if (a->image.halves & GEN16X2_REQUEST) return launch_solve_env16x2<Env>(a, p, blocks, lds_bytes, s);
+#endif
     if (a->image.img) {
 #ifdef TW_DEVICE_ENV_FP16_SOLVE
         auto *k16 = &solve_env16_kernel<Env, NC>;         // (taken before the call, as in launch_rollout_env16)
@@ -546,3 +571,4 @@ int launch_solve_env(const EnvSolveArgs *a, const void *proto, unsigned blocks, 
 }  // namespace tw
 
 #include "tw_rollout_env16x2.hpp"
+#include "tw_solve_env16x2.hpp"

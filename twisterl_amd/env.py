@@ -243,7 +243,8 @@ class DeviceEnv:
     of any generic policy on the f16 matrix core (`fp16` says whether the module has that kernel; without it: "f32 only"), and one
     built with fp16_solve=True runs collector.evaluate / collector.solve with precision="fp16" and no MCTS likewise (`fp16_solve`),
     one built with fp16_search=True beside a search form AZCollector(precision="fp16").collect and evaluate / solve WITH MCTS (`fp16_search`),
-    one built with fp16x2=True PPOCollector(precision="fp16x2").collect, f32 answers from split binary16 operands (`fp16x2`);
+    one built with fp16x2=True PPOCollector(precision="fp16x2").collect, f32 answers from split binary16 operands (`fp16x2`),
+    one built with fp16x2_solve=True collector.evaluate / collector.solve with precision="fp16x2" and no MCTS as well (`fp16x2_solve`);
     a module built with build_device_env(..., search=True) (1..4 actions; wide_search=True: 1..31) runs AZCollector.collect and evaluate with MCTS inside one kernel too
     (tw_az_collect_device_env; `search` says whether the module has that kernel), any other module steps the same struct's host
     code for those (tw_az_collect_env / tw_evaluate_env).  solve runs from the object's CURRENT state in one kernel as evaluate does
@@ -345,6 +346,13 @@ class DeviceEnv:
         the device, f32 answers from split binary16 operands on the f16 matrix core.  Asked like fp16_solve -- groups_per_cu(5, 0,
         null) -- so it works on a machine without a GPU."""
         return int(self._desc.groups_per_cu(5, 0, None)) == 0
+
+    @property
+    def fp16x2_solve(self) -> bool:
+        """The module holds the split-f16 evaluate kernel (built with fp16x2_solve=True): collector.evaluate and collector.solve with
+        precision="fp16x2" and no MCTS run on the device, f32 answers from split binary16 operands.  Asked like fp16_solve --
+        groups_per_cu(6, 0, null) -- so it works on a machine without a GPU."""
+        return int(self._desc.groups_per_cu(6, 0, None)) == 0
 
     @property
     def variable_obs(self) -> bool:
