@@ -102,6 +102,18 @@
 // returns the f32 kernel's answer, as for the collect.  The search kernel has no split form: self-play and MCTS-guided evaluate /
 // solve with precision="fp16x2" answer "f32 only" (tw_mcts_env.hpp includes the search loop exactly twice, and a test pins that).
 // A module built with TW_DEVICE_ENV_FP16X2 alone holds exactly the kernels it held.
+// The reference's default policy: every kernel above runs EngineV, which takes a "generic stack".  A policy of ONE common Linear of
+// 32 / 64 / 128 / 256 units with linear heads, an embedding size that is a multiple of 32 and obs_size <= 256 -- what the reference's
+// trainer builds unless it is told otherwise, BasicPolicy(common_layers=(256,)) -- gets the image of the Puzzle engines from
+// tw_policy_create instead (the "MFMA shape"), without EngineV's layer table, and a device environment under it runs host-stepped over
+// the module's vtable.  `#define TW_DEVICE_ENV_BASIC` before this header (build_device_env(..., basic=True) emits it; it composes
+// with every form and flag above) adds pack_basic_view_kernel (twisterl_amd/csrc/tw_env_basic_view.hpp): the module's f32 launchers
+// then also take a VIEW of such a policy, whose three layers that kernel packs -- table, padded biases, matrix-core images -- from the
+// policy's live natural-layout arrays into the call's workspace in front of every launch, and PPO collect, evaluate and solve, and with
+// a search form self-play and the MCTS-guided calls, run in the same kernels, byte-equal to the host-stepped path.  The descriptor and
+// the argument structs do not grow: the capability query is groups_per_cu(7, 0, nullptr) (DeviceEnv.basic), asked before a view is
+// formed, and a view is told by PolicyDev::generic with a non-zero PolicyDev::hidden.  fp16 / fp16x2 under such a policy still answer
+// "f32 only".  Without the define a module holds exactly the kernels it held, and behaves as it did.
 #pragma once
 
 #if defined(TW_DEVICE_ENV_FP16_SOLVE) && !defined(TW_DEVICE_ENV_FP16)

@@ -11,7 +11,7 @@ device collect is checked byte-equal to the host one first.
 
 --env perm8: an environment of MORE than four actions (examples/device_env/permutation.hpp with N = 8: 28 transpositions, 8 ids per
 state, obs_size 64, max_steps 32, difficulty 4; a module built with wide=True; policy 64-512-128-64 + heads -- two common layers: with one of 128 units and an obs_size of at most 256 the policy has
-the MFMA shape, which the device environments hand to the host-stepped path): the same two kernels stream over the 28 actions.  profiles/r11_device_env_wide.jsonl.
+the MFMA shape, which the device environments hand to the host-stepped path unless the module was built with basic=True -- see --basic): the same two kernels stream over the 28 actions.  profiles/r11_device_env_wide.jsonl.
 
 --az: self-play instead.  Whole AZCollector.collect calls of GridWorld 5 x 5 with the same policy, --az-shape episodes x searches
 (4096x100; if the first call takes more than a minute the run goes on at 1024x32 and says so), median of --reps: ONE row, whose
@@ -57,6 +57,15 @@ built with fp16_search=True (mcts_env_kernel and mcts_env16_kernel side by side;
 rows APPENDED to --out with their "precision".  fp16 has no host-stepped counterpart: the fp16 rows of --solve are device rows only.  A
 --tree from before the flag builds the plain search module and gives the fp32 rows only: the parent's figures of the same session.
 profiles/r20_device_env_fp16_search.jsonl.
+
+--basic: the reference's DEFAULT policy shape -- embedding 256 -> ONE common layer of 256 units -> linear heads, the "MFMA shape" that a
+device environment with at most 256 obs ids used to hand to the host-stepped path -- on GridWorld 3 x 3 (obs_size 81, max_steps 64) and
+Permutation8 (obs_size 64, 28 actions, max_steps 32), PPO collect of --episodes episodes from ONE module per environment built with
+basic=True: (a) the call as the tree runs it, in rollout_env_kernel behind pack_basic_view_kernel; (b) tw_ppo_collect_env over the
+module's host vtable, which is what the call ran on before the flag (byte-compared with (a) first); (c) the same module under
+common=(48,), the one-common-layer policy that is NOT the MFMA shape and that the other rows of this script's family use.  Whole calls,
+median / min / max of --reps after --warmup; the device rows also carry the rollout's milliseconds (the events around the module's
+launcher: in (a) the pack and the rollout).  Rows are APPENDED to --out.  profiles/r23_device_env_basic.jsonl.
 """
 import argparse
 import ctypes as C
@@ -401,6 +410,76 @@ def evaluate_bench(args):
                         f.write(json.dumps(row) + "\n")
 
 
+def basic_bench(args):
+    """PPO collect of GridWorld 3 x 3 and Permutation8 under the one-common-layer policy 256 -> 256, from a module built with basic=True:
+    device, host-stepped, and the same module under common=(48,)."""
+    import numpy as np
+    import twisterl_amd
+    from twisterl_amd import _lib, twisterl
+    from twisterl_amd.build import build_device_env
+    from twisterl_amd.collector import CollectedData, _DeviceResult
+    from twisterl_amd.env import DeviceEnv
+    from tests.util import amd_policy, make_deep_policy_arrays_obs, make_policy_arrays_obs
+    if twisterl_amd.device_count() < 1:
+        raise SystemExit("no GPU")
+    if args.no_persist:
+        _lib.check(_lib.lib().tw_set_launch_option(_lib.TW_OPT_NO_PERSIST, 1))
+    info = twisterl_amd.device_info()
+    grid = (os.path.join(ROOT, "examples", "device_env", "gridworld.hpp"), "tw_examples::GridWorld3x3", "gridworld3x3_basic", {}, [3, 3, 64, 1], 65,
+            "GridWorld3x3", 81, 4)
+    perm = (os.path.join(ROOT, "examples", "device_env", "permutation.hpp"), "tw_examples::Permutation8", "perm8_basic", {"wide": True}, [8, 32, 4], 33,
+            "Permutation8 (28 actions)", 64, 28)
+    for header, type_, name, kw, params, max_records, env_name, obs_size, A in (grid, perm):
+        env = DeviceEnv(build_device_env(header, type_, name, basic=True, **kw), name, params, max_records=max_records)
+        assert env.basic
+        vt = _lib.EnvVTable()
+        _lib.check(_lib.lib().tw_device_env_host_vtable(*env._args(), C.byref(vt)))
+        basic = amd_policy(make_policy_arrays_obs(obs_size, seed=0, emb=256, hidden=256, n_actions=A))
+        c48 = amd_policy(make_deep_policy_arrays_obs(obs_size, seed=0, emb=256, common=(48,), n_actions=A))
+
+        def device(pol, E, seed):
+            return twisterl.collector.PPOCollector(E, 0.995, 0.995, 32).collect(env, pol, seed=seed)
+
+        def host(pol, E, seed):
+            prm = _lib.PPOParams(E, 0, 0.995, 0.995, seed, _lib.TW_PREC_F32_EXACT, 1, 0)
+            out = C.c_void_p()
+            _lib.check(_lib.lib().tw_ppo_collect_env(C.byref(vt), pol._handle(), C.byref(prm), env.max_records, C.byref(out)))
+            return CollectedData._from_device(_DeviceResult(out.value))
+
+        for E in [int(x) for x in args.episodes.split(",")]:
+            if not args.skip_host:
+                a, b = device(basic, E, 1).to_numpy(), host(basic, E, 1).to_numpy()
+                assert all(a[k].tobytes() == b[k].tobytes() for k in a), "device and host collects differ"
+            runs = [("device", "basic=True", basic, device, f"{obs_size}-256-256+heads (one common layer: the MFMA shape)")]
+            if not args.skip_host:
+                runs.append(("host_stepped", "tw_ppo_collect_env", basic, host, f"{obs_size}-256-256+heads (one common layer: the MFMA shape)"))
+            runs.append(("device", "common=(48,)", c48, device, f"{obs_size}-256-48+heads (generic)"))
+            for path, what, pol, fn, pol_name in runs:
+                for i in range(args.warmup):
+                    fn(pol, E, 100 + i)
+                ts, recs, roll = [], [], []
+                for i in range(args.reps):
+                    t0 = time.perf_counter()
+                    c = fn(pol, E, 1000 + i)
+                    n = len(c)
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                    recs.append(n)
+                    roll.append(float(c.stats.get("ms_rollout", 0.0)))
+                k = int(np.argsort(ts)[len(ts) // 2])
+                row = {"bench": "basic", "env": env_name, "policy": pol_name, "path": path, "what": what, "episodes": E, "records": recs[k],
+                       "wall_ms": round(ts[k], 3), "wall_ms_min": round(min(ts), 3), "wall_ms_max": round(max(ts), 3),
+                       "records_per_s": round(recs[k] / (ts[k] * 1e-3), 1), "wall_ms_all": [round(t, 3) for t in ts],
+                       "ms_rollout": round(roll[k], 3) if path == "device" else None, "reps": args.reps, "warmup": args.warmup, "device": info["name"]}
+                if path == "device":
+                    last = _lib.debug_last_launch()
+                    assert last["family"] == _lib.TW_KERNEL_ROLLOUT_BIG, f"the device rows did not run the module's kernel: {last}"
+                    row.update(persist=last["persist"], blocks=last["blocks"])
+                print(json.dumps(row), flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--solve", action="store_true", help="collector.solve from the current state against the host-stepped path; appends rows to --out")
@@ -419,7 +498,10 @@ def main():
     ap.add_argument("--precision", default=None, help="fp32,fp16[,fp16x2]: device rows in these precisions from one module built with fp16=True (fp16x2=True); appends to --out")
     ap.add_argument("--policy", default="default", choices=["default", "small", "deep"], help="with --precision: the policy's widths")
     ap.add_argument("--evaluate", action="store_true", help="collector.evaluate (episodes x 1 search) instead of the PPO collect, in the precisions of --precision; appends to --out")
+    ap.add_argument("--basic", action="store_true", help="the one-common-layer policy 256 -> 256 from a module built with basic=True: device, host-stepped, and common=(48,); appends to --out")
     args = ap.parse_args()
+    if args.basic:
+        return basic_bench(args)
     if args.evaluate:
         return evaluate_bench(args)
     if args.az:

@@ -154,7 +154,7 @@ def _scan_asm(paths, who: str) -> int:
 
 def build_device_env(header: str, type_name: str, name: str, out_dir: str = None, force: bool = False, search: bool = False,
                      wide: bool = False, wide_search: bool = False, fp16: bool = False, fp16_solve: bool = False,
-                     fp16_search: bool = False, fp16x2: bool = False, fp16x2_solve: bool = False) -> str:
+                     fp16_search: bool = False, fp16x2: bool = False, fp16x2_solve: bool = False, basic: bool = False) -> str:
     """Compiles a user-written device environment (include/twisterl_device_env.hpp) into a loadable module:
     `#include "<header>"` + `TW_DEVICE_ENV(<type_name>, <name>)` with the library's own FLAGS (-ffp-contract=off: bit parity with the
     host path), the device assembly kept beside the module (<out_dir>/libtw_env_<name>.s) and scanned for MFMA hazards like the
@@ -180,7 +180,12 @@ def build_device_env(header: str, type_name: str, name: str, out_dir: str = None
     (DeviceEnv.fp16x2 says so); one more kind to the cache.  fp16x2_solve=True implies fp16x2=True (and so fp16=True) and puts
     `#define TW_DEVICE_ENV_FP16X2_SOLVE` in front of the header as well, with any of the forms and flags above: the module then also holds
     solve_env16x2_kernel (twisterl_amd/csrc/tw_solve_env16x2.hpp), and collector.evaluate / collector.solve with precision="fp16x2" (no
-    MCTS) run on the device (DeviceEnv.fp16x2_solve says so); one more kind to the cache.  Every other combination of flags generates the source it generated before."""
+    MCTS) run on the device (DeviceEnv.fp16x2_solve says so); one more kind to the cache.  basic=True puts `#define TW_DEVICE_ENV_BASIC` in front of the header, with any of the forms and flags
+    above: the module then also holds pack_basic_view_kernel (twisterl_amd/csrc/tw_env_basic_view.hpp), and the f32 kernels the module
+    has -- PPO collect, evaluate and solve, with a search form self-play and the MCTS-guided calls -- also run under the reference's
+    DEFAULT policy, one common layer of 32 / 64 / 128 / 256 units and obs_size <= 256, which otherwise runs host-stepped (DeviceEnv.basic
+    says so; fp16 / fp16x2 under such a policy stay "f32 only"); one more kind to the cache.  Every other combination of flags generates
+    the source it generated before."""
     if fp16_search and not (search or wide_search):
         raise ValueError("build_device_env: fp16_search=True needs the search kernel: search=True or wide_search=True")
     fp16x2 = fp16x2 or fp16x2_solve
@@ -197,7 +202,7 @@ def build_device_env(header: str, type_name: str, name: str, out_dir: str = None
     stem = f"libtw_env_{name}"
     so, asm, src = (os.path.join(out_dir, stem + ext) for ext in (".so", ".s", ".hip"))
     text = (f'// generated by twisterl_amd.build.build_device_env\n{"#define TW_DEVICE_ENV_WIDE" + chr(10) if wide or wide_search else ""}'
-            f'{"#define TW_DEVICE_ENV_FP16" + chr(10) if fp16 else ""}{"#define TW_DEVICE_ENV_FP16_SOLVE" + chr(10) if fp16_solve else ""}{"#define TW_DEVICE_ENV_FP16_SEARCH" + chr(10) if fp16_search else ""}{"#define TW_DEVICE_ENV_FP16X2" + chr(10) if fp16x2 else ""}{"#define TW_DEVICE_ENV_FP16X2_SOLVE" + chr(10) if fp16x2_solve else ""}#include "{header}"\n'
+            f'{"#define TW_DEVICE_ENV_FP16" + chr(10) if fp16 else ""}{"#define TW_DEVICE_ENV_FP16_SOLVE" + chr(10) if fp16_solve else ""}{"#define TW_DEVICE_ENV_FP16_SEARCH" + chr(10) if fp16_search else ""}{"#define TW_DEVICE_ENV_FP16X2" + chr(10) if fp16x2 else ""}{"#define TW_DEVICE_ENV_FP16X2_SOLVE" + chr(10) if fp16x2_solve else ""}{"#define TW_DEVICE_ENV_BASIC" + chr(10) if basic else ""}#include "{header}"\n'
             f'{"TW_DEVICE_ENV_WIDE_SEARCH" if wide_search else "TW_DEVICE_ENV_SEARCH" if search else "TW_DEVICE_ENV"}({type_name}, {name})\n')
     deps = [header] + HEADERS + sorted(glob.glob(os.path.join(ROOT, "include", "*.hpp")))
     if not force and os.path.exists(src) and open(src).read() == text and not _stale(so, deps + [src]) and os.path.exists(asm):

@@ -287,7 +287,9 @@ class PPOCollector(PyBaseCollector):
     for compatibility; the episodes run as GPU lanes, not rayon tasks.  Build extensions (all
     keyword-only, defaulted): seed, precision ("fp32" exact | "fp16" | "fp16x2"), episode_offset /
     merge_order / reserve_cus for sharded collection (twisterl_amd.dist).  On a DeviceEnv the collect
-    runs inside one kernel for any generic policy: "fp32" always, "fp16" in a module built with
+    runs inside one kernel for any generic policy (the reference's default policy -- ONE common layer of
+    32 / 64 / 128 / 256 units, obs_size <= 256 -- runs host-stepped over the module's vtable instead, unless
+    the module was built with basic=True, which takes it into the same kernel in "fp32"): "fp32" always, "fp16" in a module built with
     fp16=True (rounded activations, logits within ~1e-4 of float64), "fp16x2" in one built with
     fp16x2=True (every operand split into two binary16 terms: f32 answers on the f16 matrix core;
     a weight or an activation of 4095 or more has no such pair, and that collect runs in fp32 with
@@ -521,7 +523,9 @@ PPOCollector._collect_foreign = _collect_foreign
 
 def _collect_device_env(self, env: DeviceEnv, policy: Policy, seed) -> CollectedData:
     """PPOCollector.collect of a device environment: the whole loop on the device (tw_ppo_collect_device_env; the library hands what
-    its kernel does not take to the host-stepped path over the same struct).  AZCollector.collect: tw_az_collect_device_env -- self-play
+    its kernel does not take to the host-stepped path over the same struct: episodes above 1,820 records, a precision the module has no
+    kernel for, and a policy of ONE common layer of 32 / 64 / 128 / 256 units with obs_size <= 256 unless the module was built with
+    basic=True -- the library decides, nothing is routed here).  AZCollector.collect: tw_az_collect_device_env -- self-play
     inside one kernel for a module built with search=True, else the struct's host code (tw_az_collect_env over the module's vtable)."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
@@ -604,7 +608,9 @@ def solve(py_env, policy: Policy, deterministic, num_searches, num_mcts_searches
     runs "fp16" without MCTS on the f16 matrix core, one built with fp16_search=True "fp16" with MCTS, one built with
     fp16x2_solve=True "fp16x2" without MCTS (f32 answers from split binary16 operands; a weight or an activation of 4095 or more:
     one line on stderr and the fp32 call's answer); what an environment does not take in that precision -- "fp16x2" with MCTS
-    always -- answers with the library's own message ("... f32 only ...")."""
+    always -- answers with the library's own message ("... f32 only ...").  On a DeviceEnv the call is one kernel for any generic
+    policy; the reference's default policy (ONE common layer of 32 / 64 / 128 / 256 units, obs_size <= 256) runs host-stepped over the
+    module's vtable, unless the module was built with basic=True ("fp32" only)."""
     if not isinstance(policy, Policy):
         raise TypeError("argument 'policy': expected twisterl_amd.nn.Policy")
     _check_precision(precision)

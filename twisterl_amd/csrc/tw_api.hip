@@ -580,14 +580,14 @@ tw_policy *create_generic_policy(const tw_policy_desc *d)
     for (uint32_t i = 0; i < d->n_value; ++i) all.push_back(&d->value[i]);
     // every layer's outputs are padded to a multiple of four (zero weight columns, zero bias): the engine works on output quads
     auto pad4 = [](uint32_t x) { return (x + 3u) & ~3u; };
-    // matrix-core image of a layer (LayerDev::wm): tiles of 16 outputs, tb tiles per block, nb blocks, kg groups of four inputs
-    auto tiles_per_block = [](uint32_t out) { const uint32_t tiles = (out + 15u) / 16u; return tiles >= 4u ? 4u : tiles; };
-    auto blocks_of = [&](uint32_t out) { const uint32_t tiles = (out + 15u) / 16u, tb = tiles_per_block(out); return (tiles + tb - 1u) / tb; };
+    // matrix-core image of a layer (LayerDev::wm): tiles of 16 outputs, tb tiles per block, nb blocks, kg groups of four inputs --
+    // gen_layer_shape (tw_common.hpp), the rule the device-side pack of tw_env_basic_view.hpp shares
     std::vector<size_t> o_wm(n_layers);
     for (uint32_t i = 0; i < n_layers; ++i) {
-        const uint32_t in = all[i]->in_features, out = all[i]->out_features, tb = tiles_per_block(out), nb = blocks_of(out), kg = (in + 3u) / 4u;
-        o_w[i] = seg((size_t)in * pad4(out) * 4); o_b[i] = seg((size_t)nb * tb * 16 * 4 + 16);
-        o_wm[i] = seg((size_t)(kg + 8) * 4 * nb * 16 * tb * 4 + 64);          // (+ 8 k-groups of read slack: EngineV loads that far ahead)
+        const uint32_t in = all[i]->in_features, out = all[i]->out_features;
+        const GenLayerShape shape = gen_layer_shape(in, out);
+        o_w[i] = seg((size_t)in * pad4(out) * 4); o_b[i] = seg((size_t)shape.b_bytes);
+        o_wm[i] = seg((size_t)shape.wm_bytes);                                // (with the k-groups of read slack: EngineV loads that far ahead)
     }
     std::vector<uint8_t> img(cur, 0);
     float *emb = reinterpret_cast<float *>(img.data() + o_emb);
@@ -598,7 +598,8 @@ tw_policy *create_generic_policy(const tw_policy_desc *d)
         float *wd = reinterpret_cast<float *>(img.data() + o_w[i]);
         for (uint32_t k = 0; k < in; ++k) memcpy(wd + (size_t)k * outp, all[i]->weights + (size_t)k * out, (size_t)out * 4);
         memcpy(img.data() + o_b[i], all[i]->bias, (size_t)out * 4);
-        const uint32_t tb = tiles_per_block(out), nb = blocks_of(out), kg = (in + 3u) / 4u;
+        const GenLayerShape shape = gen_layer_shape(in, out);
+        const uint32_t tb = shape.tb, nb = shape.nb, kg = shape.kg;
         float *wm = reinterpret_cast<float *>(img.data() + o_wm[i]);
         for (uint32_t k = 0; k < kg * 4; ++k)
             for (uint32_t b = 0; b < nb; ++b)
@@ -627,7 +628,8 @@ tw_policy *create_generic_policy(const tw_policy_desc *d)
         tab[i].w = reinterpret_cast<const float *>(base + o_w[i]); tab[i].b = reinterpret_cast<const float *>(base + o_b[i]);
         tab[i].in = (int32_t)all[i]->in_features; tab[i].out = (int32_t)pad4(all[i]->out_features); tab[i].relu = all[i]->apply_relu ? 1 : 0; tab[i].pad = 0;
         tab[i].wm = reinterpret_cast<const float *>(base + o_wm[i]);
-        tab[i].kg = (int32_t)((all[i]->in_features + 3u) / 4u); tab[i].nb = (int32_t)blocks_of(all[i]->out_features); tab[i].tb = (int32_t)tiles_per_block(all[i]->out_features); tab[i].pad2 = 0;
+        const GenLayerShape shape = gen_layer_shape(all[i]->in_features, all[i]->out_features);
+        tab[i].kg = (int32_t)shape.kg; tab[i].nb = (int32_t)shape.nb; tab[i].tb = (int32_t)shape.tb; tab[i].pad2 = 0;
         pol->gen_layers.push_back(tab[i]); pol->gen_out.push_back(all[i]->out_features);
     }
     e = hipMemcpy(pol->arena, img.data(), img.size(), hipMemcpyHostToDevice);

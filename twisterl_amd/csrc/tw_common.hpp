@@ -409,6 +409,28 @@ struct LayerDev {
     int32_t kg, nb, tb, pad2;     // k-groups of four inputs; blocks of tb 16-output tiles (tb = 4 from 64 outputs up, else all tiles in one block)
 };
 
+// The shape of one Linear's EngineV image, the ONE place its rule is written down: tw_policy_create lays a generic stack's layers out
+// with it on the host, and the device-side pack of a one-common-layer policy (tw_env_basic_view.hpp) with it on the device.
+//   b:  nb * tb * 16 floats (+ 16 bytes: the engine reads the bias in quads)
+//   wm: (kg + GEN_WM_SLACK_KG) * 4 rows of nb * 16 * tb floats (+ 64 bytes) -- EngineV loads GEN_WM_SLACK_KG k-groups ahead of its MFMAs
+constexpr uint32_t GEN_WM_SLACK_KG = 8;
+struct GenLayerShape {
+    uint32_t kg, nb, tb, row;     // row = nb * 16 * tb: floats of the image per input, the layer's outputs padded to whole blocks
+    uint64_t b_bytes, wm_bytes;
+};
+__host__ __device__ inline GenLayerShape gen_layer_shape(uint32_t in, uint32_t out)
+{
+    GenLayerShape s;
+    const uint32_t tiles = (out + 15u) / 16u;
+    s.tb = tiles >= 4u ? 4u : tiles;
+    s.nb = (tiles + s.tb - 1u) / s.tb;
+    s.kg = (in + 3u) / 4u;
+    s.row = s.nb * 16u * s.tb;
+    s.b_bytes = (uint64_t)s.row * 4u + 16u;
+    s.wm_bytes = (uint64_t)(s.kg + GEN_WM_SLACK_KG) * 4u * s.row * 4u + 64u;
+    return s;
+}
+
 // ---- device-side policy image (built once by tw_policy_create) ------------------------------
 struct PolicyDev {
     int32_t obs_size, emb, hidden, n_actions, n_perms;

@@ -7,7 +7,10 @@
 // id), and an environment with other than four actions has its logits narrowed (A < 4) or moved from a wide array (A > 4).  The two
 // small kernels that serves, compact_env_obs8_kernel and narrow_logits_kernel, live here behind launch_compact_obs8 / launch_narrow_logits.
 // What the kernels do not take runs on the host-stepped path (tw_env_generic.hip) over the module's own vtable, the same code on
-// the CPU: a policy of the MFMA shape (its image has no EngineV layers), another precision (that path's "f32 only" error; but a PPO
+// the CPU: a policy of the MFMA shape (its image has no EngineV layers -- unless the module was built with TW_DEVICE_ENV_BASIC: its
+// launchers then pack those layers from the policy's live natural-layout arrays into the call's workspace in front of every f32 launch,
+// and the call runs in the same kernels under a view of the policy, kernel_policy() below; fp16 / fp16x2 under such a policy stay
+// with the host path's "f32 only"), another precision (that path's "f32 only" error; but a PPO
 // collect with precision fp16 of a module built with TW_DEVICE_ENV_FP16 runs in rollout_env16_kernel over EngineV16, its binary16
 // weight image packed into the collect's workspace by the module's launcher in front of every rollout, and evaluate / solve without
 // MCTS of a module built with TW_DEVICE_ENV_FP16_SOLVE run likewise in solve_env16_kernel, self-play and evaluate / solve WITH MCTS of
@@ -238,6 +241,35 @@ int gen16_image_size(const PolicyDev *pd, hipStream_t s, size_t *halves)
     return TW_OK;
 }
 
+// The policy the environment kernels run.  They run EngineV, which wants a layer table: a generic stack has one, a policy of the MFMA
+// shape -- the reference's default, one common layer -- does not, and goes to the host-stepped path.  But a module built with
+// TW_DEVICE_ENV_BASIC holds pack_basic_view_kernel (tw_env_basic_view.hpp), which builds that table and the three layers' images from
+// the policy's live natural-layout arrays, in a block of the call's workspace, in front of every launch: for such a module, in f32, the
+// answer is a VIEW of the policy (*view: generic = 1, one layer per stack, the same embedding rows and twist tables; `layers` is set by
+// the caller once the workspace is reserved, see launch_policy()), and the call goes down the device path with it unchanged.  The
+// capability query -- kernel 7 with a null result, answered without the HIP runtime -- is asked BEFORE a view is formed, so a module
+// built without the define never sees one.  Other precisions keep the host path's "f32 only" under such a policy.
+const PolicyDev *kernel_policy(const tw_device_env *env, const PolicyDev *pd, uint32_t precision, PolicyDev *view)
+{
+    if (precision != TW_PREC_F32_EXACT || !basic_view_source(*pd) || env->groups_per_cu(ENV_KERNEL_PACK_BASIC, 0, nullptr) != (int)hipSuccess) return pd;
+    *view = basic_view(*pd, nullptr);
+    return view;
+}
+
+// bytes of a view's block behind a call's carve (any other policy: none)
+size_t basic_block_bytes(const PolicyDev *pd)
+{
+    return is_basic_view(*pd) ? (size_t)basic_view_layout((uint32_t)pd->emb, (uint32_t)pd->hidden, (uint32_t)pd->n_actions).bytes : 0;
+}
+
+// the policy a launcher is handed: *pd, a view with its block at `block`
+PolicyDev launch_policy(const PolicyDev *pd, const void *block)
+{
+    PolicyDev p = *pd;
+    if (is_basic_view(p)) p.layers = reinterpret_cast<const LayerDev *>(block);
+    return p;
+}
+
 }  // namespace
 
 int tw::launch_compact_obs8(const uint16_t *obs16, const uint32_t *ep_len, const uint64_t *ep_start, uint64_t E, int t_pad, int n_obs,
@@ -275,7 +307,8 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     int rc = check_descriptor(env, proto, proto_bytes, "tw_ppo_collect_device_env"); if (rc) return rc;
     note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);      // (tw_debug_last_launch: nothing yet; the host-stepped path reports nothing)
     const tw_env_vtable vt = host_table(env, proto);
-    const PolicyDev *pd = policy_dev(policy);
+    PolicyDev view;                                                       // (a one-common-layer policy in a module that packs its layers)
+    const PolicyDev *pd = kernel_policy(env, policy_dev(policy), prm->precision, &view);
     // precision="fp16": rollout_env16_kernel over EngineV16, when the module holds it (built with TW_DEVICE_ENV_FP16) and the policy
     // is a generic stack with both heads (at most GEN16_MAX_LAYERS layers: tw_policy_create's own limit)
     const bool f16 = prm->precision == TW_PREC_F16 && env->launch_rollout16 && env->groups_per_cu16 && pd->generic && pd->n_action >= 1 &&
@@ -330,14 +363,15 @@ extern "C" int tw_ppo_collect_device_env(const tw_device_env *env, const void *p
     // weight padding and read slack included -- is written by pack_generic16_kernel before the rollout reads it; the table of
     // tests/memory_matrix.py lists the f32 carve's segments, and tests/test_gpu_device_env_fp16.py runs the fp16 collect on pre-filled
     // workspace memory (tw_debug_fill_memory) for this one.  fp16x2: the split image in the same place, every half of it written by
-    // pack_generic16x2_kernel (tests/test_gpu_device_env_fp16x2.py)
+    // pack_generic16x2_kernel (tests/test_gpu_device_env_fp16x2.py).  f32 under a view of a one-common-layer policy: its block of
+    // EngineV layers in the same place, every byte of it written by pack_basic_view_kernel (tests/test_gpu_device_env_basic.py)
     const size_t o_img = cur;
-    cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
+    cur = (cur + image_halves * sizeof(_Float16) + basic_block_bytes(pd) + 255) / 256 * 256;
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
     uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
     EnvRolloutArgs ra{};
-    ra.pol = *pd;
+    ra.pol = launch_policy(pd, ws + o_img);
     ra.out.rec = reinterpret_cast<PaddedRec *>(ws + o_rec); ra.out.ep_len = reinterpret_cast<uint32_t *>(ws + o_len); ra.out.t_pad = (int32_t)t_pad;
     ra.obs16 = reinterpret_cast<uint16_t *>(ws + o_obs16);
     if (A > 4) ra.lgw = reinterpret_cast<float *>(ws + o_lgw);
@@ -426,7 +460,8 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
     int rc = check_descriptor(env, proto, proto_bytes, "tw_az_collect_device_env"); if (rc) return rc;
     note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);      // (the host-stepped path reports nothing)
     const tw_env_vtable vt = host_table(env, proto);
-    const PolicyDev *pd = policy_dev(policy);
+    PolicyDev view;                                                       // (as the PPO collect)
+    const PolicyDev *pd = kernel_policy(env, policy_dev(policy), prm->precision, &view);
     uint64_t node_cap = 0;
     // precision="fp16": mcts_env16_kernel, when the module holds it and EngineV16 takes the policy (search_f16); any other precision but
     // f32, and fp16 without that, are the host-stepped path's to refuse
@@ -462,16 +497,17 @@ extern "C" int tw_az_collect_device_env(const tw_device_env *env, const void *pr
                  o_obs16 = seg(R * NO * 2), o_ce = seg(E * 16), o_arena = seg((size_t)E * node_cap * ENV_MCTS_NODE_BYTES),
                  o_pw = seg(A > 4 ? R * A * sizeof(float) : 0);           // more than four actions: the MCTS probabilities, [E][t_pad][A]
     // fp16: the binary16 weight image behind everything else, so that no f32 offset moves (f32: no bytes).  Every half of it is written
-    // by pack_generic16_kernel before mcts_env16_kernel reads it (tests/test_gpu_device_env_fp16_search.py runs on pre-filled memory)
+    // by pack_generic16_kernel before mcts_env16_kernel reads it (tests/test_gpu_device_env_fp16_search.py runs on pre-filled memory).
+    // f32 under a view of a one-common-layer policy: its block of EngineV layers in the same place, as in the PPO collect
     const size_t o_img = cur;
-    cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
+    cur = (cur + image_halves * sizeof(_Float16) + basic_block_bytes(pd) + 255) / 256 * 256;
     rc = check_memory_fit(cur, "tw_az_collect_device_env"); if (rc) return rc;
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
     uint8_t *ws = reinterpret_cast<uint8_t *>(wsp);
     EnvMctsArgs ma{};
     ma.struct_bytes = (uint32_t)sizeof(EnvMctsArgs);
-    ma.pol = *pd;
+    ma.pol = launch_policy(pd, ws + o_img);
     ma.out.rec = reinterpret_cast<PaddedRec *>(ws + o_rec); ma.out.ep_len = reinterpret_cast<uint32_t *>(ws + o_len); ma.out.t_pad = (int32_t)t_pad;
     ma.obs16 = reinterpret_cast<uint16_t *>(ws + o_obs16);
     ma.err = reinterpret_cast<uint32_t *>(ws + o_total + 8); ma.eval_count = reinterpret_cast<unsigned long long *>(ws + o_total + 16);
@@ -621,9 +657,10 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
     // fp16: the binary16 weight image behind o_act, appended as the fp16 collect appends its own (f32: no bytes, and nothing moves).
     // Every half of it is written by pack_generic16_kernel before solve_env16_kernel reads it; tests/test_gpu_device_env_fp16_solve.py
     // runs the call on pre-filled workspace memory for this region.  fp16x2: the split image in the same place, every half of it
-    // written by pack_generic16x2_kernel (tests/test_gpu_device_env_fp16x2_solve.py)
+    // written by pack_generic16x2_kernel (tests/test_gpu_device_env_fp16x2_solve.py).  f32 under a view of a one-common-layer policy
+    // (the callers' kernel_policy): its block of EngineV layers in the same place, every byte of it written by pack_basic_view_kernel
     const size_t o_img = cur;
-    cur = (cur + image_halves * sizeof(_Float16) + 255) / 256 * 256;
+    cur = (cur + image_halves * sizeof(_Float16) + basic_block_bytes(pd) + 255) / 256 * 256;
     if (mcts) { rc = check_memory_fit(cur, who); if (rc) return rc; }
     void *wsp = nullptr;
     rc = workspace_reserve(cur, &wsp); if (rc) return rc;
@@ -634,7 +671,7 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
         // MCTS-guided attempts (solve.rs:41-47): mcts_env_kernel in solve mode, one column = one attempt
         EnvMctsArgs ma{};
         ma.struct_bytes = (uint32_t)sizeof(EnvMctsArgs);
-        ma.pol = *pd; ma.num_columns = NA; ma.episode_offset = episode_offset; ma.seed = prm->seed;
+        ma.pol = launch_policy(pd, ws + o_img); ma.num_columns = NA; ma.episode_offset = episode_offset; ma.seed = prm->seed;
         ma.num_searches = prm->num_mcts_searches; ma.max_expand_depth = prm->max_expand_depth; ma.C = prm->C; ma.node_cap = (uint32_t)node_cap;
         ma.arena = ws + o_arena; ma.err = reinterpret_cast<uint32_t *>(ws + o_err); ma.eval_count = reinterpret_cast<unsigned long long *>(ws + o_err + 8);
         ma.col_err = reinterpret_cast<uint32_t *>(ws + o_ce);
@@ -649,7 +686,7 @@ int attempts_device_env(const char *who, const tw_device_env *env, const void *p
         note_launch(TW_KERNEL_MCTS_BIG, 1, (int)env->engine_nc, f16 ? 16 : 0, 0, false, true, false, false, (uint32_t)blocks, 256);
     } else {
         EnvSolveArgs sa{};
-        sa.pol = *pd; sa.num_attempts = NA; sa.episode_offset = episode_offset; sa.seed = prm->seed;
+        sa.pol = launch_policy(pd, ws + o_img); sa.num_attempts = NA; sa.episode_offset = episode_offset; sa.seed = prm->seed;
         sa.num_searches = (uint32_t)N; sa.deterministic = prm->deterministic ? 1u : 0u; sa.max_steps = max_steps;
         sa.success = reinterpret_cast<float *>(ws + o_s); sa.total = reinterpret_cast<float *>(ws + o_t);
         sa.n_steps = reinterpret_cast<uint32_t *>(ws + o_n); sa.err = reinterpret_cast<uint32_t *>(ws + o_err);
@@ -734,7 +771,8 @@ extern "C" int tw_evaluate_device_env(const tw_device_env *env, const void *prot
     int rc = check_descriptor(env, proto, proto_bytes, "tw_evaluate_device_env"); if (rc) return rc;
     note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);
     const tw_env_vtable vt = host_table(env, proto);
-    const PolicyDev *pd = policy_dev(policy);
+    PolicyDev view;                                                       // (as the PPO collect)
+    const PolicyDev *pd = kernel_policy(env, policy_dev(policy), prm->precision, &view);
     uint64_t node_cap = 0;
     if (!attempts_on_device(env, pd, prm, num_episodes, max_steps, &node_cap))
         return tw_evaluate_env(&vt, policy, prm, num_episodes, episode_offset, max_steps, success_rate, mean_reward);
@@ -759,7 +797,8 @@ extern "C" int tw_solve_device_env(const tw_device_env *env, const void *proto, 
     int rc = check_descriptor(env, proto, proto_bytes, "tw_solve_device_env"); if (rc) return rc;
     note_launch(TW_KERNEL_NONE, 0, 0, 0, 0, false, false, false, false, 0, 0);
     const tw_env_vtable vt = host_table(env, proto);
-    const PolicyDev *pd = policy_dev(policy);
+    PolicyDev view;                                                       // (as the PPO collect)
+    const PolicyDev *pd = kernel_policy(env, policy_dev(policy), prm->precision, &view);
     uint64_t node_cap = 0;
     if (!attempts_on_device(env, pd, prm, 1, max_steps, &node_cap) ||
         (uint64_t)prm->num_searches * (uint64_t)(max_steps ? max_steps : 1u) > SOLVE_ACTION_BYTES_MAX)

@@ -142,6 +142,10 @@ int launch_mcts_env(const EnvMctsArgs *a, const void *proto, unsigned blocks, si
     const void *k = reinterpret_cast<const void *>(&mcts_env_kernel<Env, NC>);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return (int)e;
+#ifdef TW_DEVICE_ENV_BASIC
+    const int eb = pack_basic_view_for(a->pol, s);        // (a view of a one-common-layer policy: as launch_rollout_env)
+    if (eb != (int)hipSuccess) return eb;
+#endif
     hipLaunchKernelGGL((mcts_env_kernel<Env, NC>), dim3(blocks), dim3(Eng::THREADS), lds_bytes, s, *a, p);
     return (int)hipGetLastError();
 }
@@ -160,7 +164,8 @@ int groups_per_cu_search_env(int kernel, size_t lds_bytes, int *out)
         return kernel_groups_per_cu(reinterpret_cast<const void *>(&mcts_env16_kernel<Env, NC>), EngineV16<NC>::THREADS, all16, out);
     }
 #endif
-    // (kernels 0, 1, 3, 5 and 6 -- solve_env16x2_kernel of TW_DEVICE_ENV_FP16X2_SOLVE -- are the plain module's, with its answers)
+    // (kernels 0, 1, 3, 5, 6 -- solve_env16x2_kernel of TW_DEVICE_ENV_FP16X2_SOLVE -- and 7 -- pack_basic_view_kernel of
+    // TW_DEVICE_ENV_BASIC -- are the plain module's, with its answers)
     if (kernel != 2) return groups_per_cu_env<Env>(kernel, lds_bytes, out);
     if (!out) return (int)hipErrorInvalidValue;
     const size_t all = lds_bytes + env_mcts_pending_bytes(Env::N_OBS) + env_mcts_probs_bytes(Env::NUM_ACTIONS);

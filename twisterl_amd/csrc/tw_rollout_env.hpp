@@ -18,6 +18,9 @@
 // (tw_engine_generic16x2.hpp), PPOCollector(precision="fp16x2"), f32 answers from split binary16 operands on the f16 matrix core.
 // One built with TW_DEVICE_ENV_FP16X2_SOLVE holds solve_env16x2_kernel<Env, NC> as well (tw_solve_env16x2.hpp): evaluate's loop over
 // EngineV16x2, collector.evaluate / collector.solve with precision="fp16x2" and no MCTS.
+// A module built with TW_DEVICE_ENV_BASIC holds pack_basic_view_kernel (tw_env_basic_view.hpp): its f32 launchers then also take the
+// reference's default policy -- one common layer, the "MFMA shape" -- as a view whose EngineV layers that kernel packs into the call's
+// workspace in front of every launch; the kernels themselves are the ones above, unchanged.
 //
 // In this file: the argument structs and the descriptor; what the steps call (the Gumbel arg-max, the twist of the actions, the
 // streaming steps of 5 .. 31 actions, env_rows / env_rows_n); the four kernels; their launchers and occupancy queries.  The two step
@@ -27,6 +30,7 @@
 #include "tw_engine_generic.hpp"
 #include "tw_engine_generic16.hpp"
 #include "tw_engine_generic16x2.hpp"
+#include "tw_env_basic_view.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -174,7 +178,12 @@ struct tw_device_env {
     // Kernel 6: solve_env16x2_kernel of a module built with TW_DEVICE_ENV_FP16X2_SOLVE (lds_bytes = EngineV16x2<engine_nc>::lds_bytes(pol));
     // any other module: hipErrorInvalidValue.  Kernel 6 with out == nullptr is that kernel's capability query (evaluate's and solve's
     // dispatch, DeviceEnv.fp16x2_solve): the library asks it BEFORE it hands launch_solve a split request -- bit 63 of
-    // EnvSolveArgs::image.halves -- so a module from before that kernel never sees one
+    // EnvSolveArgs::image.halves -- so a module from before that kernel never sees one.
+    // Kernel 7: pack_basic_view_kernel of a module built with TW_DEVICE_ENV_BASIC (tw_env_basic_view.hpp; lds_bytes is not used); any
+    // other module: hipErrorInvalidValue.  Kernel 7 with out == nullptr is the capability query (every entry point's dispatch,
+    // DeviceEnv.basic): the library asks it BEFORE it hands launch_rollout / launch_solve / launch_search a VIEW of a one-common-layer
+    // policy -- PolicyDev::generic with a non-zero PolicyDev::hidden, `layers` pointing at a block of the call's workspace that the
+    // launcher packs before its kernel -- so a module without that kernel never sees one.  No argument struct grew for it
     int (*groups_per_cu)(int kernel, size_t lds_bytes, int *out);
     // null unless the module was built with TW_DEVICE_ENV_FP16 (build_device_env(..., fp16=True)): pack_generic16_kernel (the policy's
     // f32 device copies -> the binary16 image a->image, on stream s) and then rollout_env16_kernel, with launch_rollout's return
@@ -470,6 +479,10 @@ int launch_rollout_env(const EnvRolloutArgs *a, const void *proto, unsigned bloc
     const void *k = reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return (int)e;
+#ifdef TW_DEVICE_ENV_BASIC
+    const int eb = pack_basic_view_for(a->pol, s);        // (a view of a one-common-layer policy: its EngineV layers first, on the same stream)
+    if (eb != (int)hipSuccess) return eb;
+#endif
     hipLaunchKernelGGL((rollout_env_kernel<Env, NC>), dim3(blocks), dim3(EngineV<NC>::THREADS), lds_bytes, s, *a, p);
     return (int)hipGetLastError();
 }
@@ -531,6 +544,10 @@ int groups_per_cu_env(int kernel, size_t lds_bytes, int *out)
     // kernel 6: solve_env16x2_kernel, lds_bytes = EngineV16x2<engine_nc>::lds_bytes(pol); out == nullptr: the capability query
     if (kernel == 6) return groups_per_cu_solve_env16x2<Env>(lds_bytes, out);
 #endif
+#ifdef TW_DEVICE_ENV_BASIC
+    // kernel 7: pack_basic_view_kernel (tw_env_basic_view.hpp); out == nullptr: the capability query
+    if (kernel == ENV_KERNEL_PACK_BASIC) return groups_per_cu_pack_basic(out);
+#endif
     if (!out || (kernel != 0 && kernel != 1)) return (int)hipErrorInvalidValue;
     const void *k = kernel == 0 ? reinterpret_cast<const void *>(&rollout_env_kernel<Env, NC>) : reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
     return kernel_groups_per_cu(k, EngineV<NC>::THREADS, lds_bytes, out);
@@ -564,6 +581,10 @@ int launch_solve_env(const EnvSolveArgs *a, const void *proto, unsigned blocks, 
     const void *k = reinterpret_cast<const void *>(&solve_env_kernel<Env, NC>);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return (int)e;
+#ifdef TW_DEVICE_ENV_BASIC
+    const int eb = pack_basic_view_for(a->pol, s);        // (as launch_rollout_env)
+    if (eb != (int)hipSuccess) return eb;
+#endif
     hipLaunchKernelGGL((solve_env_kernel<Env, NC>), dim3(blocks), dim3(EngineV<NC>::THREADS), lds_bytes, s, *a, p);
     return (int)hipGetLastError();
 }

@@ -245,6 +245,8 @@ class DeviceEnv:
     one built with fp16_search=True beside a search form AZCollector(precision="fp16").collect and evaluate / solve WITH MCTS (`fp16_search`),
     one built with fp16x2=True PPOCollector(precision="fp16x2").collect, f32 answers from split binary16 operands (`fp16x2`),
     one built with fp16x2_solve=True collector.evaluate / collector.solve with precision="fp16x2" and no MCTS as well (`fp16x2_solve`);
+    a policy of ONE common layer of 32 / 64 / 128 / 256 units with obs_size <= 256 (the reference's default) runs host-stepped in all
+    of these unless the module was built with basic=True (`basic`), which takes it into the f32 kernels;
     a module built with build_device_env(..., search=True) (1..4 actions; wide_search=True: 1..31) runs AZCollector.collect and evaluate with MCTS inside one kernel too
     (tw_az_collect_device_env; `search` says whether the module has that kernel), any other module steps the same struct's host
     code for those (tw_az_collect_env / tw_evaluate_env).  solve runs from the object's CURRENT state in one kernel as evaluate does
@@ -353,6 +355,14 @@ class DeviceEnv:
         precision="fp16x2" and no MCTS run on the device, f32 answers from split binary16 operands.  Asked like fp16_solve --
         groups_per_cu(6, 0, null) -- so it works on a machine without a GPU."""
         return int(self._desc.groups_per_cu(6, 0, None)) == 0
+
+    @property
+    def basic(self) -> bool:
+        """The module holds the kernel that packs the EngineV layers of a one-common-layer policy (built with basic=True): under the
+        reference's default policy -- one common layer of 32 / 64 / 128 / 256 units, obs_size <= 256 -- the module's f32 kernels run
+        on the device instead of the host-stepped path.  Asked like fp16_solve -- groups_per_cu(7, 0, null) -- so it works on a
+        machine without a GPU."""
+        return int(self._desc.groups_per_cu(7, 0, None)) == 0
 
     @property
     def variable_obs(self) -> bool:
